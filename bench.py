@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0  # MI355X spec
 
 
 def parse():
@@ -56,12 +56,37 @@ def parse():
     ap.add_argument("--scaling", default="strong", choices=("strong", "weak"),
                     help="strong: the cluster of --pools pools over N GPUs (the default: BASELINE's metric); weak: --pools pools PER GPU — a cluster of N x --pools "
                          "pools with N x the jobs, tasks and offers (what uses a node: one pool is one chain, DESIGN.md 8)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed cycle returned (per pool: rank order, job -> offer, head matched; the "
+                         "pool, quota-group and per-user usage) as DIR/<name>.npy in float64, at most 64 MB in all (a fixed, seeded sample of each "
+                         "array beyond that); the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--no-check", action="store_true", help="skip the parity check of the timed configuration (rank 0's first and last pool vs the oracle, after the timed region)")
     # rehearsal of the multi-process path on a machine without GPUs (tests/test_sharding_gloo.py): the engines load the given build of
     # the library (the SIMT emulator, test infrastructure) and the collectives run over gloo.  Never a bench line: `data` says so.
     ap.add_argument("--engine-lib", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"), help=argparse.SUPPRESS)
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit):
+    """arrays: name -> array of one step's results.  Written as float64 (exact for every index and count here); when the whole would pass
+    `limit` bytes, every array is cut by the same fraction to a sample at sorted positions drawn by a generator seeded with its name,
+    so that the same arguments give the same positions in every run."""
+    import zlib
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = min(1.0, (limit - 128 * len(arrays)) / max(1, total))  # (128: the header of a .npy file)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in sorted(arrays.items()):
+        if keep < 1.0 and a.ndim > 0:
+            m = max(1, int(len(a) * keep))
+            rows = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(len(a), size=m, replace=False))
+            a = a[rows]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return keep < 1.0
 
 
 # match_walkers / match_serve_*: the served form of the same three phases (one persistent walker workgroup per pool, ONE launch per cycle,
@@ -382,7 +407,6 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
         sys.exit(2)
     os.environ.setdefault("COOK_POOL_USAGE_MEMO", "0")  # the timed cycles sum the pools' running usage every time, as a live cycle (a new task table) does
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # one hardware queue per pool stream (read at HIP initialisation; see cook_amd/engine.py)
     os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # (the default of this ROCm build; see cook_amd/engine.py)
     import torch
     import torch.distributed as dist
@@ -484,13 +508,24 @@ def main():
     matched = considered = ranked_n = 0
     stage_ms = {}
     fetched = {}
+    heads = {}
     for p in my_pools:
         r, j2o, head = engines[p].cycle_fetch()
         fetched[p] = (r, j2o)
+        heads[p] = head
         ranked_n += len(r)
         considered += len(j2o)
         matched += int((j2o >= 0).sum())
         stage_ms[p] = engines[p].last_timing()
+    if args.dump_outputs:  # (before the roofline pass: its cycles replace the usage the cluster holds)
+        dump = {}
+        for p in my_pools:
+            dump.update({f"pool{p}_ranked": fetched[p][0], f"pool{p}_job_to_offer": fetched[p][1], f"pool{p}_head_matched": heads[p],
+                         f"pool{p}_pool_usage": cluster.last_pool_usage[p]})
+        if rank == 0:
+            dump.update(group_usage=cluster.last_group_usage, user_usage=cluster.last_user_usage)
+        sampled = dump_outputs(args.dump_outputs, dump, DUMP_LIMIT_BYTES // world)  # (every rank writes its own pools)
+        mark(f"outputs of the last timed cycle in {args.dump_outputs}" + (" (sampled)" if sampled else ""))
     timed_stats = engines[my_pools[0]].match_stats()  # of the LAST TIMED cycle (the extras below run other forms)
     timed_form = timed_stats.get("placement_form", 0)
     cnt = torch.tensor([matched, considered, ranked_n], dtype=torch.float64, device=cdev)

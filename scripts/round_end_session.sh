@@ -8,7 +8,6 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$ROOT"
-export GPU_MAX_HW_QUEUES=8
 python scripts/kernel_rev.py > "$OUT/kernel_rev.txt"; cat "$OUT/kernel_rev.txt"
 bash scripts/profile_round2.sh "$TAG" > "$OUT/profile.log" 2>&1; tail -5 "$OUT/profile.log"
 cd "$ROOT"

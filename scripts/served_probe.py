@@ -4,7 +4,6 @@ a list of environment settings (read by the library at every match).  usage: ser
 import os, sys, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 import torch
 from cook_amd import _abi as A, workload, sharding

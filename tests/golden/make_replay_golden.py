@@ -1,19 +1,19 @@
 #!/usr/bin/env python3
 """Builds tests/golden/replay_example.json from the reference's OWN recorded simulator run
-(/root/reference/scheduler/simulator_files/: example-trace.json + example-hosts.json + example-config.edn in,
+(scheduler/simulator_files/ of the reference, stored unchanged in tests/golden/simulator_files/: example-trace.json + example-hosts.json + example-config.edn in,
 example-out-trace.csv out — the output of the real Clojure scheduler with the real Fenzo over that trace).
 
 The fixture holds what the replay needs of the inputs (per job: uuid, user, cpus, mem, priority, submit / run time; per host:
 name, slave id, cpus, mem; the config's keys) and, per task row of the recorded output: hostname, status, and the cycle (of
 cycle-step-ms = 30 s) in which the task started / was seen finished.  Times are compared by cycle because the reference's
 frozen clock advances 1 ms per operation inside a cycle (zz_simulator.clj:455-480), which is bookkeeping, not a decision.
-Run here (the reference checkout is not present on the GPU box): python tests/golden/make_replay_golden.py"""
+Run: python tests/golden/make_replay_golden.py"""
 import csv
 import json
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference/scheduler/simulator_files"
+REF = os.path.join(HERE, "simulator_files")
 STEP = 30000  # :cycle-step-ms of example-config.edn
 
 

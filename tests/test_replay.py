@@ -61,14 +61,12 @@ def test_replay_parity_emulated_with_preemption(emu_engine):
 
 
 def test_replay_fixture_is_the_reference_checkout():
-    """tests/golden/replay_example.json == what tests/golden/make_replay_golden.py derives from the reference's files now
-    (this container only; the GPU box has no checkout and uses the committed fixture)"""
-    base = "/root/reference/scheduler/simulator_files"
-    if not os.path.exists(os.path.join(base, "example-out-trace.csv")):
-        pytest.skip("reference checkout not present")
+    """tests/golden/replay_example.json == what tests/golden/make_replay_golden.py derives from the reference's recorded run
+    (its simulator_files, stored unchanged under tests/golden/simulator_files/)"""
     import csv
     import json
     from tests import golden_util as G
+    base = os.path.join(G.GOLDEN, "simulator_files")
     fx = json.load(open(os.path.join(G.GOLDEN, "replay_example.json")))
     trace = replay.load_trace(os.path.join(base, "example-trace.json"))
     assert [j["job/uuid"] for j in fx["trace"]] == [j["job/uuid"] for j in trace] and len(trace) == 119
