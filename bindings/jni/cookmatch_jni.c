@@ -387,6 +387,55 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_rankPoolUsageMulti(JNIEnv* env, jcla
   for (i = 0; i < n; ++i) es[i] = H(hs[i]);
   return cook_rank_pool_usage_multi(es, (uint32_t)n, out);
 }
+/* set-stats-counters! (monitor.clj:177-207) from the last rank: limits = the 7 pointer fields of cook_user_limits (share_cpus, share_mem,
+ * quota_count, quota_cpus, quota_mem, quota_gpus, extra_quota_positive or null), n_users = the engine's staged users (the engine checks);
+ * per_user_out = direct buffer of n_users x 12 doubles or null, state_out = n_users bytes or null, totals_out = one cook_user_stats_totals */
+static cook_user_limits limits_of(JNIEnv* env, jint n, jobjectArray a, int* bad) {
+  cook_user_limits l;
+  l.n = (uint32_t)n;
+  l.share_cpus = (const double*)elem_n(env, a, 0, (uint64_t)n * sizeof(const double), bad);
+  l.share_mem = (const double*)elem_n(env, a, 1, (uint64_t)n * sizeof(const double), bad);
+  l.quota_count = (const double*)elem_n(env, a, 2, (uint64_t)n * sizeof(const double), bad);
+  l.quota_cpus = (const double*)elem_n(env, a, 3, (uint64_t)n * sizeof(const double), bad);
+  l.quota_mem = (const double*)elem_n(env, a, 4, (uint64_t)n * sizeof(const double), bad);
+  l.quota_gpus = (const double*)elem_n(env, a, 5, (uint64_t)n * sizeof(const double), bad);
+  l.extra_quota_positive = (const uint8_t*)elem_n(env, a, 6, (uint64_t)n * sizeof(const uint8_t), bad);
+  return l;
+}
+JNIEXPORT jint JNICALL Java_cook_hip_Native_userStats(JNIEnv* env, jclass c, jlong h, jint n_users, jobjectArray limits, jobject per_user_out,
+                                                      jobject state_out, jobject totals_out) {
+  int bad = 0;
+  cook_user_limits l = limits_of(env, n_users, limits, &bad);
+  double* pu = BUFN(double, per_user_out, (uint64_t)(n_users > 0 ? n_users : 0) * 12u);
+  uint8_t* st = BUFN(uint8_t, state_out, n_users > 0 ? n_users : 0);
+  cook_user_stats_totals* t = BUF(cook_user_stats_totals, totals_out);
+  (void)c;
+  if (!limits || n_users < 0) return COOK_E_INVALID;
+  return CHECKED(cook_user_stats(H(h), &l, pu, 0, st, t));
+}
+/* ... of a quota group whose pools are n engines of one device (cook_user_stats_multi): user_maps = n direct buffers of the engines'
+ * staged users' group ids (a null array or element: the identity; their length is the engine's user count, which only the engine knows),
+ * n_users / limits / outputs as userStats over the group's users */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_userStatsMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n,
+                                                           jobjectArray user_maps, jint n_users, jobjectArray limits, jobject per_user_out,
+                                                           jobject state_out, jobject totals_out) {
+  cook_engine* es[64];
+  const uint32_t* maps[64];
+  int bad = 0;
+  const int64_t* hs = BUFN(const int64_t, handles, n > 0 ? n : 0);
+  cook_user_limits l = limits_of(env, n_users, limits, &bad);
+  double* pu = BUFN(double, per_user_out, (uint64_t)(n_users > 0 ? n_users : 0) * 12u);
+  uint8_t* st = BUFN(uint8_t, state_out, n_users > 0 ? n_users : 0);
+  cook_user_stats_totals* t = BUF(cook_user_stats_totals, totals_out);
+  jint i;
+  (void)c;
+  if (bad || !hs || !limits || n <= 0 || n > 64 || n_users < 0) return COOK_E_INVALID;
+  for (i = 0; i < n; ++i) {
+    es[i] = H(hs[i]);
+    maps[i] = (const uint32_t*)elem_n(env, user_maps, i, 0, &bad);
+  }
+  return CHECKED(cook_user_stats_multi(es, (uint32_t)n, maps, (uint32_t)n_users, &l, pu, 0, st, t));
+}
 JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleMatchMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n) {
   cook_engine* es[64];
   int bad = 0;

@@ -850,3 +850,65 @@ def why_reasons(summary: dict) -> list:
     out = [dict(reason=f"Not enough {k} available.", host_count=v) for k, v in summary.get(":resources", {}).items()]
     out += [dict(reason=CONSTRAINT_MESSAGES.get(k, k), host_count=v) for k, v in summary.get(":constraints", {}).items()]
     return out
+
+
+# ---- user statistics (cook_user_stats*: set-stats-counters!, monitor.clj:40-116, 177-207) ---------------------------------------------
+USER_STATS_STATES = ("running", "waiting", "starved", "waiting-under-quota")  # the rows of per_user[u] and of totals.all
+USTAT_RUNNING, USTAT_WAITING, USTAT_STARVED, USTAT_UNDER_QUOTA = 1, 2, 4, 8   # user_state bits
+USER_STATS_COUNTS = ("total", "starved", "waiting-under-quota", "hungry", "satisfied")
+
+
+class CookUserLimits(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("share_cpus", _f64p), ("share_mem", _f64p), ("quota_count", _f64p), ("quota_cpus", _f64p),
+                ("quota_mem", _f64p), ("quota_gpus", _f64p), ("extra_quota_positive", _u8p)]
+
+
+class CookUserStatsTotals(C.Structure):
+    _fields_ = [("all", (C.c_double * 3) * 4), ("total", C.c_uint32), ("starved", C.c_uint32), ("waiting_under_quota", C.c_uint32),
+                ("hungry", C.c_uint32), ("satisfied", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+@dataclass
+class UserLimits:
+    """get-shares [:cpus :mem] (share.clj:123; unset = DMAX) and get-quota (quota.clj:82-110; :count unset = 2^31 - 1) per user id;
+    extra_quota_positive: every other quota key (the launch-rate quotas) > 0, None = all."""
+    share_cpus: np.ndarray
+    share_mem: np.ndarray
+    quota_count: Optional[np.ndarray] = None
+    quota_cpus: Optional[np.ndarray] = None
+    quota_mem: Optional[np.ndarray] = None
+    quota_gpus: Optional[np.ndarray] = None
+    extra_quota_positive: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        n = len(self.share_cpus)
+        full = lambda v: np.full(n, v, dtype=np.float64)  # noqa: E731
+        self.share_cpus = _arr(self.share_cpus, np.float64, n)
+        self.share_mem = _arr(self.share_mem, np.float64, n)
+        self.quota_count = _arr(self.quota_count if self.quota_count is not None else full(2.0 ** 31 - 1), np.float64, n)
+        self.quota_cpus = _arr(self.quota_cpus if self.quota_cpus is not None else full(DMAX), np.float64, n)
+        self.quota_mem = _arr(self.quota_mem if self.quota_mem is not None else full(DMAX), np.float64, n)
+        self.quota_gpus = _arr(self.quota_gpus if self.quota_gpus is not None else full(DMAX), np.float64, n)
+        self.extra_quota_positive = _arr(self.extra_quota_positive, np.uint8, n)
+
+    @property
+    def n(self):
+        return len(self.share_cpus)
+
+    @staticmethod
+    def from_users(users: "Users") -> "UserLimits":
+        """what a NULL limits argument means: the staged users' DRU divisors as shares, their quotas as they are"""
+        return UserLimits(users.div_cpus, users.div_mem, users.quota_count, users.quota_cpus, users.quota_mem, users.quota_gpus)
+
+    def as_struct(self) -> CookUserLimits:
+        return CookUserLimits(self.n, _ptr(self.share_cpus, _f64p), _ptr(self.share_mem, _f64p), _ptr(self.quota_count, _f64p),
+                              _ptr(self.quota_cpus, _f64p), _ptr(self.quota_mem, _f64p), _ptr(self.quota_gpus, _f64p),
+                              _ptr(self.extra_quota_positive, _u8p))
+
+
+def user_stats_result(per_user: np.ndarray, state: np.ndarray, totals: CookUserStatsTotals) -> dict:
+    """the outputs of cook_user_stats* as a dict: per_user [U, 4, 3] ({jobs, cpus, mem} of running, waiting, starved,
+    waiting-under-quota; zeros where the user is absent from that state), state [U] (USTAT_* bits), all [4, 3], counts"""
+    return dict(per_user=per_user, state=state, all=np.array([[totals.all[s][k] for k in range(3)] for s in range(4)]),
+                counts={"total": totals.total, "starved": totals.starved, "waiting-under-quota": totals.waiting_under_quota,
+                        "hungry": totals.hungry, "satisfied": totals.satisfied})

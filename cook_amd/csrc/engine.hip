@@ -130,6 +130,7 @@ struct ConsBufs;   // considerable_host.hpp
 struct OfferBufs;  // offers_host.hpp
 struct ExplainBufs;  // explain_host.hpp
 struct UpdateBufs;   // cycle_update.hpp
+struct UserStatsBufs;  // user_stats_host.hpp
 
 }  // namespace
 
@@ -253,6 +254,7 @@ struct cook_engine {
   // ---- why-unscheduled summaries / match-cycle metrics (allocated on first use) ----
   ExplainBufs* xb = nullptr;
   UpdateBufs* ub = nullptr;  // cook_cycle_update (allocated on first use)
+  UserStatsBufs* usb = nullptr;  // cook_user_stats* (allocated on first use)
   MatchIn last_in{};  // the MatchIn of the last match run (K, j_index as used)
   bool last_in_valid = false;
   unsigned rlog_id = 0;  // suffix of this engine's COOK_ROUND_LOG file
@@ -2042,6 +2044,7 @@ struct StageTimer {
 #include "offers_host.hpp"
 #include "explain_host.hpp"
 #include "cycle_update.hpp"
+#include "user_stats_host.hpp"
 
 ConsBufs& cons_bufs(cook_engine* e) {
   if (!e->cb) e->cb = new ConsBufs();
@@ -2182,6 +2185,8 @@ void cook_engine_destroy(cook_engine* e) {
   e->xb = nullptr;
   delete e->ub;
   e->ub = nullptr;
+  delete e->usb;
+  e->usb = nullptr;
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -2507,6 +2512,23 @@ int cook_rank_pool_usage_multi(cook_engine** engines, uint32_t n, cook_usage* ou
   for (uint32_t i = 0; i < n; ++i)
     if (flow_err[i].first != COOK_OK) engines[i]->err = flow_err[i].second;
   return rc != COOK_OK ? rc : flows_rc;
+}
+int cook_user_stats(cook_engine* e, const cook_user_limits* limits, double* per_user, int per_user_is_device, uint8_t* user_state,
+                    cook_user_stats_totals* totals) {
+  if (!e) return COOK_E_INVALID;
+  return guarded(e, [&] { user_stats_run(&e, 1, nullptr, e->U, limits, per_user, per_user_is_device != 0, user_state, totals); });
+}
+int cook_user_stats_multi(cook_engine** engines, uint32_t n, const uint32_t* const* user_map, uint32_t n_users, const cook_user_limits* group_limits,
+                          double* per_user, int per_user_is_device, uint8_t* user_state, cook_user_stats_totals* totals) {
+  if (!engines || n == 0 || !group_limits) return COOK_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!engines[i] || engines[i]->device != engines[0]->device) return COOK_E_INVALID;
+    for (uint32_t k = 0; k < i; ++k)
+      if (engines[i] == engines[k]) return COOK_E_INVALID;
+  }
+  return guarded(engines[0], [&] {
+    user_stats_run(engines, n, user_map, n_users, group_limits, per_user, per_user_is_device != 0, user_state, totals);
+  });
 }
 int cook_cycle_match_multi(cook_engine** engines, uint32_t n) {
   if (!engines || n == 0 || !engines[0]) return COOK_E_INVALID;

@@ -113,6 +113,7 @@ class Engine:
     def rank_stage(self, tasks: A.Tasks, users: A.Users):
         ts, us = tasks.as_struct(), users.as_struct()
         self._rank_n, self._rank_np = tasks.n, int(tasks.pending.sum()) if tasks.n else 0
+        self._n_users = users.n
         self._chk(self._lib.cook_rank_stage(self._h, C.byref(ts), C.byref(us)))
 
     def rank_set_quota(self, quota: Optional[A.CookPoolQuota]):
@@ -132,6 +133,16 @@ class Engine:
         out = np.zeros((max(1, n_users), 3), dtype=np.float64)
         self._chk(self._lib.cook_rank_user_usage(self._h, _p(out, C.c_double), 0))
         return out[:n_users]
+
+    def user_stats(self, limits: Optional[A.UserLimits] = None, per_user_device_ptr: Optional[int] = None) -> dict:
+        """set-stats-counters!'s numbers for this pool from the last rank run (cook_user_stats): a dict of per_user [U, 4, 3], state [U],
+        all [4, 3] and the five counts (cook_amd._abi.user_stats_result).  limits None: the staged users' divisors as shares and their
+        quotas.  per_user_device_ptr: the per-user rows go to that device buffer of U x 12 doubles instead (per_user is None then)."""
+        n = limits.n if limits is not None else getattr(self, "_n_users", 0)
+        lim = C.byref(limits.as_struct()) if limits is not None else None
+        out = _StatsOut(n, per_user_device_ptr)
+        _check_multi([self], self._lib.cook_user_stats(self._h, lim, *out.args()))
+        return out.result()
 
     def rank_run(self):
         self._chk(self._lib.cook_rank_run(self._h))
@@ -189,6 +200,7 @@ class Engine:
     def cycle_stage(self, tasks: A.Tasks, users: A.Users, pending_jobs: A.Jobs, offers: A.Offers,
                     groups: Optional[A.Groups] = None, reserved_hosts: Sequence[int] = ()):
         ts, us, js, os_ = tasks.as_struct(), users.as_struct(), pending_jobs.as_struct(), offers.as_struct()
+        self._n_users = users.n
         gs = groups.as_struct() if groups is not None else None
         res = np.array(list(reserved_hosts) or [0], dtype=np.uint32)
         self._rank_n, self._rank_np = tasks.n, int(tasks.pending.sum()) if tasks.n else 0
@@ -390,6 +402,7 @@ class Engine:
                                  reserved_hosts: Sequence[int] = (), with_task_limits: bool = False):
         """cook_cycle_stage with the rows of the last offers_run as offers, in place on the device."""
         ts, us, js = tasks.as_struct(), users.as_struct(), pending_jobs.as_struct()
+        self._n_users = users.n
         gs = groups.as_struct() if groups is not None else None
         res = np.array(list(reserved_hosts) or [0], dtype=np.uint32)
         self._rank_n, self._rank_np = tasks.n, int(tasks.pending.sum()) if tasks.n else 0
@@ -493,6 +506,49 @@ def rank_pool_usage_multi(engines: Sequence[Engine]):
                 e._chk(rc)
         engines[0]._chk(rc)
     return [u.as_tuple() for u in out]
+
+
+class _StatsOut:
+    """the output buffers of one cook_user_stats* call"""
+
+    def __init__(self, n, device_ptr):
+        self.n, self.device_ptr = n, device_ptr
+        self.per_user = np.zeros((max(1, n), 4, 3), dtype=np.float64)
+        self.state = np.zeros(max(1, n), dtype=np.uint8)
+        self.totals = A.CookUserStatsTotals()
+
+    def args(self):
+        pu = C.c_void_p(int(self.device_ptr)) if self.device_ptr is not None else self.per_user.ctypes.data_as(C.c_void_p)
+        return pu, int(self.device_ptr is not None), self.state.ctypes.data_as(C.c_void_p), C.byref(self.totals)
+
+    def result(self) -> dict:
+        return A.user_stats_result(self.per_user[:self.n] if self.device_ptr is None else None, self.state[:self.n], self.totals)
+
+
+def _check_multi(engines, rc):
+    if rc != 0:
+        for e in engines:  # the message is with the engine that failed
+            if e._lib.cook_last_error(e._h):
+                e._chk(rc)
+        engines[0]._chk(rc)
+
+
+def user_stats_multi(engines: Sequence[Engine], limits: A.UserLimits, user_maps: Optional[Sequence[Optional[np.ndarray]]] = None,
+                     per_user_device_ptr: Optional[int] = None) -> dict:
+    """user_stats of a quota group whose member pools are `engines` (one device; cook_user_stats_multi): user_maps[i] maps engine i's
+    user ids one-to-one into the group's limits.n users (None: the identity); per-user sums run over the pools' segments in the
+    engines' order."""
+    n = limits.n
+    lim = limits.as_struct()
+    arr = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    maps = None
+    if user_maps is not None:
+        ms = [np.ascontiguousarray(m, dtype=np.uint32) if m is not None else None for m in user_maps]
+        assert len(ms) == len(engines)
+        maps = (C.c_void_p * len(engines))(*[m.ctypes.data if m is not None else None for m in ms])
+    out = _StatsOut(n, per_user_device_ptr)
+    _check_multi(engines, engines[0]._lib.cook_user_stats_multi(arr, len(engines), maps, n, C.byref(lim), *out.args()))
+    return out.result()
 
 
 def cycle_run_rank_multi(engines: Sequence[Engine], num_considerable, user_usage_ptrs: Optional[Sequence[int]] = None,

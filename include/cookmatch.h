@@ -468,6 +468,58 @@ typedef struct cook_cycle_metrics {
 int cook_match_metrics(cook_engine* e, cook_cycle_metrics* out, uint32_t* user_considerable, uint32_t* user_matched, uint32_t n_users,
                        int64_t* job_gpus_by_model, int64_t* offer_gpus_by_model, uint32_t n_gpu_models);
 
+/* ---- USER STATISTICS: the arithmetic of set-stats-counters! (monitor.clj:40-116, 177-207) from the last rank, on the device --------
+ * Per user u and state s (0 running, 1 waiting, 2 starved, 3 waiting-under-quota): per_user[(u*4 + s)*3 + {0,1,2}] = {jobs, cpus, mem};
+ * a user absent from a state's map (monitor.clj builds maps) has zeros there and its bit clear in user_state[u] (COOK_USTAT_*).
+ *  - running / waiting (get-job-stats, :40-57): sums over the user's running / pending tasks of the engine's task table (cook_rank_stage,
+ *    cook_cycle_update) as the LAST rank run saw it.
+ *  - starved (:69-90): waiting, and running cpus < share cpus and running mem < share mem (absent running = 0.0); stats
+ *    (merge-with min waiting (merge-with - share running)): cpus = min(w.cpus, s.cpus - r.cpus), mem likewise, jobs = min(w.jobs,
+ *    r.jobs) — :jobs only exists in running, so with running stats it passes the first merge unchanged —, and without running stats
+ *    min(w, share) with jobs = w.jobs.
+ *  - waiting-under-quota (:92-116): waiting, and r.jobs < quota count, r.cpus < quota cpus, r.mem < quota mem, 0 < quota gpus and every
+ *    other quota key (the launch-rate quotas) > 0; stats min(w, max(quota - r, 0)) on jobs / cpus / mem (min(w, quota) without running
+ *    stats).  Only jobs / cpus / mem are returned: the reference's map also carries the user's gpus and launch-rate quotas unchanged,
+ *    which the host holds already.
+ *  - totals: the "all" row of each state (add-aggregated-stats, :59-67; all zeros when the map is empty) and the counts of :186-194 —
+ *    total |running u waiting|, starved, waiting-under-quota, hungry |waiting \ starved|, satisfied |running \ waiting|.
+ * Values are doubles; set-counter!'s (long (min v Long/MAX_VALUE)) is the host's.  Oracle-defined summation order (the reference's
+ * is Datomic query / hash-map order): per user left to right in the user's task order (tools.clj:614-641), running and pending tasks
+ * apart; "all" left to right in user-id order; bit-identical to those sequential sums for any fp64 inputs (exactness tracked, rounded
+ * sums folded again).  The rank, considerable and match state stay as they are: a cycle fetched afterwards is the one fetched before.
+ * Before any cook_rank_run / cook_cycle_run*, and after a cook_rank_stage or cook_cycle_update that no rank has followed (the rank's
+ * per-user order would describe the old table): COOK_E_STATE. */
+typedef struct cook_user_limits {
+  uint32_t n;                           /* users (the engine's U; n_users of the multi form)                                       */
+  const double* share_cpus;             /* [n] get-shares [:cpus :mem] (share.clj:123); unset = DBL_MAX                            */
+  const double* share_mem;
+  const double* quota_count;            /* [n] get-quota (quota.clj:82-110): :count, :cpus, :mem, :gpus                             */
+  const double* quota_cpus;
+  const double* quota_mem;
+  const double* quota_gpus;
+  const uint8_t* extra_quota_positive;  /* [n] every other quota key > 0, or NULL = all positive (the launch-rate defaults are)     */
+} cook_user_limits;
+typedef struct cook_user_stats_totals {
+  double all[4][3];                     /* the "all" row of running, waiting, starved, waiting-under-quota: {jobs, cpus, mem}          */
+  uint32_t total, starved, waiting_under_quota, hungry, satisfied, reserved;
+} cook_user_stats_totals;
+#define COOK_USTAT_RUNNING 1u
+#define COOK_USTAT_WAITING 2u
+#define COOK_USTAT_STARVED 4u
+#define COOK_USTAT_UNDER_QUOTA 8u
+/* limits NULL: the engine's staged cook_users (the DRU divisors as shares, the quotas as they are).  per_user (optional) [U][4][3];
+ * per_user_is_device != 0: per_user is a DEVICE pointer and nothing of it is copied to the host.  user_state (optional) [U]; totals
+ * (optional). */
+int cook_user_stats(cook_engine* e, const cook_user_limits* limits, double* per_user, int per_user_is_device, uint8_t* user_state,
+                    cook_user_stats_totals* totals);
+/* The same for a quota group (monitor.clj:35-38 job-ent-in-pool: the jobs of every member pool) whose pools are engines of ONE device:
+ * user_map[i] (NULL, or user_map[i] NULL: the identity) maps engine i's user ids one-to-one into the group's n_users; group_limits
+ * (required) are the group's own.  Per-user sums run over the concatenation of the member pools' segments in the order of `engines`.
+ * Engines on different devices, an engine twice, a map out of range or not one-to-one: COOK_E_INVALID. */
+int cook_user_stats_multi(cook_engine** engines, uint32_t n, const uint32_t* const* user_map, uint32_t n_users,
+                          const cook_user_limits* group_limits, double* per_user, int per_user_is_device, uint8_t* user_state,
+                          cook_user_stats_totals* totals);
+
 /* ---- OFFERS: replaces the numeric core of kubernetes.compute-cluster/generate-offers ----------------------
  * (kubernetes/compute_cluster.clj:68-190: available = capacity - consumption per node, the schedulable filter, the
  * offer resources and the capacity / consumption totals it publishes; kubernetes/api.clj:747-765 convert-resource-map,
