@@ -463,6 +463,25 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleFetch(JNIEnv* env, jclass c, jl
   if (rc || !pos) return rc;
   return cook_cycle_fetch_considerable(H(h), pos, 0);
 }
+/* handle-resource-offers-autoscaling-helper (scheduler.clj:1283-1335) from the last cycle (cook_cycle_autoscale): params = one
+ * cook_autoscale_params whose max_jobs, n_exclude and scale_factor are read (its two pointer fields are ignored: offer_skipped = n_offers
+ * bytes, the offers the cycle staged, or null; exclude = n_exclude task indices or null), task_idx_out = cap uint32 slots
+ * (max(max_jobs, n_pending) always suffices), info_out = one cook_autoscale_info */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleAutoscale(JNIEnv* env, jclass c, jlong h, jobject params, jint n_offers, jobject offer_skipped,
+                                                           jobject exclude, jobject task_idx_out, jint cap, jobject info_out) {
+  int bad = 0;
+  cook_autoscale_params p;
+  const cook_autoscale_params* in = BUF(const cook_autoscale_params, params);
+  uint32_t* out = BUFN(uint32_t, task_idx_out, cap > 0 ? cap : 0);
+  cook_autoscale_info* info = BUF(cook_autoscale_info, info_out);
+  (void)c;
+  if (bad || !in || n_offers < 0 || cap < 0 || in->n_exclude > 0x7fffffffu) return COOK_E_INVALID;
+  p = *in;
+  p.offer_skipped = BUFN(const uint8_t, offer_skipped, n_offers);
+  p.exclude_task = BUFN(const uint32_t, exclude, p.n_exclude);
+  if ((p.n_exclude && !p.exclude_task) || (cap && !out)) return COOK_E_INVALID;
+  return CHECKED(cook_cycle_autoscale(H(h), &p, out, (uint32_t)cap, info));
+}
 
 /* ---- rebalance: rebalancer/init-state + the rebalance loop's decisions ------------------------------------------------- */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_rebalance(JNIEnv* env, jclass c, jlong h, jint r, jobjectArray running,

@@ -912,3 +912,17 @@ def user_stats_result(per_user: np.ndarray, state: np.ndarray, totals: CookUserS
     return dict(per_user=per_user, state=state, all=np.array([[totals.all[s][k] for k in range(3)] for s in range(4)]),
                 counts={"total": totals.total, "starved": totals.starved, "waiting-under-quota": totals.waiting_under_quota,
                         "hungry": totals.hungry, "satisfied": totals.satisfied})
+
+
+# ---- autoscaling candidates (cook_cycle_autoscale: handle-resource-offers-autoscaling-helper, scheduler.clj:1283-1335) ----------------
+class CookAutoscaleParams(C.Structure):
+    _fields_ = [("max_jobs", C.c_uint32), ("n_exclude", C.c_uint32), ("scale_factor", C.c_double), ("offer_skipped", _u8p),
+                ("exclude_task", _u32p)]
+
+
+class CookAutoscaleInfo(C.Structure):
+    _fields_ = [("considered", C.c_uint32), ("matched", C.c_uint32), ("unmatched", C.c_uint32), ("scaled", C.c_uint32),
+                ("autoscalable", C.c_uint32), ("n_out", C.c_uint32), ("fraction_unmatched", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}

@@ -2,7 +2,20 @@
 // (included by engine.hip inside its anonymous namespace).
 #pragma once
 
-struct ConsBufs {
+// the work set of one run of the filters (cons_run_device): the considerable pass has one, cook_cycle_autoscale another
+struct ConsWork {
+  DArr<uint64_t> ukey;
+  DArr<uint32_t> permA, permB, g_user, seg_start, seg_end, inexact, rate_limited, passed, qitemA, qitemB;
+  DArr<uint8_t> head;
+  DArr<SumU4> g_use, pre, quseA, quseB, pusage;
+  DArr<int> flag1, keep_q;
+  DArr<SumI> scan;
+  // result
+  uint32_t* result = nullptr;  // device: queue positions of the surviving jobs
+  unsigned n_result = 0;
+};
+
+struct ConsBufs : ConsWork {  // the considerable pass's own work set, and the staged user state
   // user state (staged by cook_considerable / cook_cycle_set_considerable)
   bool users_staged = false;
   unsigned U = 0;
@@ -20,16 +33,6 @@ struct ConsBufs {
   DArr<double> q_cpus, q_mem, q_gpus;
   DArr<uint32_t> q_user;
   DArr<uint8_t> q_elig;
-  // work
-  DArr<uint64_t> ukey;
-  DArr<uint32_t> permA, permB, g_user, seg_start, seg_end, inexact, rate_limited, passed, qitemA, qitemB;
-  DArr<uint8_t> head;
-  DArr<SumU4> g_use, pre, quseA, quseB, pusage;
-  DArr<int> flag1, keep_q;
-  DArr<SumI> scan;
-  // result
-  uint32_t* result = nullptr;  // device: queue positions of the considerable jobs
-  unsigned n_result = 0;
 };
 
 void cons_stage_users(cook_engine* e, ConsBufs& c, const cook_user_state* us) {
@@ -58,10 +61,11 @@ void cons_stage_users(cook_engine* e, ConsBufs& c, const cook_user_state* us) {
   c.users_staged = true;
 }
 
-// the filters over a device-resident queue of n jobs; leaves the first min(K, survivors) queue positions in c.result
-void cons_run_device(cook_engine* e, ConsBufs& c, unsigned n, const double* q_cpus, const double* q_mem, const double* q_gpus,
-                     const uint32_t* q_user, const uint8_t* q_elig, unsigned K) {
-  const unsigned U = c.U;
+// the filters under the staged user state s over a device-resident queue of n jobs; leaves the first min(K, survivors) queue positions
+// in c.result (c: s itself for the considerable pass, a work set of its own for cook_cycle_autoscale)
+void cons_run_device(cook_engine* e, const ConsBufs& s, ConsWork& c, unsigned n, const double* q_cpus, const double* q_mem,
+                     const double* q_gpus, const uint32_t* q_user, const uint8_t* q_elig, unsigned K) {
+  const unsigned U = s.U;
   c.rate_limited.ensure(std::max(1u, U));
   c.passed.ensure(std::max(1u, U));
   memset_async(e, c.rate_limited.ptr(), 0, (size_t)std::max(1u, U) * 4);
@@ -90,21 +94,21 @@ void cons_run_device(cook_engine* e, ConsBufs& c, unsigned n, const double* q_cp
   KM<cons_gather, 256>(e, "cons_gather", gN, permU, n, q_user, q_cpus, q_mem, q_gpus, c.g_user.ptr(), c.g_use.ptr(), c.head.ptr(), c.seg_start.ptr(),
       c.seg_end.ptr());
   // ---- (i) per-user quota filter, seeded with the users' running usage (tools.clj:903-915) -------------------------------
-  LoadUserSeeded ld{c.g_use.ptr(), c.head.ptr(), c.g_user.ptr(), c.ucount.ptr(), c.ucpus.ptr(), c.umem.ptr(), c.ugpus.ptr()};
+  LoadUserSeeded ld{c.g_use.ptr(), c.head.ptr(), c.g_user.ptr(), s.ucount.ptr(), s.ucpus.ptr(), s.umem.ptr(), s.ugpus.ptr()};
   seg_scan<SumU4>(e, "cons_user_usage_scan", ld, (const uint8_t*)c.head.ptr(), n, c.pre.ptr(), e->tmpU4);
   KM<rank_mark_inexact, 256>(e, "rank_mark_inexact", gN, (const SumU4*)c.pre.ptr(), (const uint32_t*)c.g_user.ptr(), n, c.inexact.ptr());
   KM<cons_fix_inexact, 256>(e, "cons_fix_inexact", div_up(std::max(1u, U), 256), (const SumU4*)c.g_use.ptr(), c.pre.ptr(),
-      (const uint32_t*)c.seg_start.ptr(), (const uint32_t*)c.seg_end.ptr(), (const uint32_t*)c.inexact.ptr(), U, (const double*)c.ucount.ptr(),
-      (const double*)c.ucpus.ptr(), (const double*)c.umem.ptr(), (const double*)c.ugpus.ptr());
+      (const uint32_t*)c.seg_start.ptr(), (const uint32_t*)c.seg_end.ptr(), (const uint32_t*)c.inexact.ptr(), U, (const double*)s.ucount.ptr(),
+      (const double*)s.ucpus.ptr(), (const double*)s.umem.ptr(), (const double*)s.ugpus.ptr());
   c.flag1.ensure(n);
   c.keep_q.ensure(n);
   c.scan.ensure(n);
   KM<cons_user_quota_flag, 256>(e, "cons_user_quota_flag", gN, (const SumU4*)c.pre.ptr(), (const uint32_t*)c.g_user.ptr(), n,
-      (const double*)c.qcount.ptr(), (const double*)c.qcpus.ptr(), (const double*)c.qmem.ptr(), (const double*)c.qgpus.ptr(), c.flag1.ptr());
+      (const double*)s.qcount.ptr(), (const double*)s.qcpus.ptr(), (const double*)s.qmem.ptr(), (const double*)s.qgpus.ptr(), c.flag1.ptr());
   // ---- (ii) launch-rate limit: index of the job among its user's survivors (tools.clj:935-955) -----------------------------
   seg_scan<SumI>(e, "cons_user_index_scan", LoadI{c.flag1.ptr()}, (const uint8_t*)c.head.ptr(), n, c.scan.ptr(), e->tmpI);
   KM<cons_rate_limit, 256>(e, "cons_rate_limit", gN, (const int*)c.flag1.ptr(), (const SumI*)c.scan.ptr(), (const uint32_t*)c.g_user.ptr(), permU, n,
-      c.has_tokens ? (const int64_t*)c.tokens.ptr() : (const int64_t*)nullptr, c.enforce, c.keep_q.ptr(), c.rate_limited.ptr(), c.passed.ptr());
+      s.has_tokens ? (const int64_t*)s.tokens.ptr() : (const int64_t*)nullptr, s.enforce, c.keep_q.ptr(), c.rate_limited.ptr(), c.passed.ptr());
   // ---- survivors back in queue order ---------------------------------------------------------------------------------------------
   uint32_t* qitem = c.qitemA.ensure(n);
   uint32_t* qitem_o = c.qitemB.ensure(n);
@@ -115,12 +119,12 @@ void cons_run_device(cook_engine* e, ConsBufs& c, unsigned n, const double* q_cp
   memset_async(e, dlen, 0, 4);
   KM<cons_compact_queue, 256>(e, "cons_compact_queue", gN, (const int*)c.keep_q.ptr(), (const SumI*)c.scan.ptr(), n, q_cpus, q_mem, q_gpus, qitem, quse, dlen);
   // ---- (iii) pool quota, seeded with the pool usage (tools.clj:917-933, 966) -------------------------------------------------------
-  cook_usage base = c.pool_usage;
-  if (c.has_pool_quota && !c.pool_usage_given) {
+  cook_usage base = s.pool_usage;
+  if (s.has_pool_quota && !s.pool_usage_given) {
     c.pusage.ensure(1);
     if (U) {
-      KM<cons_pool_usage, 1024>(e, "cons_pool_usage", 1, (const double*)c.ucount.ptr(), (const double*)c.ucpus.ptr(), (const double*)c.umem.ptr(),
-          (const double*)c.ugpus.ptr(), U, c.pusage.ptr());
+      KM<cons_pool_usage, 1024>(e, "cons_pool_usage", 1, (const double*)s.ucount.ptr(), (const double*)s.ucpus.ptr(), (const double*)s.umem.ptr(),
+          (const double*)s.ugpus.ptr(), U, c.pusage.ptr());
       pinned_copy(e, e->h_scratch + 8, c.pusage.ptr(), sizeof(SumU4), hipMemcpyDeviceToHost);
     }
   }
@@ -128,12 +132,12 @@ void cons_run_device(cook_engine* e, ConsBufs& c, unsigned n, const double* q_cp
   sync(e);
   unsigned len = 0;
   std::memcpy(&len, e->h_scratch, 4);
-  if (c.has_pool_quota && !c.pool_usage_given) {
+  if (s.has_pool_quota && !s.pool_usage_given) {
     SumU4 h = SumU4::zero();
     if (U) std::memcpy(&h, e->h_scratch + 8, sizeof(SumU4));
     base = cook_usage{h.count, h.cpus, h.mem, h.gpus};
   }
-  if (len && c.has_pool_quota) len = queue_filter_quota(e, 2, len, c.pool_quota, base, qitem, quse, qitem_o, quse_o);
+  if (len && s.has_pool_quota) len = queue_filter_quota(e, 2, len, s.pool_quota, base, qitem, quse, qitem_o, quse_o);
   // ---- job-allowed-to-start? + launch plugin (host-evaluated mask), then take K (scheduler.clj:747-749) --------------------------------
   if (len && q_elig) {
     e->iflag.ensure(len);

@@ -131,6 +131,7 @@ struct OfferBufs;  // offers_host.hpp
 struct ExplainBufs;  // explain_host.hpp
 struct UpdateBufs;   // cycle_update.hpp
 struct UserStatsBufs;  // user_stats_host.hpp
+struct AutoscaleBufs;  // autoscale_host.hpp
 
 }  // namespace
 
@@ -244,6 +245,9 @@ struct cook_engine {
   MatchIn min{};
   bool cycle_staged = false;
   unsigned cycle_considered = 0;
+  // the last cycle ran the considerable filters under a staged user state, and nothing has replaced that state, the rank or the match
+  // since (cook_cycle_autoscale reads all three)
+  bool cycle_cons_ran = false;
 
   // ---- rebalancer state (allocated on first use) ----
   RebalBufs* rb = nullptr;
@@ -255,6 +259,7 @@ struct cook_engine {
   ExplainBufs* xb = nullptr;
   UpdateBufs* ub = nullptr;  // cook_cycle_update (allocated on first use)
   UserStatsBufs* usb = nullptr;  // cook_user_stats* (allocated on first use)
+  AutoscaleBufs* asb = nullptr;  // cook_cycle_autoscale (allocated on first use)
   MatchIn last_in{};  // the MatchIn of the last match run (K, j_index as used)
   bool last_in_valid = false;
   unsigned rlog_id = 0;  // suffix of this engine's COOK_ROUND_LOG file
@@ -861,6 +866,7 @@ void rank_run(cook_engine* e) {
   const unsigned N = e->N, U = e->U;
   e->n_ranked = 0;
   e->rank_done = false;
+  e->cycle_cons_ran = false;
   e->ranked.ensure(std::max(1u, e->n_pending));
   if (N == 0) {
     e->rank_done = true;
@@ -1196,6 +1202,7 @@ void match_stage_offers(cook_engine* e, const cook_offers* o) {
 void match_stage_inputs(cook_engine* e, const cook_jobs* j, const cook_offers* o, const cook_groups* g,
                         const uint32_t* reserved_hosts, uint32_t n_reserved, bool offers_dev = false) {
   if (!j || !o) e->fail(COOK_E_INVALID, "cook_match_stage: null jobs/offers");
+  e->cycle_cons_ran = false;
   const unsigned K = j->n, M = o->n, G = g ? g->n : 0;
   if (K && (!j->cpus || !j->mem)) e->fail(COOK_E_INVALID, "cook_match_stage: jobs need cpus and mem");
   if (M && (!o->cpus || !o->mem || !o->host)) e->fail(COOK_E_INVALID, "cook_match_stage: offers need cpus, mem and host");
@@ -2045,6 +2052,7 @@ struct StageTimer {
 #include "explain_host.hpp"
 #include "cycle_update.hpp"
 #include "user_stats_host.hpp"
+#include "autoscale_host.hpp"
 
 ConsBufs& cons_bufs(cook_engine* e) {
   if (!e->cb) e->cb = new ConsBufs();
@@ -2187,6 +2195,8 @@ void cook_engine_destroy(cook_engine* e) {
   e->ub = nullptr;
   delete e->usb;
   e->usb = nullptr;
+  delete e->asb;
+  e->asb = nullptr;
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -2365,8 +2375,9 @@ static unsigned cycle_rank_part(cook_engine* e, uint32_t num_considerable) {
           e->min.j_cpus, e->min.j_mem, e->min.j_gpus, (const uint32_t*)e->j_user.ptr(),
           c.has_elig_by_pending ? (const uint8_t*)c.elig_by_pending.ptr() : (const uint8_t*)nullptr, c.q_cpus.ptr(), c.q_mem.ptr(), c.q_gpus.ptr(),
           c.q_user.ptr(), c.q_elig.ptr());
-    cons_run_device(e, c, n, c.q_cpus.ptr(), c.q_mem.ptr(), c.q_gpus.ptr(), c.q_user.ptr(), c.q_elig.ptr(), num_considerable);
+    cons_run_device(e, c, c, n, c.q_cpus.ptr(), c.q_mem.ptr(), c.q_gpus.ptr(), c.q_user.ptr(), c.q_elig.ptr(), num_considerable);
     K = c.n_result;
+    e->cycle_cons_ran = true;
     e->j_index.ensure(K);
     if (K)
       KM<cons_job_index, 256>(e, "cons_job_index", div_up(K, 256), (const uint32_t*)c.result, (const uint32_t*)e->ranked.ptr(),
@@ -2572,6 +2583,7 @@ int cook_considerable(cook_engine* e, const cook_queue* q, const cook_user_state
     const unsigned n = q->n;
     if (n && (!q->cpus || !q->mem || !q->user)) e->fail(COOK_E_INVALID, "cook_considerable: the queue needs cpus, mem, user");
     ConsBufs& c = cons_bufs(e);
+    e->cycle_cons_ran = false;  // (the cycle's user state and considerable result are replaced)
     cons_stage_users(e, c, us);
     for (unsigned i = 0; i < n; ++i)
       if (q->user[i] >= c.U) e->fail(COOK_E_INVALID, "cook_considerable: user id out of range");
@@ -2580,7 +2592,7 @@ int cook_considerable(cook_engine* e, const cook_queue* q, const cook_user_state
     if (q->gpus) h2d(e, c.q_gpus, q->gpus, n);
     h2d(e, c.q_user, q->user, n);
     if (q->eligible) h2d(e, c.q_elig, q->eligible, n);
-    cons_run_device(e, c, n, c.q_cpus.ptr(), c.q_mem.ptr(), q->gpus ? (const double*)c.q_gpus.ptr() : (const double*)nullptr,
+    cons_run_device(e, c, c, n, c.q_cpus.ptr(), c.q_mem.ptr(), q->gpus ? (const double*)c.q_gpus.ptr() : (const double*)nullptr,
                     c.q_user.ptr(), q->eligible ? (const uint8_t*)c.q_elig.ptr() : (const uint8_t*)nullptr, num_considerable);
     if (c.n_result) copy_async(e, out_idx, c.result, (size_t)c.n_result * 4, hipMemcpyDeviceToHost);
     if (rate_limited && c.U) copy_async(e, rate_limited, c.rate_limited.ptr(), (size_t)c.U * 4, hipMemcpyDeviceToHost);
@@ -2593,6 +2605,7 @@ int cook_considerable(cook_engine* e, const cook_queue* q, const cook_user_state
 int cook_cycle_set_considerable(cook_engine* e, const cook_user_state* us, const uint8_t* eligible_by_pending) {
   return guarded(e, [&] {
     ConsBufs& c = cons_bufs(e);
+    e->cycle_cons_ran = false;
     if (!us) {
       c.cycle_on = false;
       return;
@@ -2620,6 +2633,13 @@ int cook_cycle_fetch_considerable(cook_engine* e, uint32_t* rank_pos, uint32_t* 
       for (unsigned k = 0; k < K; ++k) rank_pos[k] = k;
     }
     if (n_out) *n_out = K;
+  });
+}
+int cook_cycle_autoscale(cook_engine* e, const cook_autoscale_params* p, uint32_t* task_idx, uint32_t cap, cook_autoscale_info* info) {
+  if (info) *info = cook_autoscale_info{};
+  return guarded(e, [&] {
+    cycle_autoscale(e, p, task_idx, cap, info);
+    prof_collect(e);
   });
 }
 

@@ -273,6 +273,21 @@ class Engine:
         self._chk(self._lib.cook_cycle_fetch_considerable(self._h, _p(out, C.c_uint32), C.byref(n)))
         return out[: n.value].copy()
 
+    def cycle_autoscale(self, max_jobs: int = 1000, scale_factor: float = 1.0, offer_skipped=None, exclude_tasks=None):
+        """The jobs of the last cycle that get synthetic pods (handle-resource-offers-autoscaling-helper, scheduler.clj:1283-1335;
+        cook_cycle_autoscale): -> (task indices of Out in queue order, info dict: considered, matched, unmatched, scaled (N),
+        autoscalable (|A|), n_out, fraction_unmatched).  offer_skipped: per staged offer, 1 where the rate limit dropped its
+        cluster's matches; exclude_tasks: task indices the host's recent-synthetic-pod cache names."""
+        sk = np.ascontiguousarray(offer_skipped, dtype=np.uint8) if offer_skipped is not None else None
+        ex = np.ascontiguousarray(exclude_tasks if exclude_tasks is not None else [], dtype=np.uint32)
+        p = A.CookAutoscaleParams(int(max_jobs), len(ex), float(scale_factor), _p(sk, C.c_uint8) if sk is not None else None,
+                                  _p(ex, C.c_uint32) if len(ex) else None)
+        cap = max(int(max_jobs), getattr(self, "_rank_np", 0))  # >= max(max_jobs, K)
+        out = np.zeros(max(1, cap), dtype=np.uint32)
+        info = A.CookAutoscaleInfo()
+        self._chk(self._lib.cook_cycle_autoscale(self._h, C.byref(p), _p(out, C.c_uint32), cap, C.byref(info)))
+        return out[: info.n_out].copy(), info.as_dict()
+
     # ---- rebalancer ------------------------------------------------------------------------------------------
     def rebalance_stage(self, running: A.Tasks, pending: A.Jobs, pending_job_id, pending_priority, users: A.Users,
                         spare: A.HostSpare, rparams: A.CookRebalanceParams, host_attrs: Optional[A.Offers] = None,

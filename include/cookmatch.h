@@ -307,6 +307,35 @@ int cook_cycle_set_considerable(cook_engine* e, const cook_user_state* users, co
  * ranked_pending_idx[rank_pos[k]] (identity when the considerable filters are off). */
 int cook_cycle_fetch_considerable(cook_engine* e, uint32_t* rank_pos, uint32_t* n_out);
 
+/* ---- AUTOSCALE: the pending-job candidates of handle-resource-offers-autoscaling-helper (scheduler.clj:1283-1335) from the last cycle --
+ * Reads the pool's last cook_cycle_run (or cook_cycle_run_rank + cook_cycle_match_multi): the ranked queue R, the k considered rank
+ * positions C with their job_to_offer, and the user state S staged by cook_cycle_set_considerable.
+ *  1. kept matches: the job at C[i] is matched iff job_to_offer[i] >= 0 and offer_skipped[job_to_offer[i]] == 0 (offer_skipped: 1 where
+ *     filter-matches-for-ratelimit, :887-924, dropped every match of the offer's compute cluster); m matched, u = k - m unmatched.
+ *  2. N (:1288-1306) = max(u, trunc(min(fraction * scale_factor, 1) * max_jobs)), fraction = k > 0 ? (double)(float)u / k : 0.
+ *  3. Q' = R without the matched jobs, in order (remove-matched-jobs-from-pending-jobs, :790-795).
+ *  4. A = the first N jobs of Q' that pass filter-pending-jobs-for-quota (tools.clj:961-973) under S with fresh rate-limit counters:
+ *     user quota seeded with the running usage, launch rate (the n-th survivor of a user is limited iff n > tokens_left, dropped only
+ *     when enforcing), pool quota.  The eligible mask is NOT applied (job-allowed-to-start? is the considerable path's only, :747-748).
+ *  5. Out = A without the excluded tasks (caches/recent-synthetic-pod-job-uuids, removed after the take, :1319: no refill), in order.
+ * task_idx receives Out as task indices (cook_cycle_fetch's ranked_pending_idx space); cap >= max(max_jobs, k) always suffices, |Out| > cap:
+ * COOK_E_INVALID (info says |Out|).  An in-range excluded task that is no candidate is ignored; one out of range, a non-finite
+ * scale_factor or max_jobs > INT32_MAX: COOK_E_INVALID.  Before any cycle, after a stage / cook_cycle_update / cook_considerable /
+ * cook_cycle_set_considerable that no cycle has followed, and after a cycle without a staged user state: COOK_E_STATE.  Changes no rank,
+ * considerable or match state. */
+typedef struct cook_autoscale_params {
+  uint32_t max_jobs;              /* :max-jobs-for-autoscaling (<= INT32_MAX)                                            */
+  uint32_t n_exclude;
+  double scale_factor;            /* :autoscaling-scale-factor (finite)                                                  */
+  const uint8_t* offer_skipped;   /* [staged offers] or NULL                                                             */
+  const uint32_t* exclude_task;   /* [n_exclude] task indices (cook_cycle_fetch's index space) or NULL                   */
+} cook_autoscale_params;
+typedef struct cook_autoscale_info {
+  uint32_t considered, matched, unmatched, scaled /* N */, autoscalable /* |A| */, n_out /* |Out| */;
+  double fraction_unmatched;
+} cook_autoscale_info;
+int cook_cycle_autoscale(cook_engine* e, const cook_autoscale_params* p, uint32_t* task_idx, uint32_t cap, cook_autoscale_info* info);
+
 /* ---- MATCH: replaces the body of match-offer-to-schedule, i.e. TaskScheduler.scheduleOnce -----------------
  * (scheduler.clj:617-687; Fenzo 0.10.0 pinned at project.clj:46-50; constraints.clj).
  * job_to_offer[k] = offer index or -1.  head_matched mirrors scheduler.clj:1495 (first considerable job matched,
