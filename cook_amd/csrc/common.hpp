@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -48,8 +49,12 @@ static __host__ __device__ __forceinline__ uint64_t f64_key(double d) {
 static __host__ __device__ __forceinline__ uint64_t i64_key(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }
 
 // ---- exact-sum tracking ---------------------------------------------------------------------------------
-// The reference accumulates fp64 usage left-to-right (dru.clj:43-48 reductions / merge-with +).  A parallel scan
-// associates differently; it is bit-identical to the sequential sum iff every partial sum it forms is exact.
+// The reference accumulates fp64 usage left-to-right (dru.clj:43-48 reductions / merge-with +).  A parallel sum may stand in
+// for it only if EVERY PREFIX of the left-to-right order is exact: then each sequential step adds to the exact prefix and
+// lands on the next exact prefix.  That the parallel additions were exact is not enough for a reduction: with h = 2^-53,
+// 1 + (h + h) is exact while (1 + h) + h rounds twice.  So a scan checks the bad bit of every prefix (rank_mark_inexact,
+// queue_quota_flag, us_mark), and a reduction either proves exactness from its inputs (SumBound4 in scan.hpp,
+// rebal_user_safe) or folds left to right.  DESIGN.md §3 lists every site and its guard.
 // two_sum_err returns the rounding error of a+b (Knuth TwoSum): 0.0 <=> the addition was exact.
 static __host__ __device__ __forceinline__ double two_sum_err(double a, double b, double s) {
   const double bb = s - a;

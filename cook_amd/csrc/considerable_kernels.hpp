@@ -134,13 +134,21 @@ COOK_KERNEL void cons_eligible_flag(const uint32_t* __restrict__ qitem, unsigned
   if (q < len) flag[q] = elig[qitem[q]] ? 1 : 0;
 }
 
-// tools.clj:966 pool-usage = sum of the users' usage (user-id order); one workgroup, exactness tracked
+// tools.clj:966 pool-usage = sum of the users' usage (user-id order); one workgroup.  The tree's sum is kept only when SumBound4
+// proves every order exact (its additions being exact would not do, common.hpp; the count column is the caller's and checked too),
+// otherwise left to right from the first user's usage, as the reference's reduce does
 COOK_KERNEL void cons_pool_usage(const double* __restrict__ uc, const double* __restrict__ ucpus,
                                                         const double* __restrict__ umem, const double* __restrict__ ugpus, unsigned n,
                                                         SumU4* __restrict__ out) {
   __shared__ SumU4 ws[1024 / COOK_WAVE];
+  __shared__ SumBound4 wb[1024 / COOK_WAVE];
   SumU4 acc = SumU4::zero();
-  for (unsigned i = threadIdx.x; i < n; i += blockDim.x) acc = combine(acc, SumU4{uc[i], ucpus[i], umem[i], ugpus[i], 0u});
+  SumBound4 bd = SumBound4::zero();
+  for (unsigned i = threadIdx.x; i < n; i += blockDim.x) {
+    const double x[4] = {uc[i], ucpus[i], umem[i], ugpus[i]};
+    acc = combine(acc, SumU4{x[0], x[1], x[2], x[3], 0u});
+    bound_add(bd, x);
+  }
   for (int d = 32; d >= 1; d >>= 1) {
     SumU4 o;
     o.count = __shfl_xor(acc.count, d, COOK_WAVE);
@@ -149,13 +157,15 @@ COOK_KERNEL void cons_pool_usage(const double* __restrict__ uc, const double* __
     o.gpus = __shfl_xor(acc.gpus, d, COOK_WAVE);
     o.bad = __shfl_xor(acc.bad, d, COOK_WAVE);
     acc = combine(acc, o);
+    bound_merge(bd, bound_shfl_xor(bd, d));
   }
-  if (lane_id() == 0) ws[wave_id()] = acc;
+  if (lane_id() == 0) ws[wave_id()] = acc, wb[wave_id()] = bd;
   __syncthreads();
   if (threadIdx.x == 0) {
     SumU4 t = ws[0];
-    for (unsigned k = 1; k < blockDim.x / COOK_WAVE; ++k) t = combine(t, ws[k]);
-    if (t.bad) {
+    SumBound4 tb = wb[0];
+    for (unsigned k = 1; k < blockDim.x / COOK_WAVE; ++k) t = combine(t, ws[k]), bound_merge(tb, wb[k]);
+    if (t.bad || !bound_exact(tb)) {
       t = SumU4::zero();
       for (unsigned i = 0; i < n; ++i) {
         if (i == 0) {
@@ -168,6 +178,7 @@ COOK_KERNEL void cons_pool_usage(const double* __restrict__ uc, const double* __
         }
       }
     }
+    t.bad = 0u;
     *out = t;
   }
 }

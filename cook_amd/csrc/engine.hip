@@ -183,6 +183,8 @@ struct cook_engine {
   DArr<uint64_t> run_dkey;
   DArr<double> uu_out;
   DArr<SumU4> uu_pre;
+  DArr<uint32_t> uu_bad;             // users of rank_user_usage whose running-usage prefixes were not all exact
+  DArr<SumBound4> pool_usage_bound;  // pool_usage_partial's exactness bounds
   DArr<double> dru, dru_out;
   ScanTmp<SumU4> tmpU4;
   ScanTmp<SumI> tmpI;
@@ -794,12 +796,13 @@ void rank_pool_usage(cook_engine* e, cook_usage* out) {
     return;
   }
   e->pool_usage.ensure(1 + POOL_USAGE_BLOCKS);
+  e->pool_usage_bound.ensure(POOL_USAGE_BLOCKS);
   KM<pool_usage_partial, 256>(e, "pool_usage_partial", POOL_USAGE_BLOCKS, (const double*)e->t_cpus.ptr(), (const double*)e->t_mem.ptr(),
       e->has_gpus ? (const double*)e->t_gpus.ptr() : (const double*)nullptr, (const uint8_t*)e->t_pending.ptr(), e->N, e->pool_usage.ptr() + 1,
-      (unsigned)POOL_USAGE_BLOCKS);
+      e->pool_usage_bound.ptr(), (unsigned)POOL_USAGE_BLOCKS);
   KM<pool_usage_reduce, COOK_WAVE>(e, "pool_usage_reduce", 1, (const double*)e->t_cpus.ptr(), (const double*)e->t_mem.ptr(),
       e->has_gpus ? (const double*)e->t_gpus.ptr() : (const double*)nullptr, (const uint8_t*)e->t_pending.ptr(), e->N,
-      (const SumU4*)(e->pool_usage.ptr() + 1), (unsigned)POOL_USAGE_BLOCKS, e->pool_usage.ptr());
+      (const SumU4*)(e->pool_usage.ptr() + 1), (const SumBound4*)e->pool_usage_bound.ptr(), (unsigned)POOL_USAGE_BLOCKS, e->pool_usage.ptr());
   SumU4 h;
   pinned_copy(e, e->h_scratch, e->pool_usage.ptr(), sizeof(SumU4), hipMemcpyDeviceToHost);
   sync(e);
@@ -818,10 +821,13 @@ void rank_user_usage(cook_engine* e, double* out, bool out_is_device) {
   double* dst = out_is_device ? out : e->uu_out.ensure((size_t)U * 3);
   if (N) {
     SumU4* rp = e->uu_pre.ensure(N);
+    uint32_t* bad = e->uu_bad.ensure(U);
+    memset_async(e, bad, 0, (size_t)U * 4);
     seg_scan<SumU4>(e, "user_running_scan", LoadRunningU4{e->s_use.ptr(), e->s_pending.ptr()}, (const uint8_t*)e->head.ptr(), N, rp,
                     e->tmpU4);
+    KM<rank_mark_inexact, 256>(e, "user_usage_mark", div_up(N, 256), (const SumU4*)rp, (const uint32_t*)e->s_user.ptr(), N, bad);
     KM<user_usage_extract, 256>(e, "user_usage_extract", div_up(U, 256), (const SumU4*)rp, (const SumU4*)e->s_use.ptr(),
-        (const uint8_t*)e->s_pending.ptr(), (const uint32_t*)e->seg_start.ptr(), (const uint32_t*)e->seg_end.ptr(), U, dst);
+        (const uint8_t*)e->s_pending.ptr(), (const uint32_t*)e->seg_start.ptr(), (const uint32_t*)e->seg_end.ptr(), (const uint32_t*)bad, U, dst);
   } else {
     memset_async(e, dst, 0, (size_t)U * 24);
   }

@@ -477,26 +477,32 @@ COOK_KERNEL void dru_to_task_space(const double* __restrict__ dru, const uint8_t
 // ---- per-user running usage of the pool: the [U x 3] vector of the cross-pool all-reduce (BASELINE.json north_star; ----------
 // SURVEY.md §8e).  Sum of {cpus, mem, gpus} over the user's RUNNING tasks in the user's task order (tools.clj:614-641; the
 // reference's own per-user usage maps reduce in query order, which is not defined): a masked segmented scan over the
-// per-user order the rank already holds, exactness tracked and fixed up like the DRU prefixes.
+// per-user order the rank already holds, exactness tracked and fixed up like the DRU prefixes: rank_mark_inexact flags the users
+// with ANY inexact prefix (the bad bit of the segment's last prefix alone would miss 1 + h + h, common.hpp).
 struct LoadRunningU4 {
   const SumU4* use;
   const uint8_t* pending;
   __device__ __forceinline__ SumU4 operator()(unsigned i) const {
     if (pending[i]) return SumU4::zero();
-    return use[i];
+    SumU4 x = use[i];
+    // the fold starts from the user's first RUNNING task and keeps a -0.0 there; the scan adds the pending tasks' +0.0, which
+    // does not: such a user is folded left to right
+    if (__double_as_longlong(x.cpus) == LLONG_MIN || __double_as_longlong(x.mem) == LLONG_MIN || __double_as_longlong(x.gpus) == LLONG_MIN)
+      x.bad = 1u;
+    return x;
   }
 };
 COOK_KERNEL void user_usage_extract(const SumU4* __restrict__ run_pre, const SumU4* __restrict__ s_use,
                                                           const uint8_t* __restrict__ s_pending, const uint32_t* __restrict__ seg_start,
-                                                          const uint32_t* __restrict__ seg_end, unsigned n_users,
-                                                          double* __restrict__ out /*[U][3]*/) {
+                                                          const uint32_t* __restrict__ seg_end, const uint32_t* __restrict__ inexact_user,
+                                                          unsigned n_users, double* __restrict__ out /*[U][3]*/) {
   const unsigned u = blockIdx.x * blockDim.x + threadIdx.x;
   if (u >= n_users) return;
   double c = 0.0, m = 0.0, g = 0.0;
   if (seg_end[u] != 0u) {  // (rank_init: 0 = the user has no task in this pool)
     const unsigned a = seg_start[u], b = seg_end[u];
     const SumU4 t = run_pre[b - 1];
-    if (!t.bad) {
+    if (!inexact_user[u]) {
       c = t.cpus, m = t.mem, g = t.gpus;
     } else {  // an addition of the parallel scan rounded: left to right, as a sequential reduce would
       bool first = true;
@@ -516,17 +522,25 @@ COOK_KERNEL void user_usage_extract(const SumU4* __restrict__ run_pre, const Sum
   out[(size_t)u * 3 + 1] = m;
   out[(size_t)u * 3 + 2] = g;
 }
-// ---- pool running usage (scheduler.clj:2118-2123, 2173): one workgroup, exactness tracked ----------------------
+// ---- pool running usage (scheduler.clj:2118-2123, 2173) ------------------------------------------------------------------
 // stage 1: POOL_USAGE_BLOCKS blocks fold strided slices (a single 1024-thread block took 153 us for 175k tasks: 171 dependent
-// iterations); stage 2 (pool_usage_reduce) combines the partial sums, or redoes the sum left to right when one of them rounded
+// iterations), each with its SumBound4; stage 2 (pool_usage_reduce) combines the partial sums.  The strided tree is not the
+// reference's order, and its additions being exact would not make it so (common.hpp): the tree's sum is kept only when the
+// bound proves that every order is exact, otherwise stage 2 redoes the sum left to right like the reference.
 constexpr int POOL_USAGE_BLOCKS = 64;
 COOK_KERNEL void pool_usage_partial(const double* __restrict__ cpus, const double* __restrict__ mem,
                                                           const double* __restrict__ gpus, const uint8_t* __restrict__ pending,
-                                                          unsigned n, SumU4* __restrict__ part, unsigned nblk) {
+                                                          unsigned n, SumU4* __restrict__ part, SumBound4* __restrict__ part_bound, unsigned nblk) {
   __shared__ SumU4 ws[256 / COOK_WAVE];
+  __shared__ SumBound4 wb[256 / COOK_WAVE];
   SumU4 acc = SumU4::zero();
+  SumBound4 bd = SumBound4::zero();
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += nblk * blockDim.x)
-    if (!pending[i]) acc = combine(acc, SumU4{1.0, cpus[i], mem[i], gpus ? gpus[i] : 0.0, 0u});
+    if (!pending[i]) {
+      const double x[4] = {1.0, cpus[i], mem[i], gpus ? gpus[i] : 0.0};
+      acc = combine(acc, SumU4{x[0], x[1], x[2], x[3], 0u});
+      bound_add(bd, x);
+    }
   for (int d = 32; d >= 1; d >>= 1) {
     SumU4 o;
     o.count = __shfl_xor(acc.count, d, COOK_WAVE);
@@ -535,23 +549,31 @@ COOK_KERNEL void pool_usage_partial(const double* __restrict__ cpus, const doubl
     o.gpus = __shfl_xor(acc.gpus, d, COOK_WAVE);
     o.bad = __shfl_xor(acc.bad, d, COOK_WAVE);
     acc = combine(acc, o);
+    bound_merge(bd, bound_shfl_xor(bd, d));
   }
-  if (lane_id() == 0) ws[wave_id()] = acc;
+  if (lane_id() == 0) ws[wave_id()] = acc, wb[wave_id()] = bd;
   __syncthreads();
   if (threadIdx.x == 0) {
     SumU4 t = ws[0];
-    for (unsigned k = 1; k < blockDim.x / COOK_WAVE; ++k) t = combine(t, ws[k]);
+    SumBound4 tb = wb[0];
+    for (unsigned k = 1; k < blockDim.x / COOK_WAVE; ++k) t = combine(t, ws[k]), bound_merge(tb, wb[k]);
     part[blockIdx.x] = t;
+    part_bound[blockIdx.x] = tb;
   }
 }
 COOK_KERNEL void pool_usage_reduce(const double* __restrict__ cpus, const double* __restrict__ mem,
                                                                const double* __restrict__ gpus, const uint8_t* __restrict__ pending,
-                                                               unsigned n, const SumU4* __restrict__ part, unsigned n_part,
-                                                               SumU4* __restrict__ out) {
+                                                               unsigned n, const SumU4* __restrict__ part, const SumBound4* __restrict__ part_bound,
+                                                               unsigned n_part, SumU4* __restrict__ out) {
+  __shared__ SumU4 s_part[POOL_USAGE_BLOCKS];
+  __shared__ SumBound4 s_bound[POOL_USAGE_BLOCKS];
+  for (unsigned k = threadIdx.x; k < n_part; k += blockDim.x) s_part[k] = part[k], s_bound[k] = part_bound[k];  // (loads side by side)
+  __syncthreads();
   if (threadIdx.x != 0) return;
-  SumU4 t = part[0];
-  for (unsigned k = 1; k < n_part; ++k) t = combine(t, part[k]);
-  if (t.bad) {  // some partial sum rounded: redo left to right like the reference
+  SumU4 t = s_part[0];
+  SumBound4 tb = s_bound[0];
+  for (unsigned k = 1; k < n_part; ++k) t = combine(t, s_part[k]), bound_merge(tb, s_bound[k]);
+  if (t.bad || !bound_exact(tb)) {  // some order could round (t.bad: the tree's own did): left to right like the reference
     t = SumU4::zero();
     for (unsigned i = 0; i < n; ++i)
       if (!pending[i]) {
@@ -561,5 +583,6 @@ COOK_KERNEL void pool_usage_reduce(const double* __restrict__ cpus, const double
         t.gpus += gpus ? gpus[i] : 0.0;
       }
   }
+  t.bad = 0u;
   *out = t;
 }

@@ -3,9 +3,11 @@
 // Serves every prefix sum of the rank path: per-user usage prefixes (scheduler.clj:2057-2071 limit-over-quota-jobs,
 // dru.clj:43-66 accumulate-resources), the over-quota counter, and the queue-order usage prefixes of the pool / quota
 // group filters (tools.clj:917-933).  Value types carry a `bad` bit: a parallel scan associates additions differently
-// from the reference's left-to-right `reductions`; it is bit-identical iff every addition it performs is exact
-// (TwoSum error == 0).  Elements whose prefix involved an inexact addition are flagged and recomputed sequentially by
-// the caller's fix-up kernel, so results are exact for ANY fp64 inputs, not only integer-valued ones.
+// from the reference's left-to-right `reductions`.  A prefix whose bad bit is clear was formed by exact additions only, so
+// it equals the exact sum of its elements.  A segment's prefixes are ALL bit-identical to the sequential ones iff every
+// one of them is exact (common.hpp "exact-sum tracking"): the caller ORs the bad bits over the whole segment, never
+// only its last prefix, and recomputes a flagged segment sequentially in its fix-up kernel.  With that, results are
+// exact for ANY fp64 inputs, not only integer-valued ones.
 //
 //   seg_scan_local     : per-block scan of a tile (thread-sequential -> wave shuffles -> cross-wave in LDS); writes
 //                        the locally scanned values, the block aggregate and the block's first segment head.
@@ -38,6 +40,61 @@ static __device__ __forceinline__ SumU4 shfl_up_v(const SumU4& v, unsigned d) {
   r.gpus = __shfl_up(v.gpus, d, COOK_WAVE);
   r.bad = __shfl_up(v.bad, d, COOK_WAVE);
   return r;
+}
+
+// ---- an order-free exactness bound for reductions (pool usage, cons_pool_usage) ------------------------------------------
+// A reduction tree's exact additions say nothing about the prefixes of the left-to-right order (common.hpp).  Instead: if
+// every value of a column is a multiple of 2^g (g = the lowest set bit over its values) and the sum of their magnitudes is
+// below 2^(g+53), every partial sum of ANY subset is a multiple of 2^g below 2^(g+53) in magnitude, hence representable,
+// and every order of addition gives the exact sum.  The magnitude sum is computed in fp64 too: each of its nodes is either
+// exact or, rounding being monotone, at least 2^(g+53) when its exact value is, so the test cannot pass wrongly.  A -0.0
+// fails the test (a left-to-right fold that starts from the first value keeps -0.0 where a tree seeded with +0.0 does not),
+// and so does an inf or NaN (the magnitude sum is no longer finite).
+struct SumBound4 {  // per column {count, cpus, mem, gpus}
+  double mag[4];  // sum of |x|
+  int grain[4];   // lowest set bit over the values (INT_MAX: only +0.0 so far)
+  static __host__ __device__ __forceinline__ SumBound4 zero() { return SumBound4{{0.0, 0.0, 0.0, 0.0}, {INT_MAX, INT_MAX, INT_MAX, INT_MAX}}; }
+};
+static __device__ __forceinline__ int f64_grain(double x) {  // exponent of x's lowest set bit; INT_MAX for +0.0, -2^20 for -0.0
+  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+  if (b == 0ull) return INT_MAX;
+  if (b == 0x8000000000000000ull) return -(1 << 20);
+  const unsigned e = (unsigned)(b >> 52) & 0x7FFu;
+  const unsigned long long sig = (b & 0xFFFFFFFFFFFFFull) | (e ? (1ull << 52) : 0ull);
+  return (int)__builtin_ctzll(sig) + (e ? (int)e - 1075 : -1074);
+}
+static __device__ __forceinline__ void bound_add(SumBound4& a, const double (&x)[4]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    a.mag[k] += fabs(x[k]);
+    const int g = f64_grain(x[k]);
+    if (g < a.grain[k]) a.grain[k] = g;
+  }
+}
+static __device__ __forceinline__ void bound_merge(SumBound4& a, const SumBound4& b) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    a.mag[k] += b.mag[k];
+    if (b.grain[k] < a.grain[k]) a.grain[k] = b.grain[k];
+  }
+}
+static __device__ __forceinline__ SumBound4 bound_shfl_xor(const SumBound4& v, int d) {
+  SumBound4 r;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    r.mag[k] = __shfl_xor(v.mag[k], d, COOK_WAVE);
+    r.grain[k] = __shfl_xor(v.grain[k], d, COOK_WAVE);
+  }
+  return r;
+}
+static __device__ __forceinline__ bool bound_exact(const SumBound4& a) {  // every order sums every column exactly
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int e = (a.grain[k] > 1100 ? 1100 : a.grain[k] < -1200 ? -1200 : a.grain[k]) + 53;  // (all +0.0: the limit is +inf; -0.0: 0)
+    ok = ok && a.mag[k] < ldexp(1.0, e);
+  }
+  return ok;
 }
 
 struct SumI {  // integer counter (over-quota count, stream-compaction offsets)
