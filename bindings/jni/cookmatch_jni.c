@@ -483,6 +483,45 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleAutoscale(JNIEnv* env, jclass c
   return CHECKED(cook_cycle_autoscale(H(h), &p, out, (uint32_t)cap, info));
 }
 
+/* ---- the task killers over the running set (cook_sweep_running) -------------------------------------------------------------------
+ * rows = n-entry columns {start_ms int64, unknown uint8, max_runtime_ms int64, cancelled uint8, group uint32} (null elements allowed as
+ * the header allows them); group_cols = {type uint8, quantile double, multiplier double, job_count uint32 [n_groups], succ_off uint32
+ * [n_groups + 1], succ_start_ms int64, succ_end_ms int64 [succ_off[n_groups]]} or null; params = one cook_sweep_params; reason_out =
+ * n bytes or null; idx_out = cap uint32 slots (3n always suffices); threshold_out = n_groups doubles or null; info_out = one
+ * cook_sweep_info or null */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_sweepRunning(JNIEnv* env, jclass c, jlong h, jint n, jobjectArray rows, jint n_groups,
+                                                         jobjectArray group_cols, jobject params, jobject reason_out, jobject idx_out,
+                                                         jint cap, jobject threshold_out, jobject info_out) {
+  int bad = 0;
+  cook_running_set t;
+  cook_straggler_groups g;
+  const cook_sweep_params* p = BUF(const cook_sweep_params, params);
+  uint8_t* reason = BUFN(uint8_t, reason_out, n > 0 ? n : 0);
+  uint32_t* idx = BUFN(uint32_t, idx_out, cap > 0 ? cap : 0);
+  double* thr = BUFN(double, threshold_out, n_groups > 0 ? n_groups : 0);
+  cook_sweep_info* info = BUF(cook_sweep_info, info_out);
+  uint32_t ns = 0;
+  (void)c;
+  if (n < 0 || n_groups < 0 || cap < 0 || !p) return COOK_E_INVALID;
+  t.n = (uint32_t)n;
+  t.start_ms = EL(const int64_t, rows, 0, n);
+  t.unknown = EL(const uint8_t, rows, 1, n);
+  t.max_runtime_ms = EL(const int64_t, rows, 2, n);
+  t.cancelled = EL(const uint8_t, rows, 3, n);
+  t.group = EL(const uint32_t, rows, 4, n);
+  g.n = (uint32_t)n_groups;
+  g.type = EL(const uint8_t, group_cols, 0, n_groups);
+  g.quantile = EL(const double, group_cols, 1, n_groups);
+  g.multiplier = EL(const double, group_cols, 2, n_groups);
+  g.job_count = EL(const uint32_t, group_cols, 3, n_groups);
+  g.succ_off = EL(const uint32_t, group_cols, 4, (uint64_t)n_groups + 1u);
+  if (g.succ_off) ns = g.succ_off[n_groups];
+  g.succ_start_ms = EL(const int64_t, group_cols, 5, ns);
+  g.succ_end_ms = EL(const int64_t, group_cols, 6, ns);
+  if (cap && !idx) return COOK_E_INVALID;
+  return CHECKED(cook_sweep_running(H(h), &t, group_cols ? &g : 0, p, reason, idx, (uint32_t)cap, thr, info));
+}
+
 /* ---- rebalance: rebalancer/init-state + the rebalance loop's decisions ------------------------------------------------- */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_rebalance(JNIEnv* env, jclass c, jlong h, jint r, jobjectArray running,
                                                       jobject running_attrs_cached, jint p, jobjectArray pending,

@@ -926,3 +926,32 @@ class CookAutoscaleInfo(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# ---- the task killers over the running set (cook_sweep_running: scheduler.clj:1888-2016, group.clj:17-44) -------------------------
+SWEEP_LINGERING, SWEEP_STRAGGLERS, SWEEP_CANCELLED = 1, 2, 4
+SWEEP_ALL = 7
+START_ABSENT = -(2 ** 63)  # INT64_MIN: no :instance/start-time
+
+
+class CookRunningSet(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("start_ms", _i64p), ("unknown", _u8p), ("max_runtime_ms", _i64p), ("cancelled", _u8p),
+                ("group", _u32p)]
+
+
+class CookStragglerGroups(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("type", _u8p), ("quantile", _f64p), ("multiplier", _f64p), ("job_count", _u32p),
+                ("succ_off", _u32p), ("succ_start_ms", _i64p), ("succ_end_ms", _i64p)]
+
+
+class CookSweepParams(C.Structure):
+    _fields_ = [("now_ms", C.c_int64), ("default_timeout_ms", C.c_int64), ("max_timeout_ms", C.c_int64), ("what", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class CookSweepInfo(C.Structure):
+    _fields_ = [("lingering", C.c_uint32), ("stragglers", C.c_uint32), ("cancelled", C.c_uint32), ("groups_ready", C.c_uint32),
+                ("bad_row", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}

@@ -132,6 +132,7 @@ struct ExplainBufs;  // explain_host.hpp
 struct UpdateBufs;   // cycle_update.hpp
 struct UserStatsBufs;  // user_stats_host.hpp
 struct AutoscaleBufs;  // autoscale_host.hpp
+struct SweepBufs;      // sweep_host.hpp
 
 }  // namespace
 
@@ -262,6 +263,7 @@ struct cook_engine {
   UpdateBufs* ub = nullptr;  // cook_cycle_update (allocated on first use)
   UserStatsBufs* usb = nullptr;  // cook_user_stats* (allocated on first use)
   AutoscaleBufs* asb = nullptr;  // cook_cycle_autoscale (allocated on first use)
+  SweepBufs* swb = nullptr;      // cook_sweep_running (allocated on first use)
   MatchIn last_in{};  // the MatchIn of the last match run (K, j_index as used)
   bool last_in_valid = false;
   unsigned rlog_id = 0;  // suffix of this engine's COOK_ROUND_LOG file
@@ -699,28 +701,30 @@ void seg_scan(cook_engine* e, const char* tag, Load load, const uint8_t* head, u
 }
 
 // ---- radix sort driver: one stable pass of `perm` by the 8 key bits from `shift` up --------------------------------------
+// (hist: the histogram scratch, e->hist unless a caller keeps its own)
 template <int IPL>
-static void radix_pass_t(cook_engine* e, const uint64_t* key, const uint32_t* in, uint32_t* out, unsigned n, unsigned shift, bool fused) {
+static void radix_pass_t(cook_engine* e, const uint64_t* key, const uint32_t* in, uint32_t* out, unsigned n, unsigned shift, bool fused,
+                         DArr<uint32_t>& hist) {
   const unsigned nb = div_up(n, rs_tile(IPL));
-  e->hist.ensure((size_t)256 * nb);
-  KM<radix_hist<IPL>, RS_THREADS>(e, "radix_hist", nb, key, in, n, shift, nb, fused ? 1u : 0u, e->hist.ptr());
-  if (!fused) KM<excl_scan_u32_single, SCAN1_THREADS>(e, "radix_scan", 1, e->hist.ptr(), 256u * nb, (uint32_t*)nullptr);
-  KM<radix_scatter<IPL>, RS_THREADS>(e, "radix_scatter", nb, key, in, out, n, shift, nb, fused ? 1u : 0u, (const uint32_t*)e->hist.ptr());
+  hist.ensure((size_t)256 * nb);
+  KM<radix_hist<IPL>, RS_THREADS>(e, "radix_hist", nb, key, in, n, shift, nb, fused ? 1u : 0u, hist.ptr());
+  if (!fused) KM<excl_scan_u32_single, SCAN1_THREADS>(e, "radix_scan", 1, hist.ptr(), 256u * nb, (uint32_t*)nullptr);
+  KM<radix_scatter<IPL>, RS_THREADS>(e, "radix_scatter", nb, key, in, out, n, shift, nb, fused ? 1u : 0u, (const uint32_t*)hist.ptr());
 }
-void radix_pass(cook_engine* e, const uint64_t* key, const uint32_t* in, uint32_t* out, unsigned n, unsigned shift) {
-  if (div_up(n, rs_tile(RS_IPL_SMALL)) <= RS_FUSED_BLOCKS) radix_pass_t<RS_IPL_SMALL>(e, key, in, out, n, shift, true);
-  else radix_pass_t<RS_IPL_LARGE>(e, key, in, out, n, shift, div_up(n, rs_tile(RS_IPL_LARGE)) <= RS_FUSED_BLOCKS_LARGE);
+void radix_pass(cook_engine* e, const uint64_t* key, const uint32_t* in, uint32_t* out, unsigned n, unsigned shift, DArr<uint32_t>& hist) {
+  if (div_up(n, rs_tile(RS_IPL_SMALL)) <= RS_FUSED_BLOCKS) radix_pass_t<RS_IPL_SMALL>(e, key, in, out, n, shift, true, hist);
+  else radix_pass_t<RS_IPL_LARGE>(e, key, in, out, n, shift, div_up(n, rs_tile(RS_IPL_LARGE)) <= RS_FUSED_BLOCKS_LARGE, hist);
 }
 // sort by the bits of `key` selected by `mask` (bits that vary); ping-pongs between a and b; returns final buffer.  A digit starts at
 // the lowest varying bit not sorted yet (bits that never vary in between cost nothing).
 uint32_t* radix_sort_masked(cook_engine* e, const uint64_t* key, unsigned long long mask, const uint32_t* cur, uint32_t* a,
-                            uint32_t* b, unsigned n) {
+                            uint32_t* b, unsigned n, DArr<uint32_t>* hist = nullptr) {
   const uint32_t* in = cur;  // null: the identity (the first pass reads positions instead of a permutation)
   uint32_t* last = const_cast<uint32_t*>(cur);
   while (mask) {
     const unsigned shift = (unsigned)__builtin_ctzll(mask);
     uint32_t* out = (in == a) ? b : a;
-    radix_pass(e, key, in, out, n, shift);
+    radix_pass(e, key, in, out, n, shift, hist ? *hist : e->hist);
     in = out;
     last = out;
     mask = shift + 8 >= 64 ? 0ull : mask & ~((1ull << (shift + 8)) - 1ull);
@@ -2059,6 +2063,7 @@ struct StageTimer {
 #include "cycle_update.hpp"
 #include "user_stats_host.hpp"
 #include "autoscale_host.hpp"
+#include "sweep_host.hpp"
 
 ConsBufs& cons_bufs(cook_engine* e) {
   if (!e->cb) e->cb = new ConsBufs();
@@ -2203,6 +2208,8 @@ void cook_engine_destroy(cook_engine* e) {
   e->usb = nullptr;
   delete e->asb;
   e->asb = nullptr;
+  delete e->swb;
+  e->swb = nullptr;
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -2645,6 +2652,15 @@ int cook_cycle_autoscale(cook_engine* e, const cook_autoscale_params* p, uint32_
   if (info) *info = cook_autoscale_info{};
   return guarded(e, [&] {
     cycle_autoscale(e, p, task_idx, cap, info);
+    prof_collect(e);
+  });
+}
+
+int cook_sweep_running(cook_engine* e, const cook_running_set* tasks, const cook_straggler_groups* groups, const cook_sweep_params* p,
+                       uint8_t* reason, uint32_t* idx, uint32_t cap, double* group_threshold_s, cook_sweep_info* info) {
+  if (info) *info = cook_sweep_info{0u, 0u, 0u, 0u, COOK_NONE_U32};
+  return guarded(e, [&] {
+    sweep_running(e, tasks, groups, p, reason, idx, cap, group_threshold_s, info);
     prof_collect(e);
   });
 }

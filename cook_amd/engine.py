@@ -288,6 +288,55 @@ class Engine:
         self._chk(self._lib.cook_cycle_autoscale(self._h, C.byref(p), _p(out, C.c_uint32), cap, C.byref(info)))
         return out[: info.n_out].copy(), info.as_dict()
 
+    def sweep_running(self, start_ms, now_ms: int, default_timeout_ms: int = 0, max_timeout_ms: int = 0, what: int = A.SWEEP_ALL,
+                      unknown=None, max_runtime_ms=None, cancelled=None, group=None, groups: Optional[dict] = None, cap: Optional[int] = None):
+        """The three task killers over the running set (cook_sweep_running): lingering (get-lingering-tasks), stragglers (find-stragglers
+        :quantile-deviation) and cancelled (killable-cancelled-tasks).  Per running row: start_ms (A.START_ABSENT = none), unknown,
+        max_runtime_ms (< 0 = none), cancelled, group (index into `groups` or A.NONE_U32).  groups: dict of the per-group columns type,
+        quantile, multiplier, job_count and the successful instances as succ_off (CSR, n + 1), succ_start_ms, succ_end_ms (< 0 = none).
+        -> dict(reason [n] uint8 bits, lingering / stragglers / cancelled: row indices ascending, threshold_s [groups] float64 (NaN: not
+        ready or not type 1), info)."""
+        keep = []
+
+        def arr(x, dt):
+            if x is None:
+                return None
+            a = np.ascontiguousarray(x, dtype=dt)
+            keep.append(a)
+            return a
+
+        def ptr(a, t):
+            return _p(a, t) if a is not None and len(a) else None
+
+        st = arr(start_ms, np.int64)
+        n = len(st)
+        cols = [arr(unknown, np.uint8), arr(max_runtime_ms, np.int64), arr(cancelled, np.uint8), arr(group, np.uint32)]
+        assert all(c is None or len(c) == n for c in cols), "every running-set column has n entries"
+        ts = A.CookRunningSet(n, ptr(st, C.c_int64), ptr(cols[0], C.c_uint8), ptr(cols[1], C.c_int64), ptr(cols[2], C.c_uint8),
+                              ptr(cols[3], C.c_uint32))
+        gs, G = None, 0
+        if groups is not None:
+            ty = arr(groups["type"], np.uint8)
+            G = len(ty)
+            off = arr(groups.get("succ_off", np.zeros(G + 1)), np.uint32)
+            gs = A.CookStragglerGroups(G, ptr(ty, C.c_uint8), ptr(arr(groups["quantile"], np.float64), C.c_double),
+                                       ptr(arr(groups["multiplier"], np.float64), C.c_double), ptr(arr(groups["job_count"], np.uint32), C.c_uint32),
+                                       ptr(off, C.c_uint32), ptr(arr(groups.get("succ_start_ms", []), np.int64), C.c_int64),
+                                       ptr(arr(groups.get("succ_end_ms", []), np.int64), C.c_int64))
+        p = A.CookSweepParams(int(now_ms), int(default_timeout_ms), int(max_timeout_ms), int(what), 0)
+        cap = 3 * n if cap is None else int(cap)
+        reason = np.zeros(max(1, n), dtype=np.uint8)
+        idx = np.zeros(max(1, cap), dtype=np.uint32)
+        thr = np.zeros(max(1, G), dtype=np.float64)
+        info = A.CookSweepInfo()
+        rc = self._lib.cook_sweep_running(self._h, C.byref(ts), C.byref(gs) if gs is not None else None, C.byref(p), _p(reason, C.c_uint8),
+                                          _p(idx, C.c_uint32), cap, _p(thr, C.c_double), C.byref(info))
+        self.last_sweep_info = info.as_dict()  # (filled in on COOK_E_INVALID too: the list lengths, bad_row)
+        self._chk(rc)
+        L, S = info.lingering, info.stragglers
+        return dict(reason=reason[:n].copy(), lingering=idx[:L].copy(), stragglers=idx[L:L + S].copy(),
+                    cancelled=idx[L + S:L + S + info.cancelled].copy(), threshold_s=thr[:G].copy(), info=info.as_dict())
+
     # ---- rebalancer ------------------------------------------------------------------------------------------
     def rebalance_stage(self, running: A.Tasks, pending: A.Jobs, pending_job_id, pending_priority, users: A.Users,
                         spare: A.HostSpare, rparams: A.CookRebalanceParams, host_attrs: Optional[A.Offers] = None,

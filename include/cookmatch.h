@@ -336,6 +336,56 @@ typedef struct cook_autoscale_info {
 } cook_autoscale_info;
 int cook_cycle_autoscale(cook_engine* e, const cook_autoscale_params* p, uint32_t* task_idx, uint32_t cap, cook_autoscale_info* info);
 
+/* ---- SWEEP: the three task killers over the cluster's running set (scheduler.clj:1888-2016, group.clj:17-44) --------------------
+ * Stateless, like cook_offers_build: the engine handle only picks the device and stream; no rank, considerable, match, offers or
+ * rebalance state is read or written.  The running set is every :instance.status/running or /unknown instance (tools.clj:494-506).
+ *  bit 0 lingering (get-lingering-tasks): start_ms present and now_ms > start_ms + min(rt, max_timeout_ms), rt = max_runtime_ms if >= 0
+ *        else default_timeout_ms (strict: time/after?; evaluated without overflow).  Running and unknown rows.
+ *  bit 1 straggler (find-stragglers :quantile-deviation, type-1 groups only): idx = (int)trunc((double)((int64)job_count - 1) * quantile);
+ *        the group is READY iff its successful instances number more than idx; s = (end - start) / 1000 truncated (t/in-seconds; end < 0:
+ *        now_ms); threshold = (double)(idx-th smallest s) * multiplier (NaN: not ready or not type 1).  A running (not unknown) row of a
+ *        ready group is a straggler iff (double)((now_ms - start_ms) / 1000) > threshold.
+ *  bit 2 cancelled (killable-cancelled-tasks): cancelled[i] != 0, running or unknown.
+ * reason[i] = the bits of the killers that picked row i.  idx = lingering ++ stragglers ++ cancelled, each list in ascending row order (the
+ * reference's Datomic set order is unpinned: this order is oracle-defined); a row may sit in several lists.  A killer whose bit is off in
+ * `what` yields nothing and reads nothing.  More than cap entries: COOK_E_INVALID with info filled in.
+ * COOK_E_INVALID with info->bad_row where the reference throws, for the rows it evaluates (successful instances and running rows of ready
+ * type-1 groups): start absent, a negative interval or one above INT32_MAX seconds; bad_row = the lowest such running row, else n + the
+ * lowest such successful instance; a group index out of range counts as an offending row.  Also COOK_E_INVALID (bad_row = COOK_NONE_U32
+ * unless a row is at fault too) for a type-1 group with quantile outside (0, 1), multiplier <= 1 or either not finite, job_count >
+ * INT32_MAX, a type > 1, a decreasing succ_off or one that does not start at 0, a negative timeout, n > INT32_MAX.  The reference's straggler handler stops at the first group that throws;
+ * this call fails as a whole.  The first call on a handle allocates device memory. */
+typedef struct cook_running_set {
+  uint32_t n;
+  const int64_t* start_ms;        /* :instance/start-time; INT64_MIN = absent                                             */
+  const uint8_t* unknown;         /* 1 = :instance.status/unknown, 0 = running; NULL = all running                         */
+  const int64_t* max_runtime_ms;  /* :job/max-runtime of the row's job, < 0 = absent; NULL = all absent                     */
+  const uint8_t* cancelled;       /* :instance/cancelled; NULL = none                                                       */
+  const uint32_t* group;          /* the job's group (index into cook_straggler_groups) or COOK_NONE_U32; NULL = none       */
+} cook_running_set;
+typedef struct cook_straggler_groups {
+  uint32_t n;
+  const uint8_t* type;            /* 0 :straggler-handling.type/none, 1 :quantile-deviation                                */
+  const double* quantile;         /* type 1: 0 < q < 1 (api.clj:495-497)                                                   */
+  const double* multiplier;       /* type 1: > 1.0                                                                          */
+  const uint32_t* job_count;      /* (count (:group/job g)), jobs without instances included                                */
+  const uint32_t* succ_off;       /* [n + 1], succ_off[0] = 0: the :instance.status/success instances of the group's jobs  */
+  const int64_t* succ_start_ms;   /* [succ_off[n]]; INT64_MIN = absent                                                     */
+  const int64_t* succ_end_ms;     /* [succ_off[n]]; < 0 = no :instance/end-time -> now_ms (tools.clj:670-676)              */
+} cook_straggler_groups;
+typedef struct cook_sweep_params {
+  int64_t now_ms;
+  int64_t default_timeout_ms;     /* (or default-timeout-hours timeout-hours) in ms, >= 0                                  */
+  int64_t max_timeout_ms;         /* (or max-timeout-hours timeout-hours) in ms, >= 0                                      */
+  uint32_t what;                  /* bit 0 lingering, bit 1 stragglers, bit 2 cancelled                                     */
+  uint32_t reserved;              /* 0                                                                                      */
+} cook_sweep_params;
+typedef struct cook_sweep_info {
+  uint32_t lingering, stragglers, cancelled, groups_ready, bad_row;
+} cook_sweep_info;
+int cook_sweep_running(cook_engine* e, const cook_running_set* tasks, const cook_straggler_groups* groups, const cook_sweep_params* p,
+                       uint8_t* reason, uint32_t* idx, uint32_t cap, double* group_threshold_s, cook_sweep_info* info);
+
 /* ---- MATCH: replaces the body of match-offer-to-schedule, i.e. TaskScheduler.scheduleOnce -----------------
  * (scheduler.clj:617-687; Fenzo 0.10.0 pinned at project.clj:46-50; constraints.clj).
  * job_to_offer[k] = offer index or -1.  head_matched mirrors scheduler.clj:1495 (first considerable job matched,
