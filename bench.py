@@ -14,6 +14,11 @@ configs[3]).  The only cross-rank exchange is the all-reduce of per-pool running
 
 Launch: `python bench.py` (N=1) or
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N`.
+
+A plain run does only what the headline needs: it stages the inputs, warms up, times the steps, writes --dump-outputs and prints
+the line.  `--full` adds everything else the line can carry, each after the timed region: the roofline pass, the CPU baseline and
+the parity check of the timed cycle against the oracle, the extra configurations (K = 1000 / 1e5, good-enough 0.8, C2, C3, C5,
+both placement forms), the boundary leg and the adjacent rows; the --no-* options and --boundary choose among them.
 """
 from __future__ import annotations
 
@@ -46,6 +51,9 @@ def parse():
     ap.add_argument("--good-enough", type=float, default=1.0, help="1.0 = parity setting (zz_simulator.clj:84)")
     ap.add_argument("--no-constraints", action="store_true")
     ap.add_argument("--match-algo", type=int, default=0, help="cook_params.match_algo: 0 / 2 window rounds (eval, merge, resolve launches), 1 = the one-job-at-a-time sweep by a single workgroup")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the legs the headline does not need (roofline pass, cpu_baseline, parity check against "
+                         "the oracle, extra_configs, boundary, adjacent rows); the --no-* options below and --boundary apply to a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-adjacent", action="store_true", help="skip the timings of the rows next to the hot path (offers, explain, metrics)")
@@ -555,10 +563,12 @@ def main():
                       "group_usage_allreduced": np.asarray(cluster.last_group_usage).tolist(), "group_usage_equals_sum_over_all_pools": True,
                       "per_cycle": ["all_reduce(SUM) f64 [n_groups x 4] quota-group usage", f"all_reduce(SUM) f64 [{args.users} x 3] per-user usage"]}
 
-    mark("timed region done; roofline pass")
+    # ---- everything below up to the line itself runs with --full only: the headline needs none of it --------------------------
+    full = args.full
+    mark("timed region done" + ("; roofline pass" if full else ""))
     # ---- roofline of the dominant kernel: second pass with per-kernel HIP events on each engine's own stream ----
     roofline = None
-    if not args.no_roofline:  # every rank runs the pass (cycle() holds a collective); rank 0 reports
+    if full and not args.no_roofline:  # every rank runs the pass (cycle() holds a collective); rank 0 reports
         for p in my_pools:
             engines[p].set_profiling(True)
         for _ in range(max(1, min(args.steps, 3))):
@@ -614,10 +624,11 @@ def main():
     #      against the oracle, bit-exact — every pool of rank 0 when the concurrent baseline ran (its outputs are reused), else the
     #      first pool (first slot of a launch chain) and the last (last slot of another chain).  A fast wrong answer must not
     #      produce a number: a mismatch raises.
-    mark("cpu_baseline leg + parity of the timed configuration")
+    if full:
+        mark("cpu_baseline leg + parity of the timed configuration")
     cpu = None
     parity_checked, parity_pools = False, []
-    if rank == 0 and not (args.no_cpu_baseline and args.no_check):
+    if full and rank == 0 and not (args.no_cpu_baseline and args.no_check):
         cpu, oracle_out = (None, {})
         if not args.no_cpu_baseline and world == 1 and not args.as_rank_of:
             cpu, oracle_out = cpu_baseline_leg(args, params, cluster, pools, my_pools, K, n_off)
@@ -639,9 +650,10 @@ def main():
     # ---- SURVEY.md §8d's reporting matrix, beside the headline (never instead of it): the reference's default cap K = 1000
     #      (config.clj:113: launch / latency-bound, p50 and p95 in microseconds), K = 1e5, the reference's DEFAULT good-enough
     #      fitness 0.8 (config.clj:111), and BASELINE.json configs[1] / configs[2] as single pools.  N = 1 only.
-    mark("extra configurations")
+    if full:
+        mark("extra configurations")
     extra = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if full and rank == 0 and world == 1 and not args.no_extras:
         extra = {}
 
         def timed(fn, n, warm=1):
@@ -768,9 +780,10 @@ def main():
     #      one and takes the assignments back.  cook_cycle_update per pool (1 % of the tasks leave, as many arrive — half of them new
     #      submissions —, fresh offers) from page-locked columns, the cycle, cook_cycle_fetch into page-locked buffers; beside it the
     #      cost of restaging EVERYTHING from pageable and from page-locked memory (cook_cycle_stage).
-    mark("boundary leg")
+    if full:
+        mark("boundary leg")
     boundary = None
-    if rank == 0 and world == 1 and (args.boundary or not args.no_extras):
+    if full and rank == 0 and world == 1 and (args.boundary or not args.no_extras):
         from cook_amd.engine import PinnedArena
         arena = PinnedArena()
         try:
@@ -859,10 +872,11 @@ def main():
         finally:
             arena.close()  # (the engine reads host arrays only during a call)
 
-    mark("adjacent rows")
+    if full:
+        mark("adjacent rows")
     # ---- the rows either side of the path, timed once on rank 0's first pool; not part of `value` ----
     adjacent = None
-    if rank == 0 and not args.no_adjacent:
+    if full and rank == 0 and not args.no_adjacent:
         e0 = engines[my_pools[0]]
         _, j2o0, _ = e0.cycle_fetch()
         unm = np.nonzero(j2o0 < 0)[0][:64].astype(np.uint32)
@@ -890,7 +904,7 @@ def main():
             "metric": "match-cycles/sec at 1M pending x 50k offers" if not weak else f"match-cycles/sec at {world}M pending x {50 * world}k offers (weak scaling: 1M x 50k per GPU)",
             "value": value, "unit": "cycles/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "p50_cycle_latency_ms": lat_ms[len(lat_ms) // 2], "higher_is_better": True, "scaling": args.scaling,
+            "p50_cycle_latency_ms": lat_ms[len(lat_ms) // 2], "higher_is_better": True, "scaling": args.scaling, "full": full,
             "vs_baseline": None, "dtype": "f64", "data": "synthetic" if not rehearsal else "synthetic; REHEARSAL on the SIMT emulator (CPU, gloo): plumbing only, not a measurement",
             "config": {"workload": f"{P} pools x ({n_pend} pending + {n_run} running tasks, {n_off} offers), {args.users} users; "
                                    f"rank all tasks + match K={K} per pool"

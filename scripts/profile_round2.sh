@@ -15,8 +15,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B8="--steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras --no-adjacent"
-B1="--pools 1 --pending 125000 --running 50000 --offers 6250 --steps 2 --warmup 1 --no-cpu-baseline --no-check --no-extras --no-adjacent"
+B8="--steps 2 --warmup 1 --full --no-cpu-baseline --no-check --no-extras --no-adjacent"
+B1="--pools 1 --pending 125000 --running 50000 --offers 6250 --steps 2 --warmup 1 --full --no-cpu-baseline --no-check --no-extras --no-adjacent"
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY"
 cd /tmp
 kt() {  # name, command...

@@ -12,7 +12,7 @@ python scripts/kernel_rev.py > "$OUT/kernel_rev.txt"; cat "$OUT/kernel_rev.txt"
 bash scripts/profile_round2.sh "$TAG" > "$OUT/profile.log" 2>&1; tail -5 "$OUT/profile.log"
 cd "$ROOT"
 python scripts/make_pmc_traffic.py "gpurun_out/$TAG" "$TAG" && cp "profiles/${TAG}_pmc_traffic.json" "$OUT/pmc_traffic.json"
-timeout 600 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench exit $?"; tail -3 "$OUT/bench.err"
+timeout 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; echo "bench exit $?"; tail -3 "$OUT/bench.err"
 python - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))
@@ -23,7 +23,7 @@ PY
 # the rank parts as pool batches against a thread and a stream per pool, at this revision (the cycle, and the reference's default K = 1000)
 for v in "COOK_RANK_BATCHES=4" "COOK_RANK_BATCHES=1" "COOK_RANK_BATCH=0"; do
   for k in 0 1000; do
-    env $v timeout 200 python bench.py --no-cpu-baseline --no-adjacent --no-extras --no-roofline --steps 30 --warmup 3 --considerable $k > "$OUT/ab.json" 2> "$OUT/ab.err"
+    env $v timeout 200 python bench.py --full --no-cpu-baseline --no-adjacent --no-extras --no-roofline --steps 30 --warmup 3 --considerable $k > "$OUT/ab.json" 2> "$OUT/ab.err"
     python - "$v" "$k" "$OUT/ab.json" <<'PY' | tee -a "$OUT/rank_batch.txt"
 import json, sys
 try:

@@ -6,8 +6,8 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT
 for LIB in "$@"; do
   NAME=$(basename $LIB .so)
   if [ "$LIB" = default ]; then unset COOK_LIB; else export COOK_LIB=$PWD/$LIB; fi
-  timeout 120 python bench.py --pools 1 --pending 125000 --running 50000 --offers 6250 --steps 4 --warmup 1 --no-cpu-baseline --no-adjacent > $OUT/one_$NAME.json 2> $OUT/one_$NAME.err
-  timeout 120 python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-adjacent > $OUT/all_$NAME.json 2> $OUT/all_$NAME.err
+  timeout 120 python bench.py --pools 1 --pending 125000 --running 50000 --offers 6250 --steps 4 --warmup 1 --full --no-cpu-baseline --no-adjacent > $OUT/one_$NAME.json 2> $OUT/one_$NAME.err
+  timeout 120 python bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-adjacent > $OUT/all_$NAME.json 2> $OUT/all_$NAME.err
   python - <<PY
 import json
 for k in ("one", "all"):

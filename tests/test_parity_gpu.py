@@ -676,8 +676,8 @@ def test_bench_two_ranks_on_one_gpu():
         port = sk.getsockname()[1]
     env = dict(os.environ, COOK_BENCH_ONE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dist-backend", "gloo", "--no-cpu-baseline", "--no-extras",
-           "--no-adjacent", "--no-roofline"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--dist-backend", "gloo", "--full", "--no-cpu-baseline",
+           "--no-extras", "--no-adjacent", "--no-roofline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -220,7 +220,7 @@ def test_bench_self_launches_world2_over_gloo():
     lib = build_emu.build()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pools", "4", "--pending", "1600",
-           "--running", "800", "--offers", "96", "--users", "20", "--no-extras", "--no-adjacent", "--engine-lib", lib, "--dist-backend", "gloo"]
+           "--running", "800", "--offers", "96", "--users", "20", "--full", "--no-extras", "--no-adjacent", "--engine-lib", lib, "--dist-backend", "gloo"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -258,3 +258,37 @@ def test_bench_self_launches_world2_over_gloo():
     assert dw["scaling"] == "weak" and dw["n_gpus"] == 2 and dw["config"]["pools"] == 8 and dw["config"]["pending_total"] == 2 * doc["config"]["pending_total"]
     assert dw["collective"]["pools_of_rank"] == [[0, 2, 4, 6], [1, 3, 5, 7]] and dw["collective"]["group_usage_equals_sum_over_all_pools"] is True
     assert dw["parity_checked"] is True and dw["pair_evaluations_per_s"] > 0
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_is_lean(tmp_path):
+    """A plain `bench.py` run stages, warms up, times the steps, dumps and prints the line: no roofline pass, CPU baseline, parity check,
+    extras, boundary leg or adjacent rows (they run with --full).  What the timed cycles returned is the same either way."""
+    import json
+    import subprocess
+    sys.path.insert(0, os.path.join(ROOT, "tests", "simt_emu"))
+    import build_emu
+    lib = build_emu.build()
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--pools", "4", "--pending", "1600",
+           "--running", "800", "--offers", "96", "--users", "20", "--engine-lib", lib, "--dist-backend", "gloo"]
+    docs = {}
+    for kind, extra in (("plain", []), ("full", ["--full", "--no-extras", "--no-adjacent"])):
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / kind)], env=env, capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        docs[kind] = json.loads(lines[0])
+    plain, full = docs["plain"], docs["full"]
+    for d in (plain, full):
+        assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "cycles/s" and d["higher_is_better"] is True
+    assert plain["full"] is False and full["full"] is True
+    for k in ("roofline", "cpu_baseline", "extra_configs", "boundary", "adjacent_rows"):
+        assert plain[k] is None, k
+    assert plain["parity_checked"] is False and plain["parity"]["pools"] == []
+    assert full["parity_checked"] is True and full["cpu_baseline"] is not None and full["roofline"] is not None
+    assert plain["last_cycle"]["matched"] == full["last_cycle"]["matched"] and plain["last_cycle"]["considered"] == full["last_cycle"]["considered"]
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names and names == sorted(os.listdir(tmp_path / "full"))
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)), n
