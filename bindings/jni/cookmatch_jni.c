@@ -436,6 +436,38 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_userStatsMulti(JNIEnv* env, jclass c
   }
   return CHECKED(cook_user_stats_multi(es, (uint32_t)n, maps, (uint32_t)n_users, &l, pu, 0, st, t));
 }
+/* why the jobs of a pool wait (cook_unscheduled: the quota, share and queue-position reasons of cook.unscheduled/reasons) from the last
+ * rank: limits = the 7 pointer fields of cook_unsched_limits (quota_count, quota_cpus, quota_mem, quota_gpus, share_cpus, share_mem,
+ * share_gpus) over n_users = the engine's staged users, or a null array = the staged users' own; n_tasks = the staged task rows (the
+ * engine checks it, and every row of `rows`, against its own count); in_window = n_tasks bytes or null; rows = n_rows task rows or null
+ * (all n_tasks rows, n_rows ignored).  Outputs, direct buffers or null, n = n_rows (n_tasks when rows is null): reasons_out / queue_pos_out
+ * n uint32, total_out n x 4 doubles, ahead_out n_users x 10 uint32, list_len_out n_users uint32 */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_unscheduled(JNIEnv* env, jclass c, jlong h, jint n_users, jobjectArray limits, jint n_tasks,
+                                                        jobject in_window, jobject rows, jint n_rows, jobject reasons_out, jobject queue_pos_out,
+                                                        jobject total_out, jobject ahead_out, jobject list_len_out) {
+  int bad = 0;
+  const uint64_t nu = (uint64_t)(n_users > 0 ? n_users : 0), nt = (uint64_t)(n_tasks > 0 ? n_tasks : 0);
+  const uint64_t n = rows ? (uint64_t)(n_rows > 0 ? n_rows : 0) : nt;
+  cook_unsched_limits l;
+  const uint8_t* win = BUFN(const uint8_t, in_window, nt);
+  const uint32_t* rw = BUFN(const uint32_t, rows, n);
+  uint32_t* reasons = BUFN(uint32_t, reasons_out, n);
+  uint32_t* qpos = BUFN(uint32_t, queue_pos_out, n);
+  double* total = BUFN(double, total_out, n * 4u);
+  uint32_t* ahead = BUFN(uint32_t, ahead_out, nu * COOK_UNSCHED_AHEAD);
+  uint32_t* llen = BUFN(uint32_t, list_len_out, nu);
+  (void)c;
+  if (n_users < 0 || n_tasks < 0 || n_rows < 0) return COOK_E_INVALID;
+  l.n = (uint32_t)n_users;
+  l.quota_count = (const double*)elem_n(env, limits, 0, nu * sizeof(const double), &bad);
+  l.quota_cpus = (const double*)elem_n(env, limits, 1, nu * sizeof(const double), &bad);
+  l.quota_mem = (const double*)elem_n(env, limits, 2, nu * sizeof(const double), &bad);
+  l.quota_gpus = (const double*)elem_n(env, limits, 3, nu * sizeof(const double), &bad);
+  l.share_cpus = (const double*)elem_n(env, limits, 4, nu * sizeof(const double), &bad);
+  l.share_mem = (const double*)elem_n(env, limits, 5, nu * sizeof(const double), &bad);
+  l.share_gpus = (const double*)elem_n(env, limits, 6, nu * sizeof(const double), &bad);
+  return CHECKED(cook_unscheduled(H(h), limits ? &l : 0, win, rw, (uint32_t)(rows ? n_rows : n_tasks), reasons, qpos, total, 0, ahead, llen));
+}
 JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleMatchMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n) {
   cook_engine* es[64];
   int bad = 0;

@@ -914,6 +914,53 @@ def user_stats_result(per_user: np.ndarray, state: np.ndarray, totals: CookUserS
                         "hungry": totals.hungry, "satisfied": totals.satisfied})
 
 
+# ---- why a job waits (cook_unscheduled: unscheduled.clj:37-77 check-exceeds-limit, :128-158 check-queue-position) -------------------
+UNSCHED_QUOTA_COUNT, UNSCHED_QUOTA_CPUS, UNSCHED_QUOTA_MEM, UNSCHED_QUOTA_GPUS = 1, 2, 4, 8
+UNSCHED_SHARE_CPUS, UNSCHED_SHARE_MEM, UNSCHED_SHARE_GPUS = 16, 32, 64
+UNSCHED_QUEUE_POSITION, UNSCHED_AT_LEAST = 128, 256
+UNSCHED_AHEAD = 10                                  # rows of a user's list that are returned
+UNSCHED_RESOURCES = ("count", "cpus", "mem", "gpus")  # the columns of total; bit k of the quota bits, bit 4 + (k - 1) of the share bits
+
+
+class CookUnschedLimits(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("quota_count", _f64p), ("quota_cpus", _f64p), ("quota_mem", _f64p), ("quota_gpus", _f64p),
+                ("share_cpus", _f64p), ("share_mem", _f64p), ("share_gpus", _f64p)]
+
+
+@dataclass
+class UnschedLimits:
+    """get-quota (quota.clj:82-110; :count unset = 2^31 - 1, the others DMAX) and get-share (share.clj:105-119; unset = DMAX) per
+    user id."""
+    quota_count: np.ndarray
+    quota_cpus: Optional[np.ndarray] = None
+    quota_mem: Optional[np.ndarray] = None
+    quota_gpus: Optional[np.ndarray] = None
+    share_cpus: Optional[np.ndarray] = None
+    share_mem: Optional[np.ndarray] = None
+    share_gpus: Optional[np.ndarray] = None
+
+    def __post_init__(self):
+        n = len(self.quota_count)
+        for k in ("quota_count", "quota_cpus", "quota_mem", "quota_gpus", "share_cpus", "share_mem", "share_gpus"):
+            v = getattr(self, k)
+            setattr(self, k, _arr(v if v is not None else np.full(n, DMAX, dtype=np.float64), np.float64, n))
+
+    @property
+    def n(self):
+        return len(self.quota_count)
+
+    @staticmethod
+    def from_users(users: "Users") -> "UnschedLimits":
+        """what a NULL limits argument means: the staged users' quotas as they are, their DRU divisors as shares"""
+        return UnschedLimits(users.quota_count, users.quota_cpus, users.quota_mem, users.quota_gpus, users.div_cpus, users.div_mem,
+                             users.div_gpus)
+
+    def as_struct(self) -> CookUnschedLimits:
+        return CookUnschedLimits(self.n, _ptr(self.quota_count, _f64p), _ptr(self.quota_cpus, _f64p), _ptr(self.quota_mem, _f64p),
+                                 _ptr(self.quota_gpus, _f64p), _ptr(self.share_cpus, _f64p), _ptr(self.share_mem, _f64p),
+                                 _ptr(self.share_gpus, _f64p))
+
+
 # ---- autoscaling candidates (cook_cycle_autoscale: handle-resource-offers-autoscaling-helper, scheduler.clj:1283-1335) ----------------
 class CookAutoscaleParams(C.Structure):
     _fields_ = [("max_jobs", C.c_uint32), ("n_exclude", C.c_uint32), ("scale_factor", C.c_double), ("offer_skipped", _u8p),

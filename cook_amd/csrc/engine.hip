@@ -133,6 +133,7 @@ struct UpdateBufs;   // cycle_update.hpp
 struct UserStatsBufs;  // user_stats_host.hpp
 struct AutoscaleBufs;  // autoscale_host.hpp
 struct SweepBufs;      // sweep_host.hpp
+struct UnschedBufs;    // unscheduled_host.hpp
 
 }  // namespace
 
@@ -264,6 +265,7 @@ struct cook_engine {
   UserStatsBufs* usb = nullptr;  // cook_user_stats* (allocated on first use)
   AutoscaleBufs* asb = nullptr;  // cook_cycle_autoscale (allocated on first use)
   SweepBufs* swb = nullptr;      // cook_sweep_running (allocated on first use)
+  UnschedBufs* unb = nullptr;    // cook_unscheduled (allocated on first use)
   MatchIn last_in{};  // the MatchIn of the last match run (K, j_index as used)
   bool last_in_valid = false;
   unsigned rlog_id = 0;  // suffix of this engine's COOK_ROUND_LOG file
@@ -2064,6 +2066,7 @@ struct StageTimer {
 #include "user_stats_host.hpp"
 #include "autoscale_host.hpp"
 #include "sweep_host.hpp"
+#include "unscheduled_host.hpp"
 
 ConsBufs& cons_bufs(cook_engine* e) {
   if (!e->cb) e->cb = new ConsBufs();
@@ -2210,6 +2213,8 @@ void cook_engine_destroy(cook_engine* e) {
   e->asb = nullptr;
   delete e->swb;
   e->swb = nullptr;
+  delete e->unb;
+  e->unb = nullptr;
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -2552,6 +2557,14 @@ int cook_user_stats_multi(cook_engine** engines, uint32_t n, const uint32_t* con
   }
   return guarded(engines[0], [&] {
     user_stats_run(engines, n, user_map, n_users, group_limits, per_user, per_user_is_device != 0, user_state, totals);
+  });
+}
+int cook_unscheduled(cook_engine* e, const cook_unsched_limits* limits, const uint8_t* in_window, const uint32_t* rows, uint32_t n_rows,
+                     uint32_t* reasons, uint32_t* queue_pos, double* total, int total_is_device, uint32_t* ahead, uint32_t* list_len) {
+  if (!e) return COOK_E_INVALID;
+  return guarded(e, [&] {
+    unscheduled_run(e, limits, in_window, rows, n_rows, reasons, queue_pos, total, total_is_device != 0, ahead, list_len);
+    prof_collect(e);
   });
 }
 int cook_cycle_match_multi(cook_engine** engines, uint32_t n) {

@@ -113,6 +113,7 @@ class Engine:
     def rank_stage(self, tasks: A.Tasks, users: A.Users):
         ts, us = tasks.as_struct(), users.as_struct()
         self._rank_n, self._rank_np = tasks.n, int(tasks.pending.sum()) if tasks.n else 0
+        self._tasks_n = tasks.n  # the staged table's row count, exactly (unscheduled sizes its outputs by it)
         self._n_users = users.n
         self._chk(self._lib.cook_rank_stage(self._h, C.byref(ts), C.byref(us)))
 
@@ -143,6 +144,34 @@ class Engine:
         out = _StatsOut(n, per_user_device_ptr)
         _check_multi([self], self._lib.cook_user_stats(self._h, lim, *out.args()))
         return out.result()
+
+    def unscheduled(self, limits: Optional[A.UnschedLimits] = None, in_window=None, rows=None, total_device_ptr: Optional[int] = None) -> dict:
+        """Why the jobs of this pool wait, from the last rank run (cook_unscheduled): the quota, share and queue-position reasons of
+        cook.unscheduled/reasons for every task row, or for the task rows `rows` (any order, repeats allowed).  limits None: the staged
+        users' quotas and their divisors as shares.  in_window ([tasks.n] bytes): the pending rows the host's "first 100 waiting jobs"
+        query returns, None = all.  -> dict(reasons [n] uint32 (A.UNSCHED_* bits), queue_pos [n] uint32, total [n, 4] float64
+        ({count, cpus, mem, gpus}; None with total_device_ptr, the address of a device buffer of n x 4 doubles), ahead [U, 10] uint32
+        task rows (A.NONE_U32 = none), list_len [U] uint32)."""
+        N, U = getattr(self, "_tasks_n", 0), getattr(self, "_n_users", 0)
+        lim = C.byref(limits.as_struct()) if limits is not None else None
+        win = None
+        if in_window is not None:
+            win = np.ascontiguousarray(in_window, dtype=np.uint8)
+            assert len(win) == N, "in_window has one byte per task row"
+        rw = np.ascontiguousarray(rows, dtype=np.uint32) if rows is not None else None
+        n = len(rw) if rw is not None else N
+        reasons = np.zeros(max(1, n), dtype=np.uint32)
+        qpos = np.zeros(max(1, n), dtype=np.uint32)
+        total = np.zeros((max(1, n), 4), dtype=np.float64) if total_device_ptr is None else None
+        ahead = np.zeros((max(1, U), A.UNSCHED_AHEAD), dtype=np.uint32)
+        llen = np.zeros(max(1, U), dtype=np.uint32)
+        # (an empty list of rows still is a list: numpy's pointer to an empty array is not NULL)
+        self._chk(self._lib.cook_unscheduled(
+            self._h, lim, win.ctypes.data_as(C.c_void_p) if win is not None else None,
+            rw.ctypes.data_as(C.c_void_p) if rw is not None else None, n, reasons.ctypes.data_as(C.c_void_p),
+            qpos.ctypes.data_as(C.c_void_p), C.c_void_p(int(total_device_ptr)) if total is None else total.ctypes.data_as(C.c_void_p),
+            int(total is None), ahead.ctypes.data_as(C.c_void_p), llen.ctypes.data_as(C.c_void_p)))
+        return dict(reasons=reasons[:n], queue_pos=qpos[:n], total=total[:n] if total is not None else None, ahead=ahead[:U], list_len=llen[:U])
 
     def rank_run(self):
         self._chk(self._lib.cook_rank_run(self._h))
@@ -204,6 +233,7 @@ class Engine:
         gs = groups.as_struct() if groups is not None else None
         res = np.array(list(reserved_hosts) or [0], dtype=np.uint32)
         self._rank_n, self._rank_np = tasks.n, int(tasks.pending.sum()) if tasks.n else 0
+        self._tasks_n = tasks.n  # the staged table's row count, exactly (unscheduled sizes its outputs by it)
         self._chk(self._lib.cook_cycle_stage(self._h, C.byref(ts), C.byref(us), C.byref(js), C.byref(os_),
                                              C.byref(gs) if gs is not None else None, _p(res, C.c_uint32),
                                              len(reserved_hosts)))
@@ -223,6 +253,7 @@ class Engine:
         p_add = int(add_tasks.pending.sum()) if n_add else 0
         # the mirror's sizes for the fetch buffers: upper bounds (removed rows only shrink them)
         self._rank_n = self._rank_n + n_add
+        self._tasks_n = getattr(self, "_tasks_n", 0) + n_add - len(rem)  # (an accepted delta removes each listed row once)
         self._rank_np = self._rank_np + p_add
 
     def cycle_run(self, num_considerable: int):
@@ -470,6 +501,7 @@ class Engine:
         gs = groups.as_struct() if groups is not None else None
         res = np.array(list(reserved_hosts) or [0], dtype=np.uint32)
         self._rank_n, self._rank_np = tasks.n, int(tasks.pending.sum()) if tasks.n else 0
+        self._tasks_n = tasks.n  # the staged table's row count, exactly (unscheduled sizes its outputs by it)
         self._chk(self._lib.cook_cycle_stage_built_offers(self._h, C.byref(ts), C.byref(us), C.byref(js),
                                                           C.byref(gs) if gs is not None else None, _p(res, C.c_uint32),
                                                           len(reserved_hosts), int(bool(with_task_limits))))

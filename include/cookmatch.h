@@ -599,6 +599,65 @@ int cook_user_stats_multi(cook_engine** engines, uint32_t n, const uint32_t* con
                           const cook_user_limits* group_limits, double* per_user, int per_user_is_device, uint8_t* user_state,
                           cook_user_stats_totals* totals);
 
+/* ---- UNSCHEDULED: the reasons of /unscheduled_jobs that need the user's whole task list, from the last rank, on the device ----------
+ * cook.unscheduled/reasons (unscheduled.clj:178-206) asks, for ONE waiting job, two Datomic queries (the user's running jobs, the
+ * user's first 100 waiting jobs of the last 7 days), sorts the tasks with same-user-task-comparator and sums every running job's
+ * usage.  cook_unscheduled answers the three reasons that are made of that data for every row of the staged task table at once, or
+ * for a list of rows:
+ *  - check-exceeds-limit with quota/get-quota and with share/get-share (:37-77, how-job-would-exceed-resource-limits), pending rows
+ *    only: total[k] = (sum over the user's running rows of k) + the job's own k, k in {count (1 per row), cpus, mem, gpus (0.0 where
+ *    the gpus column is NULL)}; COOK_UNSCHED_QUOTA_{COUNT,CPUS,MEM,GPUS} iff total[k] > quota[k], COOK_UNSCHED_SHARE_{CPUS,MEM,GPUS}
+ *    iff total[k] > share[k] (strict, :48).  total holds the :usage numbers of the reason's data map; the :limit numbers are the
+ *    caller's inputs.  A running row gets none of these bits and zeros in total.
+ *  - check-queue-position (:128-158).  A user's LIST is its running rows plus its pending rows that are in the window, in the user's
+ *    task order of the last rank (tools.clj:614-641: sorted-tasks).  A running row stands for "the last running instance of a running
+ *    job", as everywhere in the engine (one row per job).  queue_pos = the number of list entries in front of the row when the row is
+ *    in the list; otherwise the list's length, and COOK_UNSCHED_AT_LEAST is set ("You have at least N other jobs ...").
+ *    COOK_UNSCHED_QUEUE_POSITION iff queue_pos > 0 ((seq tasks-ahead)).  The tasks ahead are the first min(queue_pos, 10) entries of
+ *    the user's list: ahead[u][0..9] (task rows, COOK_NONE_U32 beyond the list's length) and list_len[u] are returned once per user.
+ * in_window (optional, [tasks.n] bytes by task row): for a pending row, whether the host's "first 100 waiting jobs of the last 7 days"
+ * query (:117-126, 196) returns that job; NULL = every pending row.  It is an input mask like cook_queue's eligible: the engine does
+ * not know Datomic's order.  Running rows ignore it.
+ * Oracle-defined where the reference depends on Datomic order: the reference sums (conj running-jobs job) over a query result; here
+ * the running rows are added left to right in the user's task order, starting from the first of them, and the job last.  Every
+ * returned sum is bit-identical to that sequential sum for any fp64 inputs (exactness tracked over every prefix, a user whose sums
+ * rounded is folded again left to right).
+ * What stays with the host: check-exhausted-retries (two Datomic attributes), check-launch-rate-limit (the host holds
+ * cook_considerable's rate_limited counts; the caveat at that call applies), check-plugin-filter, check-fenzo-placement
+ * (cook_match_explain), the message strings and the job UUIDs behind the row numbers.
+ * The call reads the per-user order of the LAST rank run in place and writes nothing that rank, considerable, match, autoscale or any
+ * other call reads.  Before any cook_rank_run / cook_cycle_run*, and after a cook_rank_stage or cook_cycle_update that no rank has
+ * followed: COOK_E_STATE (the rule of cook_user_stats). */
+typedef struct cook_unsched_limits {
+  uint32_t n;                 /* users (the engine's U)                                                                       */
+  const double* quota_count;  /* [n] get-quota (quota.clj:82-110): :count, :cpus, :mem, :gpus; unset = DBL_MAX (count 2^31 - 1)  */
+  const double* quota_cpus;
+  const double* quota_mem;
+  const double* quota_gpus;
+  const double* share_cpus;   /* [n] get-share (share.clj:105-119): :cpus, :mem, :gpus; unset = DBL_MAX                          */
+  const double* share_mem;
+  const double* share_gpus;
+} cook_unsched_limits;
+#define COOK_UNSCHED_QUOTA_COUNT 1u
+#define COOK_UNSCHED_QUOTA_CPUS 2u
+#define COOK_UNSCHED_QUOTA_MEM 4u
+#define COOK_UNSCHED_QUOTA_GPUS 8u
+#define COOK_UNSCHED_SHARE_CPUS 16u
+#define COOK_UNSCHED_SHARE_MEM 32u
+#define COOK_UNSCHED_SHARE_GPUS 64u
+#define COOK_UNSCHED_QUEUE_POSITION 128u
+#define COOK_UNSCHED_AT_LEAST 256u
+#define COOK_UNSCHED_AHEAD 10u
+/* limits NULL: the engine's staged cook_users (its div_* as shares, its quota_*); a wrong n or a NULL column: COOK_E_INVALID.
+ * rows (optional): n_rows task-row indices into the staged cook_tasks, any order, repeats allowed, running or pending; NULL = all
+ * tasks.n rows in row order; n_rows is then 0, or the caller's idea of tasks.n, which is checked (a binding that sized its buffers by
+ * it: COOK_E_INVALID when it is wrong).  A row >= tasks.n: COOK_E_INVALID, nothing written.
+ * Outputs, each optional, caller-allocated, n = n_rows (tasks.n when rows is NULL): reasons[n] (COOK_UNSCHED_* bits), queue_pos[n],
+ * total[n][4] = {count, cpus, mem, gpus} (total_is_device != 0: a DEVICE pointer, nothing of it is copied to the host),
+ * ahead[U][COOK_UNSCHED_AHEAD], list_len[U]. */
+int cook_unscheduled(cook_engine* e, const cook_unsched_limits* limits, const uint8_t* in_window, const uint32_t* rows, uint32_t n_rows,
+                     uint32_t* reasons, uint32_t* queue_pos, double* total, int total_is_device, uint32_t* ahead, uint32_t* list_len);
+
 /* ---- OFFERS: replaces the numeric core of kubernetes.compute-cluster/generate-offers ----------------------
  * (kubernetes/compute_cluster.clj:68-190: available = capacity - consumption per node, the schedulable filter, the
  * offer resources and the capacity / consumption totals it publishes; kubernetes/api.clj:747-765 convert-resource-map,
