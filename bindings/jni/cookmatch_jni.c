@@ -468,6 +468,75 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_unscheduled(JNIEnv* env, jclass c, j
   l.share_gpus = (const double*)elem_n(env, limits, 6, nu * sizeof(const double), &bad);
   return CHECKED(cook_unscheduled(H(h), limits ? &l : 0, win, rw, (uint32_t)(rows ? n_rows : n_tasks), reasons, qpos, total, 0, ahead, llen));
 }
+/* GET /usage with its job-group breakdown from the last rank (cook_usage_breakdown): group_of_row = n_tasks uint32 (the staged task rows;
+ * interned group ids below n_groups, COOK_NONE_U32 = none) or null; users = n_list user ids or null (all n_users users, n_list ignored);
+ * cap_rows = the room of the outputs in rows.  Outputs, direct buffers or null, n_out = n_list (n_users when users is null):
+ * bucket_off_out n_out + 1 uint32, bucket_group_out cap_rows uint32, bucket_usage_out cap_rows x 4 doubles, row_off_out cap_rows + 1
+ * uint32, rows_out cap_rows uint32, total_out n_out x 4 doubles; counts_out = 2 uint32 {buckets, rows} (also filled in when cap_rows
+ * is too small) */
+static cook_usage_out usage_out_of(JNIEnv* env, uint64_t n_out, uint64_t cap, uint64_t stride, jobject bucket_off_out, jobject bucket_group_out,
+                                   jobject bucket_usage_out, jobject row_off_out, jobject rows_out, jobject total_out, int* badp) {
+  cook_usage_out o;
+  int bad = 0;
+  o.cap_rows = (uint32_t)cap;
+  o.n_buckets = 0, o.n_rows = 0, o.bucket_usage_is_device = 0, o.total_is_device = 0, o.reserved = 0;
+  o.bucket_off = BUFN(uint32_t, bucket_off_out, n_out + 1u);
+  o.bucket_group = BUFN(uint32_t, bucket_group_out, cap);
+  o.bucket_usage = BUFN(double, bucket_usage_out, cap * 4u);
+  o.row_off = BUFN(uint32_t, row_off_out, cap + 1u);
+  o.rows = BUFN(uint32_t, rows_out, cap * stride);
+  o.total = BUFN(double, total_out, n_out * 4u);
+  if (bad) *badp = 1;
+  return o;
+}
+JNIEXPORT jint JNICALL Java_cook_hip_Native_usageBreakdown(JNIEnv* env, jclass c, jlong h, jint n_users, jint n_tasks, jobject group_of_row,
+                                                           jint n_groups, jobject users, jint n_list, jint cap_rows, jobject bucket_off_out,
+                                                           jobject bucket_group_out, jobject bucket_usage_out, jobject row_off_out,
+                                                           jobject rows_out, jobject total_out, jobject counts_out) {
+  int bad = 0, rc;
+  const uint64_t nl = (uint64_t)(n_list > 0 ? n_list : 0), n_out = users ? nl : (uint64_t)(n_users > 0 ? n_users : 0);
+  const uint32_t* grp = BUFN(const uint32_t, group_of_row, n_tasks > 0 ? n_tasks : 0);
+  const uint32_t* ul = BUFN(const uint32_t, users, nl);
+  uint32_t* counts = BUFN(uint32_t, counts_out, 2);
+  cook_usage_out o = usage_out_of(env, n_out, (uint64_t)(cap_rows > 0 ? cap_rows : 0), 1u, bucket_off_out, bucket_group_out, bucket_usage_out,
+                                  row_off_out, rows_out, total_out, &bad);
+  (void)c;
+  if (bad || n_users < 0 || n_tasks < 0 || n_groups < 0 || n_list < 0 || cap_rows < 0) return COOK_E_INVALID;
+  rc = cook_usage_breakdown(H(h), grp, (uint32_t)n_groups, ul, (uint32_t)nl, &o);
+  if (counts) counts[0] = o.n_buckets, counts[1] = o.n_rows;
+  return rc;
+}
+/* ... without a pool, over n engines of one device (cook_usage_breakdown_multi): groups = n direct buffers of the engines' group_of_row
+ * (a null array or element: ungrouped; their length is the engine's task count, which only the engine knows), user_maps as in
+ * userStatsMulti, n_users the users of the call; rows_out holds cap_rows x 2 uint32 {engine index, task row} */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_usageBreakdownMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n,
+                                                                jobjectArray user_maps, jint n_users, jobjectArray groups, jint n_groups,
+                                                                jobject users, jint n_list, jint cap_rows, jobject bucket_off_out,
+                                                                jobject bucket_group_out, jobject bucket_usage_out, jobject row_off_out,
+                                                                jobject rows_out, jobject total_out, jobject counts_out) {
+  cook_engine* es[64];
+  const uint32_t* maps[64];
+  const uint32_t* grps[64];
+  int bad = 0, rc;
+  const uint64_t nl = (uint64_t)(n_list > 0 ? n_list : 0), n_out = users ? nl : (uint64_t)(n_users > 0 ? n_users : 0);
+  const int64_t* hs = BUFN(const int64_t, handles, n > 0 ? n : 0);
+  const uint32_t* ul = BUFN(const uint32_t, users, nl);
+  uint32_t* counts = BUFN(uint32_t, counts_out, 2);
+  cook_usage_out o = usage_out_of(env, n_out, (uint64_t)(cap_rows > 0 ? cap_rows : 0), 2u, bucket_off_out, bucket_group_out, bucket_usage_out,
+                                  row_off_out, rows_out, total_out, &bad);
+  jint i;
+  (void)c;
+  if (bad || !hs || n <= 0 || n > 64 || n_users < 0 || n_groups < 0 || n_list < 0 || cap_rows < 0) return COOK_E_INVALID;
+  for (i = 0; i < n; ++i) {
+    es[i] = H(hs[i]);
+    maps[i] = (const uint32_t*)elem_n(env, user_maps, i, 0, &bad);
+    grps[i] = (const uint32_t*)elem_n(env, groups, i, 0, &bad);
+  }
+  if (bad) return COOK_E_INVALID;
+  rc = cook_usage_breakdown_multi(es, (uint32_t)n, maps, (uint32_t)n_users, grps, (uint32_t)n_groups, ul, (uint32_t)nl, &o);
+  if (counts) counts[0] = o.n_buckets, counts[1] = o.n_rows;
+  return rc;
+}
 JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleMatchMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n) {
   cook_engine* es[64];
   int bad = 0;

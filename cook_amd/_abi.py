@@ -961,6 +961,16 @@ class UnschedLimits:
                                  _ptr(self.share_gpus, _f64p))
 
 
+# ---- GET /usage with its job-group breakdown (cook_usage_breakdown*: rest/api.clj:2894-2969, tools.clj:294-306) ---------------------
+USAGE_COLUMNS = ("cpus", "mem", "gpus", "jobs")  # the columns of bucket_usage and total
+
+
+class CookUsageOut(C.Structure):
+    _fields_ = [("cap_rows", C.c_uint32), ("n_buckets", C.c_uint32), ("n_rows", C.c_uint32), ("bucket_usage_is_device", C.c_int32),
+                ("total_is_device", C.c_int32), ("reserved", C.c_uint32), ("bucket_off", _u32p), ("bucket_group", _u32p),
+                ("bucket_usage", _f64p), ("row_off", _u32p), ("rows", _u32p), ("total", _f64p)]
+
+
 # ---- autoscaling candidates (cook_cycle_autoscale: handle-resource-offers-autoscaling-helper, scheduler.clj:1283-1335) ----------------
 class CookAutoscaleParams(C.Structure):
     _fields_ = [("max_jobs", C.c_uint32), ("n_exclude", C.c_uint32), ("scale_factor", C.c_double), ("offer_skipped", _u8p),

@@ -134,6 +134,7 @@ struct UserStatsBufs;  // user_stats_host.hpp
 struct AutoscaleBufs;  // autoscale_host.hpp
 struct SweepBufs;      // sweep_host.hpp
 struct UnschedBufs;    // unscheduled_host.hpp
+struct UsageBufs;      // usage_host.hpp
 
 }  // namespace
 
@@ -266,6 +267,7 @@ struct cook_engine {
   AutoscaleBufs* asb = nullptr;  // cook_cycle_autoscale (allocated on first use)
   SweepBufs* swb = nullptr;      // cook_sweep_running (allocated on first use)
   UnschedBufs* unb = nullptr;    // cook_unscheduled (allocated on first use)
+  UsageBufs* ugb = nullptr;      // cook_usage_breakdown* (allocated on first use)
   MatchIn last_in{};  // the MatchIn of the last match run (K, j_index as used)
   bool last_in_valid = false;
   unsigned rlog_id = 0;  // suffix of this engine's COOK_ROUND_LOG file
@@ -2067,6 +2069,7 @@ struct StageTimer {
 #include "autoscale_host.hpp"
 #include "sweep_host.hpp"
 #include "unscheduled_host.hpp"
+#include "usage_host.hpp"
 
 ConsBufs& cons_bufs(cook_engine* e) {
   if (!e->cb) e->cb = new ConsBufs();
@@ -2215,6 +2218,8 @@ void cook_engine_destroy(cook_engine* e) {
   e->swb = nullptr;
   delete e->unb;
   e->unb = nullptr;
+  delete e->ugb;
+  e->ugb = nullptr;
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -2565,6 +2570,28 @@ int cook_unscheduled(cook_engine* e, const cook_unsched_limits* limits, const ui
   return guarded(e, [&] {
     unscheduled_run(e, limits, in_window, rows, n_rows, reasons, queue_pos, total, total_is_device != 0, ahead, list_len);
     prof_collect(e);
+  });
+}
+int cook_usage_breakdown(cook_engine* e, const uint32_t* group_of_row, uint32_t n_groups, const uint32_t* users, uint32_t n_list,
+                         cook_usage_out* out) {
+  if (!e) return COOK_E_INVALID;
+  return guarded(e, [&] {
+    usage_run(&e, 1, nullptr, e->U, &group_of_row, n_groups, users, n_list, out, false);
+    prof_collect(e);
+  });
+}
+int cook_usage_breakdown_multi(cook_engine** engines, uint32_t n, const uint32_t* const* user_map, uint32_t n_users,
+                               const uint32_t* const* group_of_row, uint32_t n_groups, const uint32_t* users, uint32_t n_list,
+                               cook_usage_out* out) {
+  if (!engines || n == 0) return COOK_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!engines[i] || engines[i]->device != engines[0]->device) return COOK_E_INVALID;
+    for (uint32_t k = 0; k < i; ++k)
+      if (engines[i] == engines[k]) return COOK_E_INVALID;
+  }
+  return guarded(engines[0], [&] {
+    usage_run(engines, n, user_map, n_users, group_of_row, n_groups, users, n_list, out, true);
+    prof_collect(engines[0]);
   });
 }
 int cook_cycle_match_multi(cook_engine** engines, uint32_t n) {

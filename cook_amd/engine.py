@@ -173,6 +173,20 @@ class Engine:
             int(total is None), ahead.ctypes.data_as(C.c_void_p), llen.ctypes.data_as(C.c_void_p)))
         return dict(reasons=reasons[:n], queue_pos=qpos[:n], total=total[:n] if total is not None else None, ahead=ahead[:U], list_len=llen[:U])
 
+    def usage_breakdown(self, group_of_row=None, n_groups: int = 0, users=None, usage_device_ptr: Optional[int] = None,
+                        total_device_ptr: Optional[int] = None, cap_rows: Optional[int] = None) -> dict:
+        """GET /usage of this pool with its job-group breakdown, from the last rank run (cook_usage_breakdown).  group_of_row
+        ([tasks.n] uint32 by task row: interned group ids below n_groups, A.NONE_U32 = no group; None = every row ungrouped); users:
+        a list of user ids (any order, repeats allowed) instead of all users.  -> dict(bucket_off [n_out + 1], bucket_group [B]
+        (A.NONE_U32 = the ungrouped bucket, which comes first among a user's), bucket_usage [B, 4] float64 ({cpus, mem, gpus, jobs}),
+        row_off [B + 1], rows [R] task rows, total [n_out, 4]).  usage_device_ptr / total_device_ptr: the address of a device buffer
+        of cap_rows x 4 / n_out x 4 doubles; that entry of the dict is None then.  cap_rows: room for the rows (default: every task
+        row, and what a list with repeats asks for)."""
+        g = np.ascontiguousarray(group_of_row, dtype=np.uint32) if group_of_row is not None else None
+        assert g is None or len(g) == getattr(self, "_tasks_n", len(g)), "group_of_row has one id per task row"
+        return _usage_call([self], False, getattr(self, "_n_users", 0), None, [g], n_groups, users, usage_device_ptr, total_device_ptr,
+                           cap_rows)
+
     def rank_run(self):
         self._chk(self._lib.cook_rank_run(self._h))
 
@@ -645,6 +659,61 @@ def user_stats_multi(engines: Sequence[Engine], limits: A.UserLimits, user_maps:
     out = _StatsOut(n, per_user_device_ptr)
     _check_multi(engines, engines[0]._lib.cook_user_stats_multi(arr, len(engines), maps, n, C.byref(lim), *out.args()))
     return out.result()
+
+
+def _usage_call(engines, multi, n_users, user_maps, groups, n_groups, users, usage_device_ptr, total_device_ptr, cap_rows):
+    """one cook_usage_breakdown* call; a list of users whose rows need more room than cap_rows is asked again with the room it named"""
+    lib = engines[0]._lib
+    ul = np.ascontiguousarray(users, dtype=np.uint32) if users is not None else None
+    n_out = len(ul) if ul is not None else n_users
+    stride = 2 if multi else 1
+    cap = int(cap_rows) if cap_rows is not None else sum(getattr(e, "_tasks_n", 0) for e in engines)
+    arr = (C.c_void_p * len(engines))(*[e._h for e in engines])
+    gs = (C.c_void_p * len(engines))(*[g.ctypes.data if g is not None else None for g in groups])
+    maps = None
+    if user_maps is not None:
+        ms = [np.ascontiguousarray(m, dtype=np.uint32) if m is not None else None for m in user_maps]
+        assert len(ms) == len(engines)
+        maps = (C.c_void_p * len(engines))(*[m.ctypes.data if m is not None else None for m in ms])
+    while True:
+        boff = np.zeros(n_out + 1, dtype=np.uint32)
+        bgroup = np.zeros(max(1, cap), dtype=np.uint32)
+        busage = np.zeros((max(1, cap), 4), dtype=np.float64) if usage_device_ptr is None else None
+        roff = np.zeros(cap + 1, dtype=np.uint32)
+        rows = np.zeros((max(1, cap), stride), dtype=np.uint32)
+        total = np.zeros((max(1, n_out), 4), dtype=np.float64) if total_device_ptr is None else None
+        out = A.CookUsageOut(cap_rows=cap, bucket_usage_is_device=int(busage is None), total_is_device=int(total is None),
+                             bucket_off=_p(boff, C.c_uint32), bucket_group=_p(bgroup, C.c_uint32),
+                             bucket_usage=C.cast(C.c_void_p(int(usage_device_ptr)), A._f64p) if busage is None else _p(busage, C.c_double),
+                             row_off=_p(roff, C.c_uint32), rows=_p(rows, C.c_uint32),
+                             total=C.cast(C.c_void_p(int(total_device_ptr)), A._f64p) if total is None else _p(total, C.c_double))
+        # (an empty list of users still is a list: numpy's pointer to an empty array is not NULL)
+        up = ul.ctypes.data_as(C.c_void_p) if ul is not None else None
+        if multi:
+            rc = lib.cook_usage_breakdown_multi(arr, len(engines), maps, n_users, gs, int(n_groups), up, n_out if ul is not None else 0, C.byref(out))
+        else:
+            rc = lib.cook_usage_breakdown(engines[0]._h, gs[0], int(n_groups), up, n_out if ul is not None else 0, C.byref(out))
+        if rc != 0 and cap_rows is None and usage_device_ptr is None and out.n_rows > cap:
+            cap = out.n_rows
+            continue
+        _check_multi(engines, rc)
+        break
+    B, R = out.n_buckets, out.n_rows
+    return dict(bucket_off=boff, bucket_group=bgroup[:B], bucket_usage=busage[:B] if busage is not None else None, row_off=roff[:B + 1],
+                rows=rows[:R] if multi else rows[:R, 0], total=total[:n_out] if total is not None else None)
+
+
+def usage_breakdown_multi(engines: Sequence[Engine], n_users: int, groups: Optional[Sequence[Optional[np.ndarray]]] = None, n_groups: int = 0,
+                          user_maps: Optional[Sequence[Optional[np.ndarray]]] = None, users=None, usage_device_ptr: Optional[int] = None,
+                          total_device_ptr: Optional[int] = None, cap_rows: Optional[int] = None) -> dict:
+    """GET /usage without a pool, over the pools `engines` of one device (cook_usage_breakdown_multi): groups[i] is engine i's
+    group_of_row (None: ungrouped), the ids one id space over the engines; user_maps as in user_stats_multi.  The dict of
+    Engine.usage_breakdown, with rows [R, 2] = (engine index, task row)."""
+    gs = [None] * len(engines) if groups is None else [np.ascontiguousarray(g, dtype=np.uint32) if g is not None else None for g in groups]
+    assert len(gs) == len(engines)
+    for e, g in zip(engines, gs):
+        assert g is None or len(g) == getattr(e, "_tasks_n", len(g)), "group_of_row has one id per task row"
+    return _usage_call(list(engines), True, int(n_users), user_maps, gs, n_groups, users, usage_device_ptr, total_device_ptr, cap_rows)
 
 
 def cycle_run_rank_multi(engines: Sequence[Engine], num_considerable, user_usage_ptrs: Optional[Sequence[int]] = None,

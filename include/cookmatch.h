@@ -658,6 +658,63 @@ typedef struct cook_unsched_limits {
 int cook_unscheduled(cook_engine* e, const cook_unsched_limits* limits, const uint8_t* in_window, const uint32_t* rows, uint32_t n_rows,
                      uint32_t* reasons, uint32_t* queue_pos, double* total, int total_is_device, uint32_t* ahead, uint32_t* list_len);
 
+/* ---- USAGE: GET /usage with its job-group breakdown, from the last rank, on the device ---------------------------------------------
+ * rest/api.clj:2894-2969 (user-usage, usage, get-user-usage) loads every running job entity, groups by user, by pool and — with
+ * group_breakdown=true — by job group, and reduces each bucket with tools/total-resources-of-jobs (tools.clj:294-306: reduce from
+ * {:cpus 0.0 :mem 0.0 :gpus 0.0 :jobs n}, merge-with + of the jobs' resources) while collecting the bucket's job list.
+ *  - A JOB is a running row (pending == 0) of the engine's staged task table, as everywhere in the engine (one row per running job).
+ *    Pending rows take no part.
+ *  - group_of_row ([tasks.n] by task row): the host-interned id in [0, n_groups) of job-ent->group-uuid, COOK_NONE_U32 = nil; NULL =
+ *    every row ungrouped.  An input column like cook_unscheduled's in_window: the engine does not keep it.  Values of pending rows are
+ *    ignored.  A running row's value >= n_groups that is not COOK_NONE_U32: COOK_E_INVALID, nothing written.
+ *  - A BUCKET is (user, group or none).  bucket_usage[b] = {cpus, mem, gpus, jobs}: starting from 0.0, the bucket's rows added left to
+ *    right in the user's task order of the last rank (tools.clj:614-641); gpus is 0.0 where the gpus column is NULL; jobs = the number
+ *    of rows.  rows[row_off[b] .. row_off[b+1]) = the bucket's task rows in that order (:running-jobs; the host holds the UUIDs).
+ *  - total[u] (:total-usage, api.clj:2903-2905) = the same reduction over ALL running rows of the user in the user's task order.  It is
+ *    not the sum of the user's buckets: for fractional inputs the two differ in the last bits.
+ *  - Oracle-defined where the reference's order is a Clojure hash map's or a Datomic query's: users in user-id order (or the order of
+ *    `users`); the buckets of user k are bucket_off[k] .. bucket_off[k+1]: the ungrouped bucket FIRST (bucket_group = COOK_NONE_U32),
+ *    then the grouped ones in ascending group id.  Only non-empty buckets are stored: a user without an ungrouped job has no
+ *    COOK_NONE_U32 bucket, for which the reference answers zero usage and an empty list (:2913-2915); a user without running rows has
+ *    no bucket and a zero total (no-usage-map, :2917-2923).
+ *  - Every returned double is bit-identical to that sequential sum for any fp64 input (exactness tracked over every prefix of every
+ *    bucket and user; one with a rounded prefix, or a -0.0 among its values, is folded again left to right).
+ *  - users (optional; n_list user ids, any order, repeats allowed — the ?user= request): the same outputs for the listed users only, in
+ *    list order; n_out = n_list.  NULL: all users, n_out = the number of users.  A user id that is no user: COOK_E_INVALID.
+ * Outputs (cook_usage_out), each pointer optional and caller-allocated: bucket_off[n_out + 1], bucket_group[cap_rows],
+ * bucket_usage[cap_rows][4], row_off[cap_rows + 1], rows[cap_rows] (the multi form: [cap_rows][2] = {engine index, task row}),
+ * total[n_out][4]; n_buckets (B) and n_rows (R) are returned.  Every bucket holds a row, so B <= R.  Without `users` R is the number
+ * of running rows, which the caller knows; with `users` it is the listed users' rows, a repeated user counting again.  R > cap_rows:
+ * COOK_E_INVALID with n_buckets and n_rows filled in and nothing else written.  bucket_usage_is_device / total_is_device != 0: that
+ * pointer is a DEVICE pointer and nothing of it is copied to the host.
+ * The call reads the per-user order of the LAST rank run in place and writes only buffers of its own: a cycle fetched after it is the
+ * cycle fetched before it.  Before any cook_rank_run / cook_cycle_run*, and after a cook_rank_stage or cook_cycle_update that no rank
+ * has followed: COOK_E_STATE (the rule of cook_user_stats). */
+typedef struct cook_usage_out {
+  uint32_t cap_rows;              /* in: room of rows / bucket_group / bucket_usage (entries); row_off has one more                 */
+  uint32_t n_buckets;             /* out: B                                                                                          */
+  uint32_t n_rows;                /* out: R                                                                                          */
+  int32_t bucket_usage_is_device;
+  int32_t total_is_device;
+  uint32_t reserved;
+  uint32_t* bucket_off;
+  uint32_t* bucket_group;
+  double* bucket_usage;
+  uint32_t* row_off;
+  uint32_t* rows;
+  double* total;
+} cook_usage_out;
+int cook_usage_breakdown(cook_engine* e, const uint32_t* group_of_row, uint32_t n_groups, const uint32_t* users, uint32_t n_list,
+                         cook_usage_out* out);
+/* `usage` without a pool (api.clj:2930-2944: the user's jobs of every pool) for engines of ONE device.  group_of_row[i] (NULL, or
+ * group_of_row[i] NULL: engine i's rows are ungrouped) is engine i's column; group ids are ONE id space over the engines, so a group
+ * with jobs in two pools is one bucket.  user_map and n_users as in cook_user_stats_multi (same checks, same errors).  A bucket's and a
+ * user's rows are the concatenation over the engines in the order of `engines`, each engine's part in its own per-user order.  The
+ * :pools sub-map of the answer is cook_usage_breakdown of each engine. */
+int cook_usage_breakdown_multi(cook_engine** engines, uint32_t n, const uint32_t* const* user_map, uint32_t n_users,
+                               const uint32_t* const* group_of_row, uint32_t n_groups, const uint32_t* users, uint32_t n_list,
+                               cook_usage_out* out);
+
 /* ---- OFFERS: replaces the numeric core of kubernetes.compute-cluster/generate-offers ----------------------
  * (kubernetes/compute_cluster.clj:68-190: available = capacity - consumption per node, the schedulable filter, the
  * offer resources and the capacity / consumption totals it publishes; kubernetes/api.clj:747-765 convert-resource-map,
