@@ -14,6 +14,9 @@
 //                  all (level maxima over every chunk: placements only take room away) and writes the failure codes.
 // Steps that need every wave — several candidates inside the guard band (the literal fitness decides), the end of an epoch (the overlay's live lanes
 // go back into their classes' arrays), the end of a batch of 64 jobs — are COLLECTIVE turns behind a mode word and barriers.
+// A batch's end is three barriers: the one every wave leaves its loop for (the decider's books are written before it raises the mode word), one behind
+// the class waves' summaries, one behind the bookkeeper.  Batches whose walk mask is empty never reach the other waves: the bookkeeper settles a run of
+// them alone, inside its turn, and publishes where the walk goes on (CFX_NEXT_BASE).
 // Exactness of the failure codes (cook_match_explain reads them): the level maxima are exact at every batch boundary (the class waves apply the batch's
 // removals from the decider's log there); a job without a place has room somewhere at its turn iff it has at the batch's end, or had at its start and
 // some LATER placement of the batch found room for it in the offer it took (the log's old values).
@@ -52,8 +55,8 @@ constexpr unsigned CF_OVL = 58;     // overlay lanes (lanes 58..63 are the candi
 constexpr unsigned CF_EPOCH_AT = COOK_SHAPE(58, 8);  // live overlay lanes that end an epoch
 constexpr unsigned CFW_BOOKS = 4;   // the bookkeeper's wave
 enum : unsigned { CFM_EXACT = 1u, CFM_EPOCH = 2u, CFM_BATCH_END = 3u };
-enum : unsigned { CFX_SPARE0 = 0, CFX_SPARE1, CFX_LOGN, CFX_LOG_APPLIED, CFX_WALK_LO, CFX_WALK_HI, CFX_EX_LANE, CFX_FMAX_LO, CFX_FMAX_HI, CFX_EPOCH, CFX_MATCH_LO, CFX_MATCH_HI,
-                  CFX_B1_LO, CFX_B1_HI, CFX_OVN, CFX_MINFC, CFX_MINFM, CFX_N = 24 };  // words of CfLds::misc
+enum : unsigned { CFX_NEXT_BASE = 0, CFX_SPARE1, CFX_LOGN, CFX_LOG_APPLIED, CFX_WALK_LO, CFX_WALK_HI, CFX_EX_LANE, CFX_FMAX_LO, CFX_FMAX_HI, CFX_EPOCH, CFX_MATCH_LO, CFX_MATCH_HI,
+                  CFX_B1_LO, CFX_B1_HI, CFX_OVN, CFX_MINFC, CFX_MINFM, CFX_N = 24 };  // words of CfLds::misc (CFX_NEXT_BASE: the first job of the batch every wave goes on with)
 constexpr uint32_t CF_ENT_NONE = 0x80000000u, CF_ENT_AMB = 0x40000000u;  // CfEnt::cid: no candidate / another member or class may round to the same fitness
 
 struct __attribute__((aligned(8))) CfFree {  // free cpus / mem of a position (fixed point), one 8-byte LDS access
@@ -438,7 +441,7 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
            st_rewinds = 0;
   unsigned long long tk_epoch = 0, tk_books = 0, tk_walk = 0, tk_phase1 = 0;
 #ifdef CF_PROF
-  unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bnd0 = 0ull;
 #endif
   auto job_of = [&](unsigned s) -> CfJobU {
     CfJobU J;
@@ -471,7 +474,9 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
   // the bookkeeper reads the next batch's jobs (registers), settles who is walked; lane = batch slot
   CfJob nxt;
   nxt.c = nxt.m = nxt.meta = nxt.grp = nxt.eq[0] = nxt.eq[1] = nxt.nov[0] = nxt.nov[1] = 0u;
-  auto books_next = [&](unsigned nbase) {  // tables are exact: the walk mask and the "room at its start" of the batch at nbase, its jobs into the ring
+  constexpr unsigned CF_PRE = 3;  // batches the bookkeeper reads ahead of the one it settles (a run of batches nobody walks goes at the pace of these loads)
+  CfJob pre[CF_PRE];
+  auto books_next = [&](unsigned nbase) -> unsigned long long {  // tables are exact: the walk mask and the "room at its start" of the batch at nbase, its jobs into the ring
     const unsigned nn = nbase < K ? cf_min(64u, K - nbase) : 0u;
     const unsigned nslot = (nbase >> 6) & 1u;
     const bool in = lane < nn;
@@ -483,6 +488,14 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
     if (lane == 0)
       S.misc[CFX_WALK_LO] = (unsigned)wm, S.misc[CFX_WALK_HI] = (unsigned)(wm >> 32), S.misc[CFX_LOGN] = 0u, S.misc[CFX_LOG_APPLIED] = 0u,
       S.ctrl[1] = wm ? (unsigned)__ffsll(wm) - 1u : 0u;  // (the class waves run ahead of THIS step)
+    return wm;
+  };
+  // nxt holds the jobs of the batch at nbase and pre[i] those of the batches behind it: one batch on
+  auto books_advance = [&](unsigned nbase) {
+    nxt = pre[0];
+#pragma unroll
+    for (unsigned i = 0; i + 1u < CF_PRE; ++i) pre[i] = pre[i + 1u];
+    if (nbase + 64u * (CF_PRE + 1u) + lane < K) pre[CF_PRE - 1u] = b.jobs[nbase + 64u * (CF_PRE + 1u) + lane];
   };
   __syncthreads();  // (the tables of the prologue are written)
   if (is_books) {
@@ -490,6 +503,11 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
     books_next(0u);
     bk_room0 = nx_room0;
     if (64u + lane < K) nxt = b.jobs[64u + lane];
+#pragma unroll
+    for (unsigned i = 0; i < CF_PRE; ++i) {
+      pre[i] = nxt;
+      if (64u * (i + 2u) + lane < K) pre[i] = b.jobs[64u * (i + 2u) + lane];
+    }
   }
   if (is_decider) cook_set_prio_high();
   const unsigned long long t_loop = cook_ticks();
@@ -497,7 +515,7 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
   const bool isov = lane < CF_OVL;
   const unsigned clw = isov ? 0u : lane - CF_OVL + 1u;  // decider: the lane's column of the board
 
-  for (unsigned base = 0; base < K; base += 64u) {
+  for (unsigned base = 0; base < K;) {
     const unsigned bn = cf_min(64u, K - base);
     const unsigned slot = (base >> 6) & 1u;
     const unsigned long long walkmask = wave_uniform_u64((unsigned long long)S.misc[CFX_WALK_LO] | (unsigned long long)S.misc[CFX_WALK_HI] << 32);
@@ -515,8 +533,32 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
     unsigned cur_ord = 0;                // the walked ordinal (0, 1, ... over the batch's walked jobs) of the first job of todo
     unsigned ph = 0;                     // class waves: cur_ord modulo the waves that share the set's jobs (wave `rep` of `nrep` answers the ordinals = rep)
     bool batch_done = nw == 0u;
+    // the decider's books of the batch.  They are written BEFORE the decider raises CFM_BATCH_END: the barrier every wave leaves its loop for is the one
+    // that publishes them (nobody reads these words during a walk; the class waves and the bookkeeper read them behind that barrier)
+    auto decider_books = [&](unsigned n_placed) {
+      if (lane < bn) st.job_to_offer[base + lane] = res;
+      const unsigned long long mm = __ballot(res >= 0);
+      if (base == 0u) head = (unsigned)(mm & 1ull);
+      const bool live = isov && o.valid != 0u;
+      const unsigned nl = live ? cf_level_of(t, o.fc) : 0u;
+#define CF_OV_T(i) unsigned v##i = nl > (unsigned)i ? o.fm + 1u : 0u;
+      CF_FOR8(CF_OV_T)
+#undef CF_OV_T
+      wave_max8_u32(v0, v1, v2, v3, v4, v5, v6, v7);
+      if (lane == 0) {
+        S.misc[CFX_MATCH_LO] = (unsigned)mm, S.misc[CFX_MATCH_HI] = (unsigned)(mm >> 32), S.misc[CFX_B1_LO] = (unsigned)b1m, S.misc[CFX_B1_HI] = (unsigned)(b1m >> 32);
+        S.misc[CFX_LOGN] = n_placed, S.misc[CFX_MINFC] = minfc_all, S.misc[CFX_MINFM] = minfm_all;
+#define CF_OV_S(i) S.ovt[i] = v##i;
+        CF_FOR8(CF_OV_S)
+#undef CF_OV_S
+      }
+    };
     const unsigned long long tw0 = CF_TICKS();
     CF_PROF_T(cw0);
+#ifdef CF_PROF  // the decider's ticks from raising CFM_BATCH_END to the next batch that has steps; class wave 1 counts the batches without a walked job (x16: the words are stored >> 4)
+    if (is_decider && nw != 0u && bnd0 != 0ull) prof[6] += cw0 - bnd0, bnd0 = 0ull;
+    if (is_class_wave && nw == 0u) prof[6] += 16ull;
+#endif
     while (!batch_done) {
       unsigned md = 0;  // the collective turn this wave leaves its loop for
       if (is_decider) {
@@ -579,6 +621,10 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
           }
 #endif
           if (todo == 0ull) {
+#ifdef CF_PROF
+            bnd0 = __builtin_readcyclecounter();
+#endif
+            decider_books(logn);
             md = CFM_BATCH_END;
             st_lane0_b32(&S.ctrl[0], md);
             break;
@@ -894,6 +940,14 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
       WAIT_LDS();  // (stores issued by inline asm — st_lane0 / st_mask, the plain step — have landed before the barrier lets the other waves read)
       __syncthreads();
       md = wave_uniform_u32(md);  // (every wave left its loop with the mode word the decider raised)
+      if (md == CFM_BATCH_END) {
+        // the end of the batch is no turn of its own: the decider's books are behind the barrier above, and the mode word is not read again before
+        // the barrier that ends the batch (every wave has left its loop), so it is cleared here and the class waves go straight to their summaries
+        batch_done = true;
+        if (tid == 0) st_wg(&S.ctrl[0], 0u);
+        if (is_class_wave) seen = cf_poll(&S.ctrl[1u + lw]);
+        break;
+      }
       bool epoch = md == CFM_EPOCH;
       const unsigned s = wave_uniform_u32(S.misc[CFX_EX_LANE]);
       if (md == CFM_EXACT) {
@@ -1095,8 +1149,7 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
         if (tid == 0) S.misc[CFX_LOG_APPLIED] = S.misc[CFX_LOGN];
         tk_epoch += CF_TICKS() - te;
       }
-      if (md == CFM_BATCH_END) batch_done = true;
-      if (md != CFM_BATCH_END) {  // every answer on the board is void: a new generation; the class waves go on behind the step of the turn
+      {  // every answer on the board is void: a new generation; the class waves go on behind the step of the turn
         ++gen;
         if (is_class_wave) {
           todo = walkmask & ~cf_below(s) & ~(1ull << s), cur_ord = (unsigned)__popcll(walkmask & cf_below(s)) + 1u;
@@ -1112,29 +1165,10 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
     tk_walk += CF_TICKS() - tw0;
     CF_PROF_T(cw1);
     CF_PROF_ADD(7, cw1 - cw0);
-    // ---- batch end, phase 1: the decider's books of the batch, the class waves make their summaries exact
+    // ---- batch end, phase 1: the class waves make their summaries exact (the decider's books are published: the barrier of the walk's last turn)
     const unsigned long long tp0 = CF_TICKS();
-    if (is_decider) {
-      if (lane < bn) st.job_to_offer[base + lane] = res;
-      const unsigned long long mm = __ballot(res >= 0);
-      if (base == 0u) head = (unsigned)(mm & 1ull);
-      const bool live = isov && o.valid != 0u;
-      const unsigned nl = live ? cf_level_of(t, o.fc) : 0u;
-#define CF_OV_T(i) unsigned v##i = nl > (unsigned)i ? o.fm + 1u : 0u;
-      CF_FOR8(CF_OV_T)
-#undef CF_OV_T
-      wave_max8_u32(v0, v1, v2, v3, v4, v5, v6, v7);
-      if (lane == 0) {
-        S.misc[CFX_MATCH_LO] = (unsigned)mm, S.misc[CFX_MATCH_HI] = (unsigned)(mm >> 32), S.misc[CFX_B1_LO] = (unsigned)b1m, S.misc[CFX_B1_HI] = (unsigned)(b1m >> 32);
-        S.misc[CFX_LOGN] = logn, S.misc[CFX_MINFC] = minfc_all, S.misc[CFX_MINFM] = minfm_all;
-#define CF_OV_S(i) S.ovt[i] = v##i;
-        CF_FOR8(CF_OV_S)
-#undef CF_OV_S
-      }
-    }
+    if (is_decider && nw == 0u) decider_books(0u);  // (a batch nobody walks raises no turn)
     if (nw != 0u) {
-      EMU_SITE("classfit: phase 1");
-      __syncthreads();
       if (is_class_wave) {  // the batch's removals from this wave's chunks: summaries a member that left was the maximum of are recomputed
         const unsigned n_log = wave_uniform_u32(S.misc[CFX_LOGN]), a0 = wave_uniform_u32(S.misc[CFX_LOG_APPLIED]);
         const bool mine_e = lane >= a0 && lane < n_log && ((S.log[lane].info >> 8) & 15u) == lw;
@@ -1189,13 +1223,38 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
         }
         st.fail_code[base + lane] = fail;
       }
-      books_next(base + 64u);
+      // The next batch — and every batch behind it whose walk mask is empty, which is the bookkeeper's alone: no job of it is walked, so no wave
+      // places anything, the level tables, the overlay and the decider's minima stay what they are now, and the batch's books follow from them:
+      // nobody is matched; "an offer lacks room" is the decider's own ballot of an untouched batch (jc > minfc_all || jm > minfm_all, the minima it
+      // published for the batch just ended); "some offer has room at the job's turn" is nx_room0 (no placement in between: no flip).  The other
+      // waves go on at the first batch with a walked job (or K); the ring's slot follows that base's parity, whatever was skipped.
+      unsigned nb = base + 64u;
+      unsigned long long nwm = books_next(nb);
+      const unsigned minfc_pub = wave_uniform_u32(S.misc[CFX_MINFC]), minfm_pub = wave_uniform_u32(S.misc[CFX_MINFM]);
+      while (nb < K && nwm == 0ull) {
+        if (nb + lane < K) {
+          st.job_to_offer[nb + lane] = -1;
+          if (st.fail_code) {
+            const unsigned fail = ((nxt.c > minfc_pub || nxt.m > minfm_pub) ? 1u : 0u) | (nx_room0 ? 2u : 0u);
+            st.fail_code[nb + lane] = fail != 0u ? fail : 8u;
+          }
+        }
+        books_advance(nb);
+        nb += 64u;
+        nwm = books_next(nb);
+      }
+      if (lane == 0) S.misc[CFX_NEXT_BASE] = nb;
       bk_room0 = nx_room0;
-      if (base + 128u + lane < K) nxt = b.jobs[base + 128u + lane];
+      books_advance(nb);
       tk_books += CF_TICKS() - tb0;
     }
     EMU_SITE("classfit: batch end");
     __syncthreads();
+    const unsigned nbase = wave_uniform_u32(S.misc[CFX_NEXT_BASE]);
+#ifdef CF_PROF
+    if (is_class_wave) prof[6] += 16ull * ((nbase - base) / 64u - 1u);  // (the batches the bookkeeper settled alone)
+#endif
+    base = nbase;
   }
   if (is_decider) {
     if (lane == 0) {
@@ -1233,6 +1292,7 @@ static __device__ __forceinline__ void cf_walk_pool(char* lds, const MatchIn* __
   const bool any_eq = ctl->any_eq != 0u, any_group = ctl->any_group != 0u;
   // ---- group table sizes (needed for the layout): entries per unique group = running cotasks on hosts of this call + pending members
   __shared__ unsigned s_total, s_wsum[CF_WAVES];
+  static_assert(CF_MAXG % CF_THREADS == 0, "the groups are dealt out GPT to a thread: a workgroup size that does not divide CF_MAXG would leave some without one");
   constexpr unsigned GPT = CF_MAXG / CF_THREADS;
   unsigned gsz[GPT];
   unsigned gsum = 0;
