@@ -375,6 +375,28 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunRankMulti(JNIEnv* env, jclas
   }
   return cook_cycle_run_rank_multi(es, (uint32_t)n, ks, 0, 0);
 }
+/* a match cycle on the standing ranked queue, without a re-rank (cook_cycle_run_queue; defer != 0: cook_cycle_run_queue_rank, the placement
+ * then runs in cycleMatchMulti).  offer_skipped: n_last_offers bytes (the offers of the LAST cycle; the buffer is checked against that
+ * length here, and the library refuses a count other than the last cycle's offer count) or null; offers == null: the staged
+ * offers stay; groups == null: the kept matches' cotasks are folded into their groups on the device, else the table replaces the groups'
+ * running cotasks.  The multi form of the C ABI (cook_cycle_run_queue_multi) takes one step per pool: a binding that wants it calls this
+ * with defer for every pool of the device from one thread and then cycleMatchMulti. */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueue(JNIEnv* env, jclass c, jlong h, jint num_considerable, jint remove_mode,
+                                                          jint n_last_offers, jobject offer_skipped, jint m, jobject offer_dims,
+                                                          jobjectArray offers, jint n_groups, jobjectArray groups, jint defer) {
+  int bad = 0;
+  cook_offers o = offers_of(env, m, dims_of(env, offer_dims, &bad), offers, &bad);
+  cook_groups g = groups_of(env, n_groups, groups, &bad);
+  cook_queue_step s;
+  (void)c;
+  s.offer_skipped = BUFN(const uint8_t, offer_skipped, n_last_offers > 0 ? n_last_offers : 0);
+  s.remove_mode = (uint32_t)remove_mode;
+  s.n_offer_skipped = (uint32_t)(n_last_offers > 0 ? n_last_offers : 0); /* the library refuses a count other than the last cycle's offers */
+  s.offers = offers ? &o : 0;
+  s.groups = groups ? &g : 0;
+  if (bad) return COOK_E_INVALID;
+  return defer ? cook_cycle_run_queue_rank(H(h), &s, (uint32_t)num_considerable) : cook_cycle_run_queue(H(h), &s, (uint32_t)num_considerable);
+}
 /* the running usage of n staged engines of one device in ONE call (cook_rank_pool_usage_multi): usage_out = direct buffer of n cook_usage */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_rankPoolUsageMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n, jobject usage_out) {
   cook_engine* es[64];

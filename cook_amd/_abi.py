@@ -125,6 +125,11 @@ class CookGroups(C.Structure):
     ]
 
 
+class CookQueueStep(C.Structure):  # cook_cycle_run_queue*
+    _fields_ = [("offer_skipped", _u8p), ("remove_mode", C.c_uint32), ("n_offer_skipped", C.c_uint32), ("offers", C.POINTER(CookOffers)),
+                ("groups", C.POINTER(CookGroups))]
+
+
 class CookRebalanceParams(C.Structure):
     _fields_ = [("safe_dru_threshold", C.c_double), ("min_dru_diff", C.c_double),
                 ("max_preemption", C.c_int32), ("reserved", C.c_int32)]

@@ -135,6 +135,7 @@ struct AutoscaleBufs;  // autoscale_host.hpp
 struct SweepBufs;      // sweep_host.hpp
 struct UnschedBufs;    // unscheduled_host.hpp
 struct UsageBufs;      // usage_host.hpp
+struct QueueBufs;      // queue_host.hpp
 
 }  // namespace
 
@@ -253,6 +254,18 @@ struct cook_engine {
   // the last cycle ran the considerable filters under a staged user state, and nothing has replaced that state, the rank or the match
   // since (cook_cycle_autoscale reads all three)
   bool cycle_cons_ran = false;
+  // ---- the standing queue of the queue cycles (queue_host.hpp): `ranked` is the queue a match cycle may consume — the last cycle took its
+  // jobs from it and nothing has shifted or dropped the rows it points at since (with rank_done and match_done: that cycle is complete)
+  bool q_valid = false;
+  const uint32_t* q_last_pos = nullptr;  // device: rank positions of the last cycle's considered jobs; null: 0 .. cycle_considered - 1
+  bool q_groups_own = false;             // min.g_run_* point at a queue cycle's table; the staged one is q_sg_*
+  const uint32_t *q_sg_off = nullptr, *q_sg_host = nullptr, *q_sg_attr = nullptr;
+  uint32_t q_sg_total = 0;
+  uint32_t q_advance_us = 0;             // host microseconds in the last queue cycle's advance, its synchronisation included (stats [31])
+  std::vector<uint8_t> h_g_type;         // the staged groups' type / attr_key / minimum (a queue step's table must agree)
+  std::vector<uint32_t> h_g_key;
+  std::vector<int32_t> h_g_min;
+  QueueBufs* qb = nullptr;               // (allocated on first use)
 
   // ---- rebalancer state (allocated on first use) ----
   RebalBufs* rb = nullptr;
@@ -881,6 +894,7 @@ void rank_run(cook_engine* e) {
   e->n_ranked = 0;
   e->rank_done = false;
   e->cycle_cons_ran = false;
+  e->q_valid = false;  // (the standing queue is rewritten)
   e->ranked.ensure(std::max(1u, e->n_pending));
   if (N == 0) {
     e->rank_done = true;
@@ -1234,6 +1248,10 @@ void match_stage_inputs(cook_engine* e, const cook_jobs* j, const cook_offers* o
   in.G = G;
   e->Kjobs = K;
   e->cf_group_run_total = 0;
+  e->q_valid = false, e->q_groups_own = false;
+  e->h_g_type.clear(), e->h_g_key.clear(), e->h_g_min.clear();
+  if (G && g->type && g->attr_key && g->minimum)
+    e->h_g_type.assign(g->type, g->type + G), e->h_g_key.assign(g->attr_key, g->attr_key + G), e->h_g_min.assign(g->minimum, g->minimum + G);
   in.j_cpus = h2d_opt(e, e->j_cpus, j->cpus, K);
   in.j_mem = h2d_opt(e, e->j_mem, j->mem, K);
   in.j_gpus = h2d_opt(e, e->j_gpus, j->gpus, K);
@@ -2067,6 +2085,7 @@ struct StageTimer {
 #include "cycle_update.hpp"
 #include "user_stats_host.hpp"
 #include "autoscale_host.hpp"
+#include "queue_host.hpp"
 #include "sweep_host.hpp"
 #include "unscheduled_host.hpp"
 #include "usage_host.hpp"
@@ -2220,6 +2239,8 @@ void cook_engine_destroy(cook_engine* e) {
   e->unb = nullptr;
   delete e->ugb;
   e->ugb = nullptr;
+  delete e->qb;
+  e->qb = nullptr;
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -2338,6 +2359,10 @@ int cook_cycle_stage_built_offers(cook_engine* e, const cook_tasks* tasks, const
 int cook_match_run(cook_engine* e) {
   return guarded(e, [&] {
     if (!e->match_staged) e->fail(COOK_E_STATE, "cook_match_run before cook_match_stage");
+    // the match of the STAGED jobs replaces the last cycle's job_to_offer and considered count: neither a queue cycle's advance nor
+    // cook_cycle_autoscale may read them as that cycle's
+    e->q_valid = false;
+    e->cycle_cons_ran = false;
     StageTimer t(e, 2, &e->match_ms);
     match_run_device(e, e->K, nullptr);
     t.stop();
@@ -2377,16 +2402,9 @@ int cook_cycle_stage(cook_engine* e, const cook_tasks* tasks, const cook_users* 
     if (e->ub) e->ub->csr_known = false;  // (cycle_update.hpp: the staged CSR columns' sizes are looked up again)
   });
 }
-// rank -> (considerable filters) -> take K -> the job index array of the match; returns K
-static unsigned cycle_rank_part(cook_engine* e, uint32_t num_considerable) {
-  if (!e->cycle_staged) e->fail(COOK_E_STATE, "cook_cycle_run before cook_cycle_stage");
-  if (recording()) {  // (a pool batch times its joint sequence of launches itself)
-    rank_run(e);
-  } else {
-    StageTimer tr(e, 0, &e->rank_ms);
-    rank_run(e);
-    tr.stop();
-  }
+// (considerable filters) -> take K over the standing queue -> the job index array of the match; returns K
+static unsigned cycle_take_part(cook_engine* e, uint32_t num_considerable) {
+  e->q_last_pos = nullptr;
   unsigned K = std::min<unsigned>(num_considerable, e->n_ranked);  // (take num-considerable), scheduler.clj:751
   if (e->cb && e->cb->cycle_on) {  // pending-jobs->considerable-jobs between rank and match (scheduler.clj:729-762)
     ConsBufs& c = *e->cb;
@@ -2401,6 +2419,7 @@ static unsigned cycle_rank_part(cook_engine* e, uint32_t num_considerable) {
     cons_run_device(e, c, c, n, c.q_cpus.ptr(), c.q_mem.ptr(), c.q_gpus.ptr(), c.q_user.ptr(), c.q_elig.ptr(), num_considerable);
     K = c.n_result;
     e->cycle_cons_ran = true;
+    e->q_last_pos = c.result;
     e->j_index.ensure(K);
     if (K)
       KM<cons_job_index, 256>(e, "cons_job_index", div_up(K, 256), (const uint32_t*)c.result, (const uint32_t*)e->ranked.ptr(),
@@ -2410,6 +2429,32 @@ static unsigned cycle_rank_part(cook_engine* e, uint32_t num_considerable) {
     if (K)
       KM<cycle_job_index, 256>(e, "cycle_job_index", div_up(K, 256), (const uint32_t*)e->ranked.ptr(), (const uint32_t*)e->pend_ord.ptr(), K, e->j_index.ptr());
   }
+  e->q_valid = true;
+  return K;
+}
+// rank -> cycle_take_part.  Any rank resets the standing queue to the fresh order and the groups' cotasks to the staged table
+static unsigned cycle_rank_part(cook_engine* e, uint32_t num_considerable) {
+  if (!e->cycle_staged) e->fail(COOK_E_STATE, "cook_cycle_run before cook_cycle_stage");
+  queue_reset_groups(e);
+  if (recording()) {  // (a pool batch times its joint sequence of launches itself)
+    rank_run(e);
+  } else {
+    StageTimer tr(e, 0, &e->rank_ms);
+    rank_run(e);
+    tr.stop();
+  }
+  return cycle_take_part(e, num_considerable);
+}
+// a queue cycle's part in front of the placement: advance -> cycle_take_part, no rank
+static unsigned cycle_queue_part(cook_engine* e, const cook_queue_step* step, uint32_t num_considerable) {
+  if (recording()) {
+    queue_advance(e, step);
+    return cycle_take_part(e, num_considerable);
+  }
+  StageTimer tr(e, 0, &e->rank_ms);
+  queue_advance(e, step);
+  const unsigned K = cycle_take_part(e, num_considerable);
+  tr.stop();
   return K;
 }
 int cook_cycle_update(cook_engine* e, const cook_cycle_delta* delta) {
@@ -2455,21 +2500,24 @@ int cook_cycle_run_rank(cook_engine* e, uint32_t num_considerable) {
 }
 // the rank part of a cycle for every pool of a GPU: one flow per pool in a pool batch (above)
 static const bool g_rank_batch = env_switch_on_unless_zero("COOK_RANK_BATCH");
-int cook_cycle_run_rank_multi(cook_engine** engines, uint32_t n, const uint32_t* num_considerable, double* const* user_usage, int usage_is_device) {
-  if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
-  for (uint32_t i = 0; i < n; ++i)
-    if (!engines[i] || (user_usage && !user_usage[i])) return COOK_E_INVALID;
-  for (uint32_t i = 0; i < n; ++i)  // (an engine twice: two flows would record launches against one engine's buffers)
-    for (uint32_t k = 0; k < i; ++k)
+// The pools of a GPU through one call: `one(i)` is the call for engine i alone (the fall-back: one engine, COOK_RANK_BATCH=0, engines of
+// several devices, COOK_SYNC_TRACE, a call from inside a flow), `body(i)` what engine i's flow does inside the pool batch.  Returns the
+// first engine's error that is not COOK_OK; every engine whose flow failed keeps its own message.
+extern "C++" {
+template <class One, class Body>
+static int run_pools_batched(cook_engine** engines, uint32_t n, One&& one, Body&& body) {
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!engines[i]) return COOK_E_INVALID;
+    for (uint32_t k = 0; k < i; ++k)  // (an engine twice: two flows would record launches against one engine's buffers)
       if (engines[i] == engines[k]) return COOK_E_INVALID;
+  }
   cook_engine* lead = engines[0];
   bool same_device = true;
   for (uint32_t i = 1; i < n; ++i) same_device = same_device && engines[i]->device == lead->device;
   if (n == 1 || !g_rank_batch || !same_device || g_sync_trace || tl_flow) {
     int first = COOK_OK;
     for (uint32_t i = 0; i < n; ++i) {
-      int rc = cook_cycle_run_rank(engines[i], num_considerable[i]);
-      if (rc == COOK_OK && user_usage) rc = cook_rank_user_usage(engines[i], user_usage[i], usage_is_device);
+      const int rc = one(i);
       if (rc != COOK_OK && first == COOK_OK) first = rc;
     }
     return first;
@@ -2483,15 +2531,8 @@ int cook_cycle_run_rank_multi(cook_engine** engines, uint32_t n, const uint32_t*
     b.stream = lead->stream;
     b.flows.resize(n);
     for (uint32_t i = 0; i < n; ++i) {
-      cook_engine* e = engines[i];
-      double* uu = user_usage ? user_usage[i] : nullptr;
-      const uint32_t nc = num_considerable[i];
-      b.flows[i].e = e;
-      b.flows[i].body = [e, nc, uu, usage_is_device] {
-        const unsigned K = cycle_rank_part(e, nc);
-        if (uu) rank_user_usage(e, uu, usage_is_device != 0);
-        match_run_device(e, K, K ? e->j_index.ptr() : nullptr, /*defer=*/true);
-      };
+      b.flows[i].e = engines[i];
+      b.flows[i].body = [&body, i] { body(i); };
     }
     StageTimer tr(lead, 0, &lead->rank_ms);
     flows_rc = batch_run(b);
@@ -2506,6 +2547,53 @@ int cook_cycle_run_rank_multi(cook_engine** engines, uint32_t n, const uint32_t*
   for (uint32_t i = 0; i < n; ++i)
     if (flow_err[i].first != COOK_OK) engines[i]->err = flow_err[i].second;  // every engine whose flow failed keeps its own message
   return rc != COOK_OK ? rc : flows_rc;
+}
+}  // extern "C++"
+int cook_cycle_run_rank_multi(cook_engine** engines, uint32_t n, const uint32_t* num_considerable, double* const* user_usage, int usage_is_device) {
+  if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i)
+    if (user_usage && !user_usage[i]) return COOK_E_INVALID;
+  return run_pools_batched(
+      engines, n,
+      [&](uint32_t i) {
+        int rc = cook_cycle_run_rank(engines[i], num_considerable[i]);
+        if (rc == COOK_OK && user_usage) rc = cook_rank_user_usage(engines[i], user_usage[i], usage_is_device);
+        return rc;
+      },
+      [&](uint32_t i) {
+        cook_engine* e = engines[i];
+        const unsigned K = cycle_rank_part(e, num_considerable[i]);
+        if (user_usage) rank_user_usage(e, user_usage[i], usage_is_device != 0);
+        match_run_device(e, K, K ? e->j_index.ptr() : nullptr, /*defer=*/true);
+      });
+}
+// ---- queue cycles: match cycles on the standing ranked queue, without a re-rank (cookmatch.h) -----------------------------------
+int cook_cycle_run_queue(cook_engine* e, const cook_queue_step* step, uint32_t num_considerable) {
+  return guarded(e, [&] {
+    const unsigned K = cycle_queue_part(e, step, num_considerable);
+    StageTimer tm(e, 2, &e->match_ms);
+    match_run_device(e, K, K ? e->j_index.ptr() : nullptr);
+    tm.stop();
+    prof_collect(e);
+  });
+}
+int cook_cycle_run_queue_rank(cook_engine* e, const cook_queue_step* step, uint32_t num_considerable) {
+  return guarded(e, [&] {
+    const unsigned K = cycle_queue_part(e, step, num_considerable);
+    match_run_device(e, K, K ? e->j_index.ptr() : nullptr, /*defer=*/true);  // set up; the rounds run in cook_cycle_match_multi
+    prof_collect(e);
+  });
+}
+// ... for every pool of a GPU: one flow per pool in a pool batch, as cook_cycle_run_rank_multi
+int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const uint32_t* num_considerable) {
+  if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
+  return run_pools_batched(
+      engines, n, [&](uint32_t i) { return cook_cycle_run_queue_rank(engines[i], steps ? steps[i] : nullptr, num_considerable[i]); },
+      [&](uint32_t i) {
+        cook_engine* e = engines[i];
+        const unsigned K = cycle_queue_part(e, steps ? steps[i] : nullptr, num_considerable[i]);
+        match_run_device(e, K, K ? e->j_index.ptr() : nullptr, /*defer=*/true);
+      });
 }
 int cook_rank_pool_usage_multi(cook_engine** engines, uint32_t n, cook_usage* out) {
   if (!engines || n == 0 || !out) return COOK_E_INVALID;
@@ -2637,6 +2725,7 @@ int cook_considerable(cook_engine* e, const cook_queue* q, const cook_user_state
     if (n && (!q->cpus || !q->mem || !q->user)) e->fail(COOK_E_INVALID, "cook_considerable: the queue needs cpus, mem, user");
     ConsBufs& c = cons_bufs(e);
     e->cycle_cons_ran = false;  // (the cycle's user state and considerable result are replaced)
+    e->q_valid = false;
     cons_stage_users(e, c, us);
     for (unsigned i = 0; i < n; ++i)
       if (q->user[i] >= c.U) e->fail(COOK_E_INVALID, "cook_considerable: user id out of range");
@@ -2839,6 +2928,7 @@ int cook_match_stats_ex(cook_engine* e, uint32_t* out, uint32_t cap) {
   for (unsigned k = 0; k < 8u; ++k)
     if (e->upd_phase_us[k] > v[30]) v[29] = k, v[30] = e->upd_phase_us[k];
   for (unsigned k = 0; k < 5u; ++k) v[32 + k] = e->batch_stats[k];
+  v[31] = e->q_advance_us;
   v[37] = e->last_form, v[38] = e->cf_inelig;
   if (e->last_form == 3u)
     for (unsigned k = 0; k < 24u; ++k) v[40 + k] = e->cf_stats[k];

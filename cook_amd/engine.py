@@ -277,6 +277,30 @@ class Engine:
         """The rank / considerable / take-K part of cycle_run; the placement then runs in cycle_match_multi()."""
         self._chk(self._lib.cook_cycle_run_rank(self._h, int(num_considerable)))
 
+    def _queue_step(self, offer_skipped=None, remove_mode: int = 0, offers: Optional[A.Offers] = None, groups: Optional[A.Groups] = None):
+        """-> (CookQueueStep, the objects its pointers refer to).  offer_skipped has one entry per offer of the LAST cycle: the library
+        refuses another length (COOK_E_INVALID, nothing changed)."""
+        sk = np.ascontiguousarray(offer_skipped if offer_skipped is not None else [0], dtype=np.uint8)
+        os_ = offers.as_struct() if offers is not None else None
+        gs = groups.as_struct() if groups is not None else None
+        st = A.CookQueueStep(_p(sk, C.c_uint8) if offer_skipped is not None else None, int(remove_mode), len(sk) if offer_skipped is not None else 0,
+                             C.pointer(os_) if os_ is not None else None, C.pointer(gs) if gs is not None else None)
+        return st, (sk, os_, gs, offers, groups)
+
+    def cycle_run_queue(self, num_considerable: int, offer_skipped=None, remove_mode: int = 0, offers: Optional[A.Offers] = None,
+                        groups: Optional[A.Groups] = None, defer: bool = False):
+        """A match cycle on the standing ranked queue, without a re-rank (cook_cycle_run_queue): the last cycle's kept matches
+        (remove_mode 1: every considered job) leave the queue, their cotasks join their groups on the device (or `groups` replaces the
+        table), `offers` replaces the staged offers, then considerable -> take K -> match.  defer: set the placement up only
+        (cook_cycle_run_queue_rank); it runs in cycle_match_multi()."""
+        st, keep = self._queue_step(offer_skipped, remove_mode, offers, groups)
+        fn = self._lib.cook_cycle_run_queue_rank if defer else self._lib.cook_cycle_run_queue
+        self._chk(fn(self._h, C.byref(st), int(num_considerable)))
+        del keep
+
+    def cycle_run_queue_rank(self, num_considerable: int, **step):
+        self.cycle_run_queue(num_considerable, defer=True, **step)
+
     def cycle_fetch(self, out=None):
         """-> (ranked task indices, job_to_offer by rank position, head matched).  `out` = (u32 buffer, i32 buffer) to fetch into
         (e.g. page-locked arrays of a PinnedArena, each with room for every pending task): views of them are returned."""
@@ -536,7 +560,7 @@ class Engine:
         n = self._lib.cook_match_stats_ex(self._h, out, 64)
         keys = ("rounds", "matched", "stop_list", "stop_full", "stop_group", "stop_window", "segments", "resolved", "setup_us", "seq_us", "touched", "visited",
                 "_12", "_13", "_14", "_15", "trunc_lists", "served_mode", "served_pools", "serve_iterations", "serve_empty_iterations",
-                "serve_pool_windows", "serve_latch_wait_us", "served_fell_back", "serve_streams", "guard_hits", "update_us", "update_sync_us", "update_allocs", "update_slowest_phase", "update_slowest_phase_us", "_31",
+                "serve_pool_windows", "serve_latch_wait_us", "served_fell_back", "serve_streams", "guard_hits", "update_us", "update_sync_us", "update_allocs", "update_slowest_phase", "update_slowest_phase_us", "queue_advance_us",
                 "rank_batch_pools", "rank_batch_launches", "rank_batch_grouped_launches", "rank_batch_single_ops", "rank_batch_syncs",
                 "placement_form", "classfit_refused", "_39", "cf_walked", "cf_matched", "cf_overlay_wins", "cf_opened", "cf_opened_full", "cf_gpu_places", "cf_epochs",
                 "cf_scans", "cf_exact_turns", "cf_retightened", "_50", "cf_batches", "cf_dead_lanes", "cf_ticks", "cf_ticks_prologue", "cf_ticks_epochs", "cf_ticks_books",
@@ -745,6 +769,28 @@ def cycle_run_rank_multi(engines: Sequence[Engine], num_considerable, user_usage
                 e._chk(rc)
         engines[0]._chk(rc)
     return [o[:n_users] for o in outs] if outs is not None else None
+
+
+def cycle_run_queue_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None):
+    """cycle_run_queue_rank of several engines (pools of one device) in ONE call (cook_cycle_run_queue_multi); cycle_match_multi places
+    them.  steps: per engine None or the keywords of Engine.cycle_run_queue (offer_skipped, remove_mode, offers, groups)."""
+    if not engines:
+        return
+    n = len(engines)
+    arr = (C.c_void_p * n)(*[e._h for e in engines])
+    ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
+    assert len(ks) == n
+    ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
+    steps = list(steps) if steps is not None else [None] * n
+    assert len(steps) == n
+    built = [e._queue_step(**(s or {})) for e, s in zip(engines, steps)]
+    ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
+    rc = engines[0]._lib.cook_cycle_run_queue_multi(arr, n, ptrs, ks)
+    if rc != 0:
+        for e in engines:
+            if e._lib.cook_last_error(e._h):
+                e._chk(rc)
+        engines[0]._chk(rc)
 
 
 def cycle_match_multi(engines: Sequence[Engine]):

@@ -321,7 +321,7 @@ int cook_cycle_fetch_considerable(cook_engine* e, uint32_t* rank_pos, uint32_t* 
  * task_idx receives Out as task indices (cook_cycle_fetch's ranked_pending_idx space); cap >= max(max_jobs, k) always suffices, |Out| > cap:
  * COOK_E_INVALID (info says |Out|).  An in-range excluded task that is no candidate is ignored; one out of range, a non-finite
  * scale_factor or max_jobs > INT32_MAX: COOK_E_INVALID.  Before any cycle, after a stage / cook_cycle_update / cook_considerable /
- * cook_cycle_set_considerable that no cycle has followed, and after a cycle without a staged user state: COOK_E_STATE.  Changes no rank,
+ * cook_cycle_set_considerable / cook_match_run that no cycle has followed, and after a cycle without a staged user state: COOK_E_STATE.  Changes no rank,
  * considerable or match state. */
 typedef struct cook_autoscale_params {
   uint32_t max_jobs;              /* :max-jobs-for-autoscaling (<= INT32_MAX)                                            */
@@ -460,6 +460,55 @@ int cook_cycle_run_rank_multi(cook_engine** engines, uint32_t n, const uint32_t*
 int cook_cycle_match_multi(cook_engine** engines, uint32_t n);
 int cook_cycle_fetch(cook_engine* e, uint32_t* ranked_pending_idx, uint32_t* n_ranked, int32_t* job_to_offer,
                      uint32_t* n_considered, uint8_t* head_matched);
+
+/* ---- QUEUE CYCLES: match cycles on the standing ranked queue, without a re-rank ------------------------------------------------
+ * The reference runs on two clocks: rank-jobs (scheduler.clj:2262-2296) writes pool-name->pending-jobs-atom every few seconds;
+ * handle-resource-offers! (:1339-1520) runs far more often, does NOT rank, reads the atom (:1360), matches its considerable jobs and
+ * takes the matched jobs out of it (remove-matched-jobs-from-pending-jobs, :790-795, at :1506-1508; the Kubernetes pool handler removes
+ * every considered job, :1792-1794).  After a rank (cook_cycle_run, cook_cycle_run_rank*, + cook_cycle_match_multi) the engine holds
+ * the STANDING QUEUE Q = the rank's output order.  A queue cycle does, in this order, with no rank and no host round trip of per-job data:
+ *  1. Advance.  From the pool's last cycle (rank cycle or queue cycle): the considered rank positions, their job_to_offer and
+ *     offer_skipped (1 = filter-matches-for-ratelimit, :887-924, dropped every match of that offer's compute cluster; indexed by the
+ *     offers of THAT cycle, as in cook_autoscale_params).  remove_mode 0 removes from Q the jobs with a KEPT match, remove_mode 1 every
+ *     considered job.  The survivors keep their order.
+ *  2. Groups.  groups non-NULL: the groups' running-cotask table is replaced by it (layout of cook_groups; n, type, attr_key, minimum
+ *     must equal the staged ones).  NULL: every job of step 1 WITH A KEPT MATCH and a group g becomes a running cotask of g on the host
+ *     of its offer (run_host = the offer's host, run_attr = that offer's value of attr_key[g], 0 = absent), appended on the device:
+ *     what the reference sees once the launched instances are in the DB (constraints.clj:553-566).  The order inside a group's list
+ *     is not defined (unique, balanced and attribute-equals read it as a set / as counts).
+ *  3. Offers.  offers non-NULL replaces the staged offers wholesale (as cook_cycle_delta.offers).  NULL leaves them as they are, which
+ *     only describes the cluster when step 1 removed nothing: placements are NOT subtracted from the offers.
+ *  4. Considerable -> take num_considerable -> match over Q, exactly as a rank cycle does over the rank's output: the user state is
+ *     whatever cook_cycle_set_considerable staged last (refresh usage and tokens between cycles with that call: it does not invalidate
+ *     Q), the eligible mask follows the job rows, reserved hosts stay as staged, all placement forms apply unchanged.
+ * Afterwards cook_cycle_fetch / cook_cycle_fetch_considerable / cook_match_explain / cook_match_metrics / cook_cycle_autoscale describe
+ * THIS cycle: ranked_pending_idx is the current Q (task indices, the index space of the rank), n_ranked its length, rank_pos positions
+ * in it.  cook_user_stats / cook_unscheduled / cook_usage_breakdown keep describing the last RANK (they read the per-user order, which a
+ * queue cycle does not touch): a job matched since the rank still shows as waiting there until the next rank.
+ * State: a queue cycle needs a completed cycle since the last cook_cycle_stage / cook_cycle_update / cook_rank* / cook_considerable /
+ * cook_match_stage / cook_match_run (those shift or drop the rows Q points at, or replace the last cycle's job_to_offer), else
+ * COOK_E_STATE and nothing changes.  A refused step (COOK_E_INVALID: remove_mode > 1, offer_skipped given with n_offer_skipped other than
+ * the last cycle's offer count, a groups table of another shape, offers the stage would refuse) leaves Q, the groups and the offers
+ * as they were.  A call that fails later than that (a device error) leaves no standing queue: rank again.
+ * Timing: cook_last_timing's rank_ms of a queue cycle is the time of its advance + considerable filters + take (no rank ran);
+ * cook_match_stats_ex [31] has the host's microseconds in the advance alone.  Any rank call resets Q to the fresh order and the groups' cotasks to the staged table.  step NULL: all defaults. */
+typedef struct cook_queue_step {
+  const uint8_t* offer_skipped;  /* [offers of the LAST cycle] or NULL */
+  uint32_t remove_mode;          /* 0 kept matches, 1 every considered job */
+  uint32_t n_offer_skipped;      /* entries of offer_skipped: must equal the offer count of the LAST cycle (ignored when offer_skipped is NULL) */
+  const cook_offers* offers;     /* NULL: stay */
+  const cook_groups* groups;     /* NULL: fold the kept matches' cotasks on the device */
+} cook_queue_step;
+/* like cook_cycle_run */
+int cook_cycle_run_queue(cook_engine* e, const cook_queue_step* step, uint32_t num_considerable);
+/* like cook_cycle_run_rank: the placement is set up and runs in cook_cycle_match_multi */
+int cook_cycle_run_queue_rank(cook_engine* e, const cook_queue_step* step, uint32_t num_considerable);
+/* n pools of a device in ONE call from one thread, then cook_cycle_match_multi: the pools' advances and filters side by side, the same
+ * kernel of several pools launched once (blockIdx.y = pool), one synchronisation where each pool's flow would have its own (the
+ * mechanism of cook_cycle_run_rank_multi).  steps NULL or steps[i] NULL: defaults.  An engine twice: COOK_E_INVALID.  Returns the first
+ * engine's error that is not COOK_OK; a pool whose step was refused stays as it was, the others go on.  cook_cycle_match_multi accepts any
+ * mix of engines prepared by a rank call and by a queue call. */
+int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const uint32_t* num_considerable);
 
 /* ---- REBALANCE: replaces init-state + the rebalance loop's decisions ---------------------------------------
  * (rebalancer.clj:222-266, 320-407, 270-309, 434-467; dru.clj:128-144).
@@ -845,7 +894,9 @@ int cook_match_stats(cook_engine* e, uint32_t out[16]);
    environment (diagnostics: every device buffer sits between two bands of a pattern) the writes found outside a buffer so far, process-wide —
    the call looks at this engine's bands first —, else 0; [26..28] the last cook_cycle_update of this engine: microseconds in the call, microseconds of those the host waited in
    stream synchronisations, device buffers it had to (re)allocate, [29..30] the phase of the call that took the host longest (0 checks, 1 the delta's block,
-   2 marks and scans, 3 column compactions, 4 CSR columns, 5 the look at the device, 6 swaps and offers) and its microseconds; [31] reserved (0);
+   2 marks and scans, 3 column compactions, 4 CSR columns, 5 the look at the device, 6 swaps and offers) and its microseconds; [31] the last queue cycle of this engine
+   (cook_cycle_run_queue*): microseconds the host spent in its advance (steps 1-3), the one synchronisation included — inside
+   cook_cycle_run_queue_multi that wait is shared with the other pools' flows;
    [32..36] the last cook_cycle_run_rank_multi LED by this engine: pools, launches made, of them for more than one pool, operations
    issued on their own (copies, fills, kernels outside the batched path), stream synchronisations; [37] how the last match was placed (0 window
    rounds, 1 serial sweep, 3 class-ordered best fit), [38] why a match that could have been placed by class-ordered best fit was not (0 = it was; bits:
