@@ -15,10 +15,6 @@ struct AutoscaleBufs {
   DArr<unsigned> counters;  // [0] m, [1] |Out|
 };
 
-AutoscaleBufs& as_bufs(cook_engine* e) {
-  if (!e->asb) e->asb = new AutoscaleBufs();
-  return *e->asb;
-}
 
 void cycle_autoscale(cook_engine* e, const cook_autoscale_params* p, uint32_t* task_idx, uint32_t cap, cook_autoscale_info* info) {
   if (!p) e->fail(COOK_E_INVALID, "cook_cycle_autoscale: null params");
@@ -32,7 +28,7 @@ void cycle_autoscale(cook_engine* e, const cook_autoscale_params* p, uint32_t* t
     if (p->exclude_task[x] >= e->N) e->fail(COOK_E_INVALID, "cook_cycle_autoscale: exclude_task index out of range");
   if (cap && !task_idx) e->fail(COOK_E_INVALID, "cook_cycle_autoscale: null task_idx");
   const ConsBufs& c = *e->cb;
-  AutoscaleBufs& b = as_bufs(e);
+  AutoscaleBufs& b = bufs(e->asb);
   const unsigned n = e->n_ranked, k = e->cycle_considered;
   // ---- the kept matches and Q' (remove-matched-jobs-from-pending-jobs, scheduler.clj:790-795) ------------------------------------------
   unsigned* cnt = b.counters.ensure(2);

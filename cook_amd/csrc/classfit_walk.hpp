@@ -1315,7 +1315,7 @@ static __device__ __forceinline__ void cf_walk_pool(char* lds, const MatchIn* __
   if (tid == CF_THREADS - 1) s_total = wbase + incl;
   __syncthreads();
   const unsigned Stot = any_group ? s_total : 0u, Gl = any_group ? G : 0u;
-  // ---- layout (cf_lds_bytes_host in engine.hip computes the same sum)
+  // ---- layout (cf_lds_bytes_host in classfit_host.hpp computes the same sum)
   CfLds S;
   {
     CfFixed* F = (CfFixed*)lds;

@@ -15,7 +15,7 @@
 //   * row counts stay on the device until one read-back at the end (buffers are sized by bounds the host knows whatever the removal
 //     list holds: every old row plus the new ones, every old value of a CSR column plus the new ones);
 //   * the fresh offers are one block too, used in place (offers_block_plan / offers_block_commit).
-// Included by engine.hip (uses its DArr / KL / seg_scan helpers).
+// Included by engine.hip inside its anonymous namespace (uses device_buf.hpp, launch.hpp, rank_host.hpp's seg_scan and match_host.hpp's staging).
 #pragma once
 
 constexpr unsigned UPD_MAX_COLS = 24;
@@ -149,7 +149,6 @@ struct UpdateBufs {
   }
 };
 
-// (included inside engine.hip's anonymous namespace)
 struct BlockWriter {  // lays arrays out in a host block, 16-byte aligned; first pass (base == nullptr) only measures
   char* base;
   size_t used = 0;

@@ -6,7 +6,7 @@
 // one-dimensional grid; `cook_multi` is the one __global__ entry for all of them: blockIdx.y names the pool, the pool's own argument
 // list is read from the kernel arguments with scalar loads (blockIdx.y is uniform), and a pool whose grid is shorter than the launch's
 // leaves at once.  blockIdx.x / threadIdx.x mean what they always meant, so a kernel body does not know whether it runs alone.
-// The host side (engine.hip "pool batches") records the launches of each pool's flow and issues those of the same kernel together.
+// The host side (pool_batch.hpp) records the launches of each pool's flow and issues those of the same kernel together.
 #pragma once
 
 // a kernel of the batched path: a device function over a 1-D grid that never reads gridDim (its launch may be wider than its own grid)

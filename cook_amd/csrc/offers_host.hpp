@@ -177,3 +177,41 @@ void offers_fetch(cook_engine* e, OfferBufs& b, cook_node_offers* o, uint32_t* n
     totals->nodes_schedulable = R;
   }
 }
+
+COOK_KERNEL void fill_i32(int32_t* p, unsigned n, int32_t v) {
+  const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+// the rows of the last cook_offers_run as a cook_offers of device columns (offer.clj:31-76: Kubernetes leases; COOK_MAX_TASKS_PER_HOST
+// = the cluster's max pods per node, COOK_NUM_TASKS_ON_HOST = the node's pod count)
+cook_offers built_offers_view(cook_engine* e, int with_task_limits) {
+  if (!e->ofb || !e->ofb->done) e->fail(COOK_E_STATE, "built offers requested before cook_offers_run");
+  OfferBufs& b = *e->ofb;
+  const unsigned M = b.n_offers;
+  b.o_k8s.ensure(std::max(1u, M));
+  b.o_max_tasks.ensure(std::max(1u, M));
+  if (M) {
+    memset_async(e, b.o_k8s.ptr(), 1, M);
+    KM<fill_i32, 256>(e, "fill_i32", div_up(M, 256), b.o_max_tasks.ptr(), M, (int32_t)b.params.max_pods_per_node);
+  }
+  cook_offers o;
+  std::memset(&o, 0, sizeof(o));
+  o.n = M;
+  o.cpus = b.o_cpus.ptr();
+  o.mem = b.o_mem.ptr();
+  o.host = b.o_host.ptr();
+  o.k8s = b.o_k8s.ptr();
+  o.gpu_model = b.o_gpu_model.ptr();
+  o.gpu_count = b.o_gpu_count.ptr();
+  o.disk_type = b.o_disk_type.ptr();
+  o.disk_space = b.o_disk_space.ptr();
+  o.gpu_slots = b.gpu_slots;
+  o.disk_slots = b.disk_slots;
+  o.n_attr_keys = b.n_attr;
+  o.attr = b.n_attr ? b.o_attr.ptr() : nullptr;
+  if (with_task_limits) {
+    o.max_tasks = b.o_max_tasks.ptr();
+    o.num_tasks = b.o_num_pods.ptr();
+  }
+  return o;
+}

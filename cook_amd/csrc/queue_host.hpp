@@ -16,10 +16,6 @@ struct QueueBufs {
   unsigned cur = 0;  // which of g_*[2] holds the groups' current cotask table (when e->q_groups_own)
 };
 
-QueueBufs& queue_bufs(cook_engine* e) {
-  if (!e->qb) e->qb = new QueueBufs();
-  return *e->qb;
-}
 
 // a rank puts the groups' cotasks back to the staged table (the queue cycles' folds live in QueueBufs)
 void queue_reset_groups(cook_engine* e) {
@@ -64,7 +60,7 @@ void queue_advance(cook_engine* e, const cook_queue_step* s) {
   queue_check_step(e, s);
   const auto t_call = std::chrono::steady_clock::now();
   e->q_valid = false;  // from here on the queue is being edited: a call that fails below leaves no standing queue (cycle_take_part sets it again)
-  QueueBufs& b = queue_bufs(e);
+  QueueBufs& b = bufs(e->qb);
   MatchIn& in = e->min;
   const unsigned n = e->n_ranked, k = e->cycle_considered, G = e->G, M_old = e->M;
   const bool fold = G && k && in.j_group && !(s && s->groups);

@@ -17,10 +17,6 @@ struct SweepBufs {
   DArr<unsigned> ctl;
 };
 
-SweepBufs& sweep_bufs(cook_engine* e) {
-  if (!e->swb) e->swb = new SweepBufs();
-  return *e->swb;
-}
 
 void sweep_running(cook_engine* e, const cook_running_set* tasks, const cook_straggler_groups* groups, const cook_sweep_params* p,
                    uint8_t* reason, uint32_t* idx, uint32_t cap, double* group_threshold_s, cook_sweep_info* info) {
@@ -45,7 +41,7 @@ void sweep_running(cook_engine* e, const cook_running_set* tasks, const cook_str
     if (NS > (unsigned)INT32_MAX) e->fail(COOK_E_INVALID, "cook_sweep_running: more than INT32_MAX successful instances");
     if (NS && (!groups->succ_start_ms || !groups->succ_end_ms)) e->fail(COOK_E_INVALID, "cook_sweep_running: succ_start_ms / succ_end_ms missing");
   }
-  SweepBufs& b = sweep_bufs(e);
+  SweepBufs& b = bufs(e->swb);
   unsigned* ctl = b.ctl.ensure(SW_CTL_WORDS);
   memset_async(e, ctl, 0, SW_CTL_WORDS * 4);
   memset_async(e, ctl + SW_BAD_ROW, 0xFF, 8);  // SW_BAD_ROW, SW_BAD_SUCC = COOK_NONE_U32

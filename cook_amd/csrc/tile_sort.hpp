@@ -8,7 +8,7 @@
 // Here a workgroup takes the segments that START in its nominal stretch of TS_NOMINAL positions (so tiles are made of whole segments
 // and a tile is at most TS_NOMINAL + longest segment - 1 long), sorts them in LDS with one bitonic network whose most significant key
 // is the segment, and writes them back: one launch.  An input with a segment too long for a tile raises a flag and the host takes the
-// radix path for it (engine.hip) — the result is the same order either way, the tests run both.
+// radix path for it (rank_host.hpp) — the result is the same order either way, the tests run both.
 // (The per-user task order was tried the same way and dropped: a user of the benchmark pool holds 26 375 of its 175 000 tasks, and
 // the counting sort by user in front of it spent 300 us per launch on same-address atomics.)
 #pragma once

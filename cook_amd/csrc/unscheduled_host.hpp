@@ -13,10 +13,6 @@ struct UnschedBufs {
   DArr<double> run, total, lim[7];
 };
 
-UnschedBufs& unsched_bufs(cook_engine* e) {
-  if (!e->unb) e->unb = new UnschedBufs();
-  return *e->unb;
-}
 
 void unscheduled_run(cook_engine* e, const cook_unsched_limits* lim, const uint8_t* in_window, const uint32_t* rows, uint32_t n_rows,
                      uint32_t* reasons, uint32_t* queue_pos, double* total, bool total_is_device, uint32_t* ahead, uint32_t* list_len) {
@@ -33,7 +29,7 @@ void unscheduled_run(cook_engine* e, const cook_unsched_limits* lim, const uint8
   for (unsigned i = 0; rows && i < n_rows; ++i)
     if (rows[i] >= N) e->fail(COOK_E_INVALID, "cook_unscheduled: a row is not a row of the staged tasks");
   COOK_HIP(hipStreamSynchronize(e->stream));
-  UnschedBufs& B = unsched_bufs(e);
+  UnschedBufs& B = bufs(e->unb);
   UnLimits L;
   if (lim) {
     const double* src[7] = {lim->quota_count, lim->quota_cpus, lim->quota_mem, lim->quota_gpus, lim->share_cpus, lim->share_mem, lim->share_gpus};

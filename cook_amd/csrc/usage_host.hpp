@@ -32,10 +32,6 @@ struct UsageBufs {
   DArr<double> o_usage, o_total;
 };
 
-UsageBufs& usage_bufs(cook_engine* e) {
-  if (!e->ugb) e->ugb = new UsageBufs();
-  return *e->ugb;
-}
 
 static unsigned ub_bit_width(unsigned v) { return v ? 32u - (unsigned)__builtin_clz(v) : 0u; }
 
@@ -77,7 +73,7 @@ void usage_run(cook_engine* const* es, unsigned n, const uint32_t* const* maps, 
   }
   const unsigned stride = multi ? 2u : 1u;
   for (unsigned i = 0; i < n; ++i) COOK_HIP(hipStreamSynchronize(es[i]->stream));  // (the ranks ran on the engines' own streams)
-  UsageBufs& L = usage_bufs(e);
+  UsageBufs& L = bufs(e->ugb);
   uint32_t B_all = 0;  // buckets of all users
   uint32_t* counts = L.counts.ensure(4);
   double* d_total = L.total.ensure((size_t)n_users * 4);
@@ -96,7 +92,7 @@ void usage_run(cook_engine* const* es, unsigned n, const uint32_t* const* maps, 
     unsigned base = 0;
     for (unsigned i = 0; i < n; ++i) {
       cook_engine* p = es[i];
-      UsageBufs& Bq = usage_bufs(p);
+      UsageBufs& Bq = bufs(p->ugb);
       const uint32_t* dmap = (maps && maps[i] && p->U) ? (h2d(e, Bq.map, maps[i], p->U), Bq.map.ptr()) : nullptr;
       const uint32_t* dgrp = (groups && groups[i] && p->N) ? (h2d(e, Bq.group, groups[i], p->N), Bq.group.ptr()) : nullptr;
       hp[i] = UbPool{base, p->N, p->s_use.ptr(), p->s_pending.ptr(), p->s_user.ptr(), p->permB, dmap, dgrp};

@@ -20,10 +20,6 @@ struct UserStatsBufs {
   DArr<UsPool> pools;
 };
 
-UserStatsBufs& us_bufs(cook_engine* e) {
-  if (!e->usb) e->usb = new UserStatsBufs();
-  return *e->usb;
-}
 
 void user_stats_run(cook_engine* const* es, unsigned n, const uint32_t* const* maps, unsigned n_users, const cook_user_limits* lim,
                     double* per_user, bool per_user_is_device, uint8_t* user_state, cook_user_stats_totals* totals) {
@@ -52,7 +48,7 @@ void user_stats_run(cook_engine* const* es, unsigned n, const uint32_t* const* m
     }
   }
   for (unsigned i = 0; i < n; ++i) COOK_HIP(hipStreamSynchronize(es[i]->stream));  // (the ranks ran on the engines' own streams)
-  UserStatsBufs& L = us_bufs(e);
+  UserStatsBufs& L = bufs(e->usb);
   uint32_t* flags = L.flags.ensure(n_users);
   unsigned* counts = L.counts.ensure(8);
   const unsigned nblk = std::max(1u, std::min(div_up(n_users, 256), 64u));
@@ -74,7 +70,7 @@ void user_stats_run(cook_engine* const* es, unsigned n, const uint32_t* const* m
   std::vector<const uint32_t*> dmaps(n, nullptr);
   for (unsigned i = 0; i < n; ++i) {
     cook_engine* p = es[i];
-    UserStatsBufs& B = us_bufs(p);
+    UserStatsBufs& B = bufs(p->usb);
     const unsigned N = p->N, U = p->U;
     if (maps && maps[i]) {
       h2d(e, B.map, maps[i], U);
@@ -99,8 +95,8 @@ void user_stats_run(cook_engine* const* es, unsigned n, const uint32_t* const* m
   for (unsigned i = 1; i < n; ++i) {
     const cook_engine* p = es[i];
     if (p->N)
-      KM<us_check, 256>(e, "us_check", div_up(p->N, 256), (const SumRW*)us_bufs(es[i]).pre.ptr(), (const uint32_t*)p->s_user.ptr(), dmaps[i],
-          (const double*)us_bufs(es[i]).carry.ptr(), p->N, flags);
+      KM<us_check, 256>(e, "us_check", div_up(p->N, 256), (const SumRW*)bufs(es[i]->usb).pre.ptr(), (const uint32_t*)p->s_user.ptr(), dmaps[i],
+          (const double*)bufs(es[i]->usb).carry.ptr(), p->N, flags);
   }
   KM<us_fold, 64>(e, "us_fold", div_up(n_users, 64), (const UsPool*)L.pools.ptr(), n, n_users, (const uint32_t*)flags, out);
   // ---- starved / under quota / counts, then the "all" rows

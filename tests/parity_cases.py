@@ -79,7 +79,7 @@ def rank_parity(make_engine, pool: synth.Pool, params, quota=None):
 
 
 def tie_rule_forms(make_engine, monkeypatch, n_users=400, per_user=6):
-    """The sorted-merge tie rule in both of the engine's forms (cook_amd/csrc/tile_sort.hpp: tie groups sorted in LDS tiles; engine.hip
+    """The sorted-merge tie rule in both of the engine's forms (cook_amd/csrc/tile_sort.hpp: tie groups sorted in LDS tiles; rank_host.hpp
     tie_refine_radix: radix passes over the tied items), on the same pools.  Many users with the SAME tasks in the same order make tie
     groups of n_users items that stay tied until the users' name order decides (deep doubling rounds); with the emulated suite's small
     tiles such a group does not fit one and the call has to fall back on its own."""

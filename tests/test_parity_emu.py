@@ -717,7 +717,7 @@ def test_guard_bands_report_a_write_past_a_buffer():
             assert "PAST its end" in r.stderr
 
 
-# ---- the rank parts of several pools in one call (cook_cycle_run_rank_multi: pool batches, engine.hip) ------------------------------------
+# ---- the rank parts of several pools in one call (cook_cycle_run_rank_multi: pool batches, pool_batch.hpp) ------------------------------------
 def test_rank_batch_diverging_flows(make_engine):
     stats = P.rank_batch_parity(make_engine, P.rank_batch_cases(), k=300, n_users=300, min_grouped=20)
     assert stats[-1]["rank_batch_single_ops"] <= stats[-1]["rank_batch_launches"], stats[-1]
