@@ -103,6 +103,12 @@ struct CfLds {  // the workgroup's LDS, carved at run time
   const uint32_t* envw; // CFE_*: the call's constants
 };
 
+// eight level values in eight REGISTERS (as an array inside a structure, or as a vector type indexed by a variable, the compiler keeps them in scratch
+// memory: a store of the whole set and an indexed load per access, seen in the ISA)
+struct CfLv8 {
+  uint32_t v0, v1, v2, v3, v4, v5, v6, v7;
+};
+#define CF_FOR8(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
 static __device__ __forceinline__ unsigned cf_level_of(const uint32_t* t, uint32_t fc) {  // (t: the call's levels, in LDS)
    // how many of the levels fc reaches (t ascending)
   unsigned n = 0;
@@ -110,12 +116,20 @@ static __device__ __forceinline__ unsigned cf_level_of(const uint32_t* t, uint32
   for (int i = 0; i < CF_LV; ++i) n += fc >= t[i] ? 1u : 0u;
   return n;
 }
-// eight level values in eight REGISTERS (as an array inside a structure, or as a vector type indexed by a variable, the compiler keeps them in scratch
-// memory: a store of the whole set and an indexed load per access, seen in the ISA)
-struct CfLv8 {
-  uint32_t v0, v1, v2, v3, v4, v5, v6, v7;
-};
-#define CF_FOR8(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7)
+// the call's levels (CfLds::t never changes during a launch) as eight wave-uniform values: a role loads them once, and a level count is eight
+// compares without a trip to the LDS
+static_assert(CF_LV == 8, "CfLv8 holds the call's levels");
+static __device__ __forceinline__ CfLv8 cf_levels_load(const uint32_t* t) {
+  const uint32_t t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4], t5 = t[5], t6 = t[6], t7 = t[7];  // (one trip: the eight reads are in flight together)
+  return CfLv8{wave_uniform_u32(t0), wave_uniform_u32(t1), wave_uniform_u32(t2), wave_uniform_u32(t3), wave_uniform_u32(t4), wave_uniform_u32(t5), wave_uniform_u32(t6), wave_uniform_u32(t7)};
+}
+static __device__ __forceinline__ unsigned cf_level_of(const CfLv8& t, uint32_t fc) {
+  unsigned n = 0;
+#define CF_LO(i) n += fc >= t.v##i ? 1u : 0u;
+  CF_FOR8(CF_LO)
+#undef CF_LO
+  return n;
+}
 static __device__ __forceinline__ uint32_t cf_lv_get(const CfLv8& a, unsigned i) {  // a wave-uniform index: a tree of selects on its three bits
   const bool b0 = (i & 1u) != 0u, b1 = (i & 2u) != 0u, b2 = (i & 4u) != 0u;
   const uint32_t r01 = b0 ? a.v1 : a.v0, r23 = b0 ? a.v3 : a.v2, r45 = b0 ? a.v5 : a.v4, r67 = b0 ? a.v7 : a.v6;
@@ -147,8 +161,7 @@ static __device__ __forceinline__ void cf_setup_chunks(const CfClass* cls, unsig
 }
 
 // the level summaries of chunk `ch` (wave-uniform) from its members; lanes = positions
-static __device__ __forceinline__ void cf_tighten(const CfLds& S, unsigned lane, unsigned ch, CfChunkLane& c) {
-  const uint32_t* t = S.t;
+static __device__ __forceinline__ void cf_tighten(const CfLds& S, const CfLv8& t, unsigned lane, unsigned ch, CfChunkLane& c) {
   const unsigned pos0 = (unsigned)wave_read_lane((int)c.pos0, (int)ch), n = (unsigned)wave_read_lane((int)c.n, (int)ch);
   const bool in = lane < n;
   const CfFree f = S.fcm[pos0 + lane];
@@ -178,21 +191,18 @@ static __device__ __forceinline__ void cf_wave_tables(const CfLds& S, unsigned l
 #undef CF_TB_A
   wave_max8_u32(p0, p1, p2, p3, p4, p5, p6, p7);
   wave_max8_u32(a0, a1, a2, a3, a4, a5, a6, a7);
-#define CF_TB_S(i) \
-  if (lane == 0) S.pw[lw * CF_LV + i] = p##i, S.aw[lw * CF_LV + i] = a##i;
-  CF_FOR8(CF_TB_S)
-#undef CF_TB_S
+  // (a row is 32 bytes, 16-byte aligned: two wide stores of one lane, no compare and no branch on the lane)
+  st_lane0_b128(&S.pw[lw * CF_LV], p0, p1, p2, p3), st_lane0_b128(&S.pw[lw * CF_LV + 4], p4, p5, p6, p7);
+  st_lane0_b128(&S.aw[lw * CF_LV], a0, a1, a2, a3), st_lane0_b128(&S.aw[lw * CF_LV + 4], a4, a5, a6, a7);
   for (unsigned k = 1; k < n_kind; ++k) {
     if (!((kinds >> k) & 1u)) continue;
 #define CF_TB_G(i) unsigned g##i = c.kind == k ? c.lv.v##i : 0u;
     CF_FOR8(CF_TB_G)
 #undef CF_TB_G
     wave_max8_u32(g0, g1, g2, g3, g4, g5, g6, g7);
-#define CF_TB_GS(i) \
-  if (lane == 0) S.gk[k * CF_LV + i] = g##i;
-    CF_FOR8(CF_TB_GS)
-#undef CF_TB_GS
+    st_lane0_b128(&S.gk[k * CF_LV], g0, g1, g2, g3), st_lane0_b128(&S.gk[k * CF_LV + 4], g4, g5, g6, g7);
   }
+  WAIT_LDS();  // (these stores are not on the compiler's books: they have landed before the barrier behind which the bookkeeper reads the rows)
 }
 
 // the job's constraints other than the gpu kind against offer `id` (lane-parallel; the branches are wave-uniform)
@@ -234,7 +244,7 @@ struct CfAns {
   unsigned pos, ch, cid, fc, fm, cls;
   double fa;
 };
-static __device__ __forceinline__ void cf_class_answer(const CfLds& S, const CfJobU& J, unsigned lane, CfChunkLane& c, CfAns& out, unsigned& scans,
+static __device__ __forceinline__ void cf_class_answer(const CfLds& S, const CfLv8& tl, const CfJobU& J, unsigned lane, CfChunkLane& c, CfAns& out, unsigned& scans,
                                                        unsigned& tightened) {
   out.have = false, out.amb = false, out.pos = 0u, out.ch = 0u, out.cid = 0u, out.fc = 0u, out.fm = 0u, out.cls = 0u, out.fa = 0.0;
   const uint32_t lvL = cf_lv_get(c.lv, J.L);
@@ -251,7 +261,7 @@ static __device__ __forceinline__ void cf_class_answer(const CfLds& S, const CfJ
     const unsigned long long b = __ballot(ok);
     if (b == 0ull) {
       if (__ballot(room) == 0ull) {  // a stale summary (members have left since): exact again
-        cf_tighten(S, lane, ch, c);
+        cf_tighten(S, tl, lane, ch, c);
         ++tightened;
       }
       m &= ~(1ull << ch);
@@ -371,6 +381,7 @@ struct CfFixed {
   uint32_t env_t[CF_LV], envw[CFE_N];
 };
 static_assert(sizeof(CfFixed) % 16 == 0, "the arrays behind it are 16-byte aligned");
+static_assert(offsetof(CfFixed, pw) % 16 == 0 && offsetof(CfFixed, aw) % 16 == 0 && offsetof(CfFixed, gk) % 16 == 0 && (CF_LV * 4) % 16 == 0, "cf_wave_tables stores the rows 16 bytes at a time");
 #if COOK_HAS_ASM_WALK
 #define CF_ASM_EPOCH_LIVE "57"
 #include "classfit_asm.hpp"
@@ -393,6 +404,10 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
   // (the call's constants live in LDS: what a rare path needs is read there, not kept in scalar registers across the walk)
   const unsigned K = wave_uniform_u32(S.envw[CFE_K]), cmin = wave_uniform_u32(S.envw[CFE_CMIN]), mmin = wave_uniform_u32(S.envw[CFE_MMIN]);
   const uint32_t* t = S.t;
+  // a class wave: the call's levels, loaded once per launch as wave-uniform values.  (The walk is short of scalar registers: the compiler parks
+  // them in lanes of a vector register and brings them back with v_readlane where phase 1 / cf_tighten use them; no scratch, no LDS trip.)
+  CfLv8 tl = CfLv8{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  if (is_class_wave) tl = cf_levels_load(t);
 #define n_cls wave_uniform_u32(S.envw[CFE_NCLS])
 #define n_kind wave_uniform_u32(S.envw[CFE_NKIND])
 #define NP wave_uniform_u32(S.envw[CFE_NP])
@@ -421,7 +436,7 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
   };
   if (is_class_wave) {
     class_setup();
-    for (unsigned ch = 0; ch < nch_wave; ++ch) cf_tighten(S, lane, ch, c);
+    for (unsigned ch = 0; ch < nch_wave; ++ch) cf_tighten(S, tl, lane, ch, c);
     if (rep == 0u && lw != 0u) cf_wave_tables(S, lw, lane, c, wk, n_kind);
   }
   // the decider's lanes
@@ -879,7 +894,7 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
             if (!done) {  // constraints, several classes, a chunk whose summary promised too much
               const CfJobU J = job_of(s);
               CfAns a;
-              cf_class_answer(S, J, lane, c, a, st_scans, st_tight);
+              cf_class_answer(S, tl, J, lane, c, a, st_scans, st_tight);
               const unsigned long long fb = (unsigned long long)__double_as_longlong(a.fa);
               st_lane0_b32(&e->tag, 0xFFFFFFFFu);
               st_lane0_b128(&e->fc, a.fc, a.fm, (unsigned)fb, (unsigned)(fb >> 32));
@@ -1142,7 +1157,7 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
         if (is_class_wave) {
           cf_setup_chunks(S.cls, n_cls, lw, lane, c, nch_wave);
           class_setup();
-          for (unsigned ch = 0; ch < nch_wave; ++ch) cf_tighten(S, lane, ch, c);
+          for (unsigned ch = 0; ch < nch_wave; ++ch) cf_tighten(S, tl, lane, ch, c);
           if (rep == 0u && lw != 0u) cf_wave_tables(S, lw, lane, c, wk, n_kind);
           tight_applied = st_tight;
         }
@@ -1169,24 +1184,36 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
     const unsigned long long tp0 = CF_TICKS();
     if (is_decider && nw == 0u) decider_books(0u);  // (a batch nobody walks raises no turn)
     if (nw != 0u) {
-      if (is_class_wave) {  // the batch's removals from this wave's chunks: summaries a member that left was the maximum of are recomputed
+      if (is_class_wave) {
+        // The batch's removals from this wave's chunks, one pass with lane = log entry: every lane reads its own entry, fetches the eight summaries of
+        // the entry's chunk from the lane that holds them (a lane-indexed shuffle), and flags the chunk if the member that left was the maximum of a
+        // level it reached (or is a gpu host: changed in place).  Each flagged chunk is recomputed ONCE.  Exact, because the decider zeroes a member in
+        // LDS at commit (a gpu host: its new free values and CF_OCC), so every removal of the batch is in S.fcm / S.cid by now and one cf_tighten of a
+        // chunk yields its exact summary however many members left it.  Every entry is compared against the summaries as they stand at this point, not
+        // as an earlier entry's recomputation would have left them: that can only flag a chunk which the entry-by-entry order would have flagged too, or
+        // one whose second member equals the one that left — it recomputes to the same value.  A chunk nobody flags lost no maximum at any level (a
+        // summary is an upper bound that was exact when it was last computed; a member that left since then and held the maximum has an entry that says
+        // so), so it is still exact.  (cf_retightened counts chunks here, not entries: lower where two entries of a batch name one chunk.)
+        const CfLog* lp = &S.log[lane];
+        const unsigned info = lp->info, ofc = lp->ofc, ofm = lp->ofm;
         const unsigned n_log = wave_uniform_u32(S.misc[CFX_LOGN]), a0 = wave_uniform_u32(S.misc[CFX_LOG_APPLIED]);
-        const bool mine_e = lane >= a0 && lane < n_log && ((S.log[lane].info >> 8) & 15u) == lw;
-        bool dirty = st_tight != tight_applied;
-        for (unsigned long long mm = __ballot(mine_e); mm; mm &= mm - 1ull) {
-          const unsigned x = (unsigned)__ffsll(mm) - 1u;
-          const CfLog lg = S.log[x];
-          const unsigned ch = (lg.info >> 12) & 255u;
-          bool retable = ((lg.info >> 20) & 1u) != 0u;  // (a gpu placement changes the member in place)
-          const unsigned nl = cf_level_of(t, lg.ofc);
-#define CF_WAS_MAX(i) retable = retable || (__ballot(lane == ch && (unsigned)i < nl && c.lv.v##i == lg.ofm + 1u) != 0ull);
-          CF_FOR8(CF_WAS_MAX)
+        const bool mine = lane >= a0 && lane < n_log && ((info >> 8) & 15u) == lw;
+        const unsigned ch = (info >> 12) & 63u;  // (lane = chunk: a wave holds at most 64; the mask keeps the shuffle's index and the shift below in range for lanes whose entry is not the wave's)
+        const unsigned nl = cf_level_of(tl, ofc);
+#define CF_LV_AT(i) const unsigned g##i = (unsigned)__shfl((int)c.lv.v##i, (int)ch, COOK_WAVE);  // (every lane takes part; the eight are in flight together)
+        CF_FOR8(CF_LV_AT)
+#undef CF_LV_AT
+        bool was_max = ((info >> 20) & 1u) != 0u;  // (a gpu placement changes the member in place)
+#define CF_WAS_MAX(i) was_max = was_max | (((unsigned)i < nl) & (g##i == ofm + 1u));
+        CF_FOR8(CF_WAS_MAX)
 #undef CF_WAS_MAX
-          if (retable) {
-            cf_tighten(S, lane, ch, c);
-            ++st_tight;
-            dirty = true;
-          }
+        unsigned long long stale = 0ull;  // the chunks to recompute, one bit per chunk lane
+        for (unsigned long long fm = cook_ballot(mine & was_max); fm != 0ull; fm &= fm - 1ull) stale |= 1ull << (unsigned)wave_read_lane((int)ch, __ffsll(fm) - 1);
+        bool dirty = st_tight != tight_applied;
+        for (; stale != 0ull; stale &= stale - 1ull) {
+          cf_tighten(S, tl, lane, (unsigned)__ffsll(stale) - 1u, c);
+          ++st_tight;
+          dirty = true;
         }
         if (dirty && rep == 0u && lw != 0u) cf_wave_tables(S, lw, lane, c, wk, n_kind);
         tight_applied = st_tight;
