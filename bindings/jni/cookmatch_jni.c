@@ -9,7 +9,9 @@
  * java.nio.ByteBuffers (native byte order), one element per pointer field of the struct IN THE FIELD ORDER OF
  * include/cookmatch.h; a null element = a NULL (optional) pointer.  Scalars of the struct (n, n_attr_keys, flags) are
  * explicit jint arguments.  Plain-data structs (cook_params, cook_pool_quota, cook_rebalance_params) cross as one
- * direct buffer holding the struct itself.  Outputs are direct buffers sized by the caller as the header documents.
+ * direct buffer holding the struct itself (cook_params: the last int32, at byte 44, is `fitness` — the pool's
+ * :fenzo-fitness-calculator as COOK_FITNESS_*; a value outside 0..5 makes create / setParams return
+ * COOK_E_INVALID, and lastError(0) has the message of a refused create).  Outputs are direct buffers sized by the caller as the header documents.
  * cook_jobs / cook_offers take their three extra scalars (n_scalars; gpu_slots, disk_slots) as explicit jints too.
  * GetDirectBufferAddress never copies or pins: the SoA arrays the Clojure side fills are read in place by the
  * H2D copies of the engine.

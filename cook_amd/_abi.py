@@ -32,7 +32,7 @@ class CookParams(C.Structure):
         ("good_enough_fitness", C.c_double),
         ("host_lifetime_mins", C.c_int64),
         ("match_algo", C.c_int32),
-        ("reserved", C.c_int32),
+        ("fitness", C.c_int32),
     ]
 
 
@@ -201,10 +201,27 @@ def default_params(**kw) -> CookParams:
     """Reference defaults: config.clj:108-116 (fenzo), :413-416 (max-over-quota-jobs 100), :398-407 (task-constraints)."""
     p = CookParams(dru_mode=0, max_over_quota_jobs=100, offensive_max_mem_mb=float("inf"),
                    offensive_max_cpus=float("inf"), good_enough_fitness=0.8, host_lifetime_mins=0, match_algo=0,
-                   reserved=0)
+                   fitness=0)
     for k, v in kw.items():
+        if k == "fitness":
+            v = fitness_value(v)
         setattr(p, k, v)
     return p
+
+
+# cook_params.fitness by the names Cook's :fenzo-fitness-calculator carries (config.clj:108; INTEGRATION.md §2)
+FITNESS_NAMES = ("cpuMemBinPacker", "cpuBinPacker", "memoryBinPacker", "cpuMemSpreader", "cpuSpreader", "memorySpreader")
+
+
+def fitness_value(v) -> int:
+    """0..5, or a calculator's name — bare ("cpuSpreader") or as the config writes it
+    ("com.netflix.fenzo.plugins.BinPackingFitnessCalculators/cpuMemBinPacker") — -> the value of cook_params.fitness."""
+    if isinstance(v, str):
+        name = v.replace("/", ".").rsplit(".", 1)[-1]
+        if name not in FITNESS_NAMES:
+            raise ValueError(f"fitness calculator {v!r}: one of {', '.join(FITNESS_NAMES)}")
+        return FITNESS_NAMES.index(name)
+    return int(v)
 
 
 @dataclass

@@ -52,6 +52,7 @@ enum : unsigned {
   CF_X_SHAPE = 32u,       // too many classes / kinds / offers, a class beyond 64 chunks, LDS
   CF_X_LEVELS = 64u,      // job cpus values not on the 8 levels
   CF_X_ZERO = 128u,       // a job asking for nothing (fitness 0 is a failure in Fenzo), totals of 0
+  CF_X_FITNESS = 0x20000u,  // cook_params.fitness other than cpuMemBinPacker (the host's check, from the params alone: no set-up launch ran)
 };
 
 struct CfClass {

@@ -220,6 +220,7 @@ struct cook_engine {
   bool has_deferred_cf = false;         // this engine's match is set up for cf_walk and waits for cook_cycle_match_multi
   CfPoolCtx deferred_cf{};
   unsigned last_form = 0;               // how the last match was placed: 0 window rounds, 1 serial sweep, 3 class-ordered best fit
+  unsigned spread_serial_calls = 0;     // matches that match_algo 0 / 2 / 3 would have placed in window rounds and the sweep placed: a spreader (cook_match_stats_ex [39])
   unsigned cf_inelig = 0;               // why the last match that asked for class-ordered best fit did not get it (CF_X_* bits; 0x10000: switched off / the host's checks)
   uint32_t cf_stats[48] = {};
   char* h_cf = nullptr;                 // pinned: summaries and statistics of the pools of a cf_run led by this engine
@@ -328,9 +329,19 @@ const char* cook_version(void) {
 }
 int cook_abi_version(void) { return COOK_ABI_VERSION; }
 
+// the values of cook_params that are refused where they are set (create, set_params) -> the message, or nullptr
+static const char* params_refusal(const cook_params* p) {
+  if (p->fitness < 0 || p->fitness >= COOK_FITNESS_N)
+    return "cook_params.fitness: 0 = cpuMemBinPacker, 1 = cpuBinPacker, 2 = memoryBinPacker, 3 = cpuMemSpreader, 4 = cpuSpreader, 5 = memorySpreader";
+  return nullptr;
+}
+static thread_local const char* tl_create_err = nullptr;  // cook_last_error(NULL): why the thread's last create refused its params (null: it did not)
+
 int cook_engine_create(const cook_params* params, int device_id, cook_engine** out) {
   if (!params || !out) return COOK_E_INVALID;
   *out = nullptr;
+  tl_create_err = params_refusal(params);
+  if (tl_create_err) return COOK_E_INVALID;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return COOK_E_DEVICE;  // no GPU: fail loudly, no CPU fallback
   if (device_id < 0 || device_id >= ndev) return COOK_E_INVALID;
@@ -370,11 +381,15 @@ void cook_engine_destroy(cook_engine* e) {
 
 int cook_engine_set_params(cook_engine* e, const cook_params* p) {
   if (!e || !p) return COOK_E_INVALID;
+  if (const char* why = params_refusal(p)) {  // the engine keeps the params it had
+    e->err = why;
+    return COOK_E_INVALID;
+  }
   e->params = *p;
   return COOK_OK;
 }
 
-const char* cook_last_error(const cook_engine* e) { return e ? e->err.c_str() : "null engine"; }
+const char* cook_last_error(const cook_engine* e) { return e ? e->err.c_str() : (tl_create_err ? tl_create_err : "null engine"); }
 
 int cook_rank_stage(cook_engine* e, const cook_tasks* tasks, const cook_users* users) {
   return guarded(e, [&] { rank_stage(e, tasks, users); });
@@ -840,7 +855,7 @@ int cook_match_stats_ex(cook_engine* e, uint32_t* out, uint32_t cap) {
     if (e->upd_phase_us[k] > v[30]) v[29] = k, v[30] = e->upd_phase_us[k];
   for (unsigned k = 0; k < 5u; ++k) v[32 + k] = e->batch_stats[k];
   v[31] = e->q_advance_us;
-  v[37] = e->last_form, v[38] = e->cf_inelig;
+  v[37] = e->last_form, v[38] = e->cf_inelig, v[39] = e->spread_serial_calls;
   if (e->last_form == 3u)
     for (unsigned k = 0; k < 24u; ++k) v[40 + k] = e->cf_stats[k];
   if (g_guard) {  // COOK_GUARD=1: look at the bands of every live buffer now, this engine's among them; the count is process-wide and includes buffers already freed

@@ -195,7 +195,7 @@ __global__ void __launch_bounds__(256) explain_classify(MatchIn in, MatchState s
         atomicAdd(&s_cnt[why], 1u);
       } else {
         const double rc = in.o_run_cpus ? in.o_run_cpus[v] : 0.0, rm = in.o_run_mem ? in.o_run_mem[v] : 0.0;
-        const double fit = ((rc + ac + c) / (in.o_cpus[v] + rc) + (rm + am + m) / (in.o_mem[v] + rm)) / 2.0;
+        const double fit = fitness_calc(in.fitness, rc + ac + c, in.o_cpus[v] + rc, rm + am + m, in.o_mem[v] + rm);
         if (!(fit > 0.0)) atomicAdd(&s_cnt[WHY_FITNESS], 1u);
       }
     }

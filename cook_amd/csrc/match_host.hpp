@@ -5,8 +5,10 @@
 
 // The placement walk keeps one LDS byte per offer of the pool.  A pool in a lockstep chain runs the good-enough flavour of the kernels
 // whenever ANY pool of its chain has good-enough < 1 (match_rounds_multi), so the table must leave room for segments in both.
+// the spreaders (cook_params.fitness 3..5) are placed by the serial sweep whatever match_algo says (match_run_device)
+static bool fitness_is_spreader(const cook_engine* e) { return e->params.fitness >= COOK_FITNESS_CPU_MEM_SPREADER; }
 void match_check_offer_count(cook_engine* e, unsigned M) {
-  if (e->params.match_algo == 1) return;  // (the one-job-at-a-time sweep has no such table)
+  if (e->params.match_algo == 1 || fitness_is_spreader(e)) return;  // (the one-job-at-a-time sweep has no such table)
   if (std::min(resolve_wseg<true>(M), resolve_wseg<false>(M)) < MV_WSEG_MIN)
     e->fail(COOK_E_INVALID, "cook_match: too many offers in one pool for the placement walk's offer table (about 150 000)");
 }
@@ -162,6 +164,7 @@ void match_stage_inputs(cook_engine* e, const cook_jobs* j, const cook_offers* o
   }
   in.good_enough = e->params.good_enough_fitness;
   in.host_lifetime_mins = e->params.host_lifetime_mins;
+  in.fitness = (unsigned)e->params.fitness;
   sync(e);  // `bits` is a host temporary
   e->K = K;
   e->M = M;
@@ -356,6 +359,10 @@ static WinCtl first_window(const cook_engine* e, unsigned K) {
 // class-ordered best fit when the call's numbers and constraints allow it (classfit_host.hpp) -> true: the match is placed, or (defer) set up
 // for cook_cycle_match_multi, which runs the walks of a device's pools in one launch
 static bool match_try_classfit(cook_engine* e, const MatchIn& in, const MatchState& st, const V2Buf& vb, bool defer) {
+  if (in.fitness != 0u) {  // its class order IS cpuMemBinPacker's: refused from the params alone, before any of its set-up launches
+    e->cf_inelig = CF_X_FITNESS;
+    return false;
+  }
   if (!cf_setup(e, in, (const MatchIn*)vb.in_dev, st, vb.jr, vb.jcons, vb.oa, vb.ob, e->deferred_cf)) return false;
   e->cycle_considered = in.K;
   e->match_done = false;
@@ -464,14 +471,23 @@ void match_run_device(cook_engine* e, unsigned K, const uint32_t* j_index, bool 
   in.j_index = j_index;
   in.good_enough = e->params.good_enough_fitness;
   in.host_lifetime_mins = e->params.host_lifetime_mins;
+  in.fitness = (unsigned)e->params.fitness;
   e->last_in = in;
   e->last_in_valid = true;
   const MatchState st = match_state_setup(e, in);
   e->has_deferred = false;
+  e->cf_inelig = 0;  // (stats word 38 speaks of THIS match: set below or by match_try_classfit where the class-ordered form was asked for and refused)
   const int algo = e->params.match_algo;
   if (!(algo == 0 || algo == 1 || algo == 2 || algo == 3))
     e->fail(COOK_E_INVALID, "cook_params.match_algo: 0 = engine default (window rounds; class-ordered best fit where the call allows it when six or more engines share the device), 1 = serial sweep, 2 = window rounds, 3 = class-ordered best fit where the call allows it, else window rounds");
-  if (algo == 1) {  // one-job-at-a-time sweep by a single workgroup (reference implementation of the chain)
+  // A spreader's fitness FALLS on the offer a job lands on, so the window rounds' rule "a touched offer that is still feasible beats every
+  // untouched offer behind it" is false for it: such a pool is placed by the sweep, as match_algo 1
+  const bool spread = fitness_is_spreader(e);
+  if (spread && algo != 1) {
+    ++e->spread_serial_calls;
+    if (algo == 3 || (algo == 0 && classfit_by_default(e))) e->cf_inelig = CF_X_FITNESS;
+  }
+  if (algo == 1 || spread) {  // one-job-at-a-time sweep by a single workgroup (reference implementation of the chain)
     constexpr int SERIAL_THREADS = COOK_SHAPE(1024, 256);
     auto k_match = match_serial<SERIAL_THREADS>;
     KL("match_serial", k_match, 1, SERIAL_THREADS, in, st);

@@ -1,10 +1,10 @@
 // match_kernels.hpp — device side of cook_match: rank-ordered bin-pack placement, i.e. what Cook delegates to
-// Fenzo's TaskScheduler.scheduleOnce (scheduler.clj:617-687, 2301-2324) with cpuMemBinPacker fitness (config.clj:108)
-// and Cook's hard constraints (constraints.clj).
+// Fenzo's TaskScheduler.scheduleOnce (scheduler.clj:617-687, 2301-2324) with the pool's fitness calculator (config.clj:108: cpuMemBinPacker
+// unless configured otherwise; fitness_calc below) and Cook's hard constraints (constraints.clj).
 //
 // Semantics (DESIGN.md "placement"): for each job in rank order, among the
 // offers that still have room and pass every constraint pick the one with the strictly greatest fitness
-//   ((run_cpus + assigned_cpus + job.cpus) / (offer.cpus + run_cpus) + (same for mem)) / 2
+//   ((run_cpus + assigned_cpus + job.cpus) / (offer.cpus + run_cpus) + (same for mem)) / 2        [cook_params.fitness 0; 1..5: fitness_calc]
 // (lowest offer index on ties; the first offer in array order whose fitness exceeds good-enough wins outright), then
 // commit the job to it.  Job i+1 sees job i's commitment: the placement is a sequential chain.
 #pragma once
@@ -53,6 +53,7 @@ struct MatchIn {
   // != 0: two offers of the call share a host (then a placement can forbid, for a unique host-placement group, an offer OTHER
   // than the one it was made on, and the placement walk sends every group member through its general path)
   unsigned host_dup;
+  unsigned fitness;  // cook_params.fitness (0..5, checked by the host): which calculator fitness_calc applies
   // entries per host in the k8s "gpus" / "disk" maps (>= 1; o_gpu_model / o_gpu_count are [M][gpu_slots], model 0 = empty slot)
   unsigned gpu_slots, disk_slots;
   // Fenzo's other additive resources (cookmatch.h cook_jobs.ports / .scalars): has_x == 0 when no job of the call asks for any
@@ -244,6 +245,19 @@ static __device__ __forceinline__ bool constraints_pass(const MatchIn& in, const
   return static_pass(in, jj, v) && dyn_pass(in, jj, v, acount_v) && group_pass(in, st, jj, v);
 }
 
+// The fitness calculators of cook_params.fitness on the fill ratios cf = nc / dc (nc = run_cpus + assigned_cpus + job.cpus, dc = offer.cpus +
+// run_cpus) and mf = nm / dm: 0 cpuMemBinPacker (config.clj:108), 1 cpuBinPacker, 2 memoryBinPacker, 3 cpuMemSpreader, 4 cpuSpreader,
+// 5 memorySpreader, operation for operation as the oracles compute them (the frozen CPU oracle's match_impl for 0, tests/fitness_oracle.py for the
+// rest).  `f` is uniform over a launch's pool: a scalar branch, and the one-resource forms execute one divide.
+static __device__ __forceinline__ double fitness_calc(unsigned f, double nc, double dc, double nm, double dm) {
+  if (f == 0u) return (nc / dc + nm / dm) / 2.0;
+  if (f == 1u) return nc / dc;
+  if (f == 2u) return nm / dm;
+  if (f == 3u) return ((1.0 - nc / dc) + (1.0 - nm / dm)) / 2.0;
+  if (f == 4u) return 1.0 - nc / dc;
+  return 1.0 - nm / dm;
+}
+
 struct Cand {
   double fit;
   int idx;
@@ -282,7 +296,7 @@ __global__ void __launch_bounds__(THREADS) match_serial(MatchIn in, MatchState s
         continue;
       }
       const double rc = in.o_run_cpus ? in.o_run_cpus[v] : 0.0, rm = in.o_run_mem ? in.o_run_mem[v] : 0.0;
-      const double fit = ((rc + ac + c) / (in.o_cpus[v] + rc) + (rm + am + m) / (in.o_mem[v] + rm)) / 2.0;
+      const double fit = fitness_calc(in.fitness, rc + ac + c, in.o_cpus[v] + rc, rm + am + m, in.o_mem[v] + rm);
       if (!(fit > 0.0)) {
         fail |= 4u;
         continue;

@@ -401,9 +401,41 @@ static __device__ __forceinline__ bool dyn_fast(const JobRec& j, const OfferB& o
   if (j.g > 0 && (o.flags & 1u) && o.run_count + acount != 0) return false;
   return acount < o.task_slack;
 }
-// cpuMemBinPacker (config.clj:108), operation for operation as the oracle computes it
-static __device__ __forceinline__ double fitness_of(const OfferA& a, double ac, double am, double c, double m) {
-  return ((a.rc + ac + c) / (a.oc + a.rc) + (a.rm + am + m) / (a.om + a.rm)) / 2.0;
+// the pool's fitness calculator (fm = cook_params.fitness; 0 = cpuMemBinPacker, config.clj:108), operation for operation as the oracle computes it.
+// Only the bin packers (0..2) reach the window rounds: the walk rests on "a placement never lowers the fitness of the offer it lands on", which
+// the spreaders turn round (the host places those by the serial sweep, match_host.hpp).
+static __device__ __forceinline__ double fitness_of(unsigned fm, const OfferA& a, double ac, double am, double c, double m) {
+  return fitness_calc(fm, a.rc + ac + c, a.oc + a.rc, a.rm + am + m, a.om + a.rm);
+}
+// The approximate terms a1 ~ cf, a2 ~ mf (numerator times the rounded reciprocal of the denominator) under a one-resource packer: the term that
+// does not count is replaced by the one that does, and every expression built for cpuMemBinPacker then stands for the one-resource fitness
+// EXACTLY: (x + x) * 0.5 == x in binary floating point (the sum is a change of exponent, the halving another; no overflow: x is a fill ratio).
+// So the bounds are derived for ONE term x = fl(n * fl(1 / d)) against the exact fitness fl(n / d), n >= 0, d > 0, u = 2^-53:
+//   x = (n / d) (1 + e1) (1 + e2) with |e1|, |e2| <= u (reciprocal, product), fl(n / d) = (n / d) (1 + e3) with |e3| <= u
+//   => |x - fl(n / d)| <= fl(n / d) * ((1 + u)^2 / (1 - u) - 1) < fl(n / d) * 2^-51 (3u + O(u^2)).
+// (The two-resource form adds the rounding of its sum on either side, 2^-50 in all; its constants below were chosen with that in hand.)
+//   pruning bound (eval): a pair is skipped when x < thr = tf * (1 - 2^-40), tf the lane's worst kept fitness.  Then fl(n / d) <= x (1 + 2^-51)
+//     < tf (1 - 2^-40) (1 + 2^-51) < tf: the exact fitness could not have entered the list.  Towards good-enough: fl(n / d) > ge implies
+//     x >= fl(n / d) (1 - 2^-51) > ge (1 - 2^-40) = ge_lo for ge >= 0, so a pair that clears the threshold is never skipped.
+//   guard band (resolve, general path): two fitness values whose approximations differ by more than a factor 1 -+ 2^-38 are ordered as their
+//     approximations are, since each lies within 2^-51 relative of its own exact value and 2 * 2^-51 < 2^-38.
+//   fp32 image (resolve, fast path): kf = fl32(x) for 2^-100 < x <= 1, round to nearest: monotone, kf = x (1 + d), |d| <= 2^-24.
+//     "one touched offer clearly ahead": mx = max kf is lane w's, and every other candidate q has kf_q < fl32(mx (1 - 2^-20))
+//     <= mx (1 - 2^-20) (1 + 2^-24).  Then x_q <= kf_q / (1 - 2^-24) < x_w (1 - 2^-20) (1 + 2^-24)^2 / (1 - 2^-24) < x_w (1 - 2^-21), and with
+//     each x within 2^-51 relative of its exact value: fl(n_q / d_q) <= x_q (1 + 2^-51) < x_w (1 - 2^-21) (1 + 2^-51) < x_w (1 - 2^-51)
+//     <= fl(n_w / d_w), strictly.  All it asks of the approximation is 2 * 2^-51 < 2^-21.  w against the best untouched entry (exact under
+//     S) goes through the 2^-38 band above, in fp64.
+//     good-enough, first look: ge_near_f = fl32(ge (1 - 2^-30)).  Rounding is monotone, so kf < ge_near_f implies x < ge (1 - 2^-30), hence
+//     x (1 + 2^-38) < ge: the lane is neither "above" nor "maybe above" in the fp64 tests that a nearer lane gets (x (1 - 2^-38) > ge
+//     implies fl(n / d) >= x (1 - 2^-51) > ge; x (1 + 2^-38) <= ge implies fl(n / d) <= x (1 + 2^-51) <= ge by the same margin).
+// The one-resource error (2^-51) is below the two-resource one (2^-50), so the same 2^-40 / 2^-38 / 2^-20 / 2^-30 bands hold, each by the
+// inequality written out above for one term.  One-resource fitness values tie far more often than two-resource ones (every offer of a
+// pool of equal machines filled alike); a tie is inside every band and goes to the exact divisions, as any near-tie does.
+static __device__ __forceinline__ void fitness_terms(unsigned fm, double& a1, double& a2) {
+  if (fm != 0u) {  // (uniform over the pool)
+    if (fm == 1u) a2 = a1;
+    else a1 = a2;
+  }
 }
 
 template <int N>
@@ -696,6 +728,7 @@ static __device__ __forceinline__ void eval_scan_offers(EvalLane& E, EvalWaveLds
   if (trp && lane == 0) trp[3] = cook_ticks();
 #endif
   unsigned long long feasm = 0ull, gem = 0ull;  // gem: bit vi = the fitness on offer v0 + vi exceeds good-enough
+  const unsigned fm = wave_uniform_u32(in.fitness);
   for (unsigned long long m = live; m != 0ull;) {  // wave-uniform
     const unsigned vi = (unsigned)__ffsll((unsigned long long)m) - 1u;
     m &= m - 1ull;
@@ -718,12 +751,13 @@ static __device__ __forceinline__ void eval_scan_offers(EvalLane& E, EvalWaveLds
     }
     feasm |= feas ? 1ull << vi : 0ull;
     if (feas) {
-      const double t1 = (a.rc + ac + j.c) * a.inv_dc, t2 = (a.rm + am + j.m) * a.inv_dm;
+      double t1 = (a.rc + ac + j.c) * a.inv_dc, t2 = (a.rm + am + j.m) * a.inv_dm;
+      fitness_terms(fm, t1, t2);  // (a one-resource packer: ub is that resource's term; the bound's derivation is at fitness_terms)
       const double ub = (t1 + t2) * 0.5;
       bool prune = E.ti[MV_L - 1] >= 0 && t1 >= 0.0 && t2 >= 0.0 && ub < E.thr;
       if (GE && E.use_ge && !(ub < E.ge_lo)) prune = false;  // (it may clear the threshold: the exact value decides)
       if (!prune) {
-        const double fit = fitness_of(a, ac, am, j.c, j.m);
+        const double fit = fitness_of(fm, a, ac, am, j.c, j.m);
         if (!(fit > 0.0)) {
           E.c4 += 1u;
         } else {
@@ -1468,6 +1502,7 @@ static __device__ void resolve_round(char* lds, MatchState st, const V2Buf& vb) 
   const unsigned nwin = wend - head;
   const double good_enough = wave_uniform_f64(vb.in_dev->good_enough);
   const bool use_ge = GE && good_enough < 1.0;
+  const unsigned fit_mode = wave_uniform_u32(vb.in_dev->fitness);  // 0 cpuMemBinPacker, 1 / 2 the one-resource packers (fitness_of)
   const uint32_t* const j_index = wave_uniform_ptr(vb.in_dev->j_index);
   // dead lanes are given away (MV_RETIRE_CAP) unless jobs of the call move ports / named scalars (their per-lane snapshots would go with the lane)
   // ... and unless the previous round used few of its lanes: a round that may touch MV_TMAX offers must WALK every unmatched job whose
@@ -1790,7 +1825,8 @@ static __device__ void resolve_round(char* lds, MatchState st, const V2Buf& vb) 
         }
       }
       auto publish_member = [&](int w_offer, unsigned w_host) { publish_group_member(ghits, gslot, g, k, w_offer, w_host); };
-      const double a1 = (t_basec + c) * t_invc, a2 = (t_basem + m) * t_invm;
+      double a1 = (t_basec + c) * t_invc, a2 = (t_basem + m) * t_invm;
+      fitness_terms(fit_mode, a1, a2);  // (a one-resource packer: fa is that resource's term, exactly; the fp32 margins' derivation is at fitness_terms)
       const double fa = (a1 + a2) * 0.5;
       const bool cand = res_ok && con_ok;
       // fp32 image of the approximate fitness: monotone in fa; a candidate whose approximation cannot be trusted for ordering
@@ -2016,7 +2052,8 @@ static __device__ void resolve_round(char* lds, MatchState st, const V2Buf& vb) 
       bool con_ok = ((t_col >> bl) & 1ull) != 0 && t_acount < t_slack && gok;
       if (job_gpu && t_k8s && t_run + t_acount != 0) con_ok = false;
       const double nc_ = t_basec + c, nm_ = t_basem + m;  // (rc + ac) + c, (rm + am) + m
-      const double a1 = nc_ * t_invc, a2 = nm_ * t_invm;
+      double a1 = nc_ * t_invc, a2 = nm_ * t_invm;
+      fitness_terms(fit_mode, a1, a2);
       const double fa = (a1 + a2) * 0.5;
       const bool cand = res_ok && con_ok;
       res_ok_g = res_ok, con_ok_g = con_ok, nc_g = nc_, nm_g = nm_;
@@ -2084,7 +2121,7 @@ static __device__ void resolve_round(char* lds, MatchState st, const V2Buf& vb) 
             } else if (!con_ok) {
               pe_bits = 2u;
             } else {
-              pe_fit = (nc_ / (t_oc + t_rc) + nm_ / (t_om + t_rm)) / 2.0;
+              pe_fit = fitness_calc(fit_mode, nc_, t_oc + t_rc, nm_, t_om + t_rm);
               if (!(pe_fit > 0.0)) pe_bits = 4u;
             }
           }
@@ -2267,7 +2304,7 @@ static __device__ void resolve_round(char* lds, MatchState st, const V2Buf& vb) 
           } else if (!con_ok_g) {
             pe_bits = 2u;
           } else {
-            pe_fit = (nc_g / (t_oc + t_rc) + nm_g / (t_om + t_rm)) / 2.0;
+            pe_fit = fitness_calc(fit_mode, nc_g, t_oc + t_rc, nm_g, t_om + t_rm);
             if (!(pe_fit > 0.0)) pe_bits = 4u;
           }
         }
@@ -2302,7 +2339,7 @@ static __device__ void resolve_round(char* lds, MatchState st, const V2Buf& vb) 
             if (!ok) {
               p0 = 2u;
             } else {
-              const double f0 = ((t_rc + ac0 + c) / (t_oc + t_rc) + (t_rm + am0 + m) / (t_om + t_rm)) / 2.0;
+              const double f0 = fitness_calc(fit_mode, t_rc + ac0 + c, t_oc + t_rc, t_rm + am0 + m, t_om + t_rm);
               if (!(f0 > 0.0)) p0 = 4u;
             }
           }

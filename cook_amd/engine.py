@@ -75,6 +75,9 @@ class Engine:
         h = C.c_void_p()
         rc = self._lib.cook_engine_create(C.byref(self.params), int(device), C.byref(h))
         if rc != 0 or not h:
+            why = self._lib.cook_last_error(None).decode()  # (the thread's last refused create; "null engine" when the params were not the reason)
+            if why != "null engine":
+                raise CookError(rc, f"cook_engine_create: {why}")
             raise CookError(rc, "cook_engine_create failed (no visible MI355X / HIP runtime error); "
                                 "cook_amd has no CPU fallback")
         self._h = h
@@ -562,7 +565,7 @@ class Engine:
                 "_12", "_13", "_14", "_15", "trunc_lists", "served_mode", "served_pools", "serve_iterations", "serve_empty_iterations",
                 "serve_pool_windows", "serve_latch_wait_us", "served_fell_back", "serve_streams", "guard_hits", "update_us", "update_sync_us", "update_allocs", "update_slowest_phase", "update_slowest_phase_us", "queue_advance_us",
                 "rank_batch_pools", "rank_batch_launches", "rank_batch_grouped_launches", "rank_batch_single_ops", "rank_batch_syncs",
-                "placement_form", "classfit_refused", "_39", "cf_walked", "cf_matched", "cf_overlay_wins", "cf_opened", "cf_opened_full", "cf_gpu_places", "cf_epochs",
+                "placement_form", "classfit_refused", "spreader_serial_calls", "cf_walked", "cf_matched", "cf_overlay_wins", "cf_opened", "cf_opened_full", "cf_gpu_places", "cf_epochs",
                 "cf_scans", "cf_exact_turns", "cf_retightened", "_50", "cf_batches", "cf_dead_lanes", "cf_ticks", "cf_ticks_prologue", "cf_ticks_epochs", "cf_ticks_books",
                 "cf_spins", "cf_ticks_walk", "cf_ticks_phase1", "cf_rewinds", "cf_flips", "cf_hwid_decider", "cf_hwid_books")
         return {k: int(x) for k, x in zip(keys, out[:max(0, n)]) if not k.startswith("_")}

@@ -30,7 +30,7 @@ CSV_HEADERS = ["job_id", "instance_id", "group_id", "submit_time_ms", "mesos_sta
 
 # zz_simulator.clj:73-78 default-rebalancer-config, :80-87 default-schedulers-config, :371-375 simulate's defaults
 DEFAULTS = dict(cycle_step_ms=30000, time_ms_between_rebalancing=30 * 60 * 1000, max_considerable=2000, scaleback=0.95,
-                floor_iterations_before_reset=1000, good_enough_fitness=1.0, safe_dru_threshold=1.0, min_dru_diff=0.5,
+                floor_iterations_before_reset=1000, good_enough_fitness=1.0, fitness=0, safe_dru_threshold=1.0, min_dru_diff=0.5,
                 max_preemption=100, default_share=dict(mem=4000.0, cpus=4.0, gpus=1.0), max_retries_default=5)
 
 
@@ -72,6 +72,8 @@ def config_from_edn_keys(cfg: dict) -> dict:
         out["max_considerable"] = int(fz["fenzo-max-jobs-considered"])
     if "good-enough-fitness" in fz:
         out["good_enough_fitness"] = float(fz["good-enough-fitness"])
+    if "fenzo-fitness-calculator" in fz:  # config.clj:108; a number 0..5 or the calculator's name (cook_params.fitness)
+        out["fitness"] = A.fitness_value(fz["fenzo-fitness-calculator"])
     return out
 
 
@@ -144,7 +146,7 @@ class Simulator:
         self.floor_iterations = 0
         self.cycles = 0
         self.log: List[dict] = []     # per cycle: what was submitted / completed / matched / preempted
-        self.params = A.default_params(good_enough_fitness=self.cfg["good_enough_fitness"])
+        self.params = A.default_params(good_enough_fitness=self.cfg["good_enough_fitness"], fitness=self.cfg["fitness"])
 
     # ---- tables -> SoA -----------------------------------------------------------------------------------------------------
     def _users(self) -> A.Users:

@@ -61,8 +61,27 @@ typedef struct cook_params {
                                   chain), 2 window rounds (eval / merge / resolve launches), 3 class-ordered best fit (one workgroup per pool,
                                   no evaluation launches) where the call's numbers and constraints allow it, else as 2.
                                   Other values: COOK_E_INVALID.  Identical results */
-  int32_t reserved;
+  int32_t fitness;             /* :fenzo-fitness-calculator of the pool (config.clj:108 default cpuMemBinPacker; docs/configuration.adoc:263-264).
+                                  With cf = (run_cpus + assigned_cpus + job.cpus) / (offer.cpus + run_cpus) and mf the same over mem:
+                                  Fenzo 0.10.0's own BinPackingFitnessCalculators: 0 = cpuMemBinPacker (cf + mf) / 2.0, 1 = cpuBinPacker cf,
+                                  2 = memoryBinPacker mf; their spreading counterparts: 3 = cpuMemSpreader ((1.0 - cf) + (1.0 - mf)) / 2.0,
+                                  4 = cpuSpreader 1.0 - cf, 5 = memorySpreader 1.0 - mf.  The spreaders' arithmetic (the operations and their
+                                  order, as written here) is oracle-defined, as the tie order between offers already is: Fenzo's source is
+                                  not part of the reference tree.  A fitness that is not > 0.0 is a failure under every calculator (a spreader
+                                  refuses the offer a job would fill to the brim); winner, ties and good-enough as under cook_match below.
+                                  match_algo 3 / the engine's own choice of it serve fitness 0 only (else window rounds); the spreaders are
+                                  placed by the serial sweep whatever match_algo says (cook_match_stats_ex [39] counts those calls).
+                                  networkBinPacker / cpuMemNetworkBinPacker: not offered.
+                                  Other values: COOK_E_INVALID from cook_engine_create and cook_engine_set_params.  (This field was `reserved`,
+                                  always 0, before: the layout and COOK_ABI_VERSION are unchanged.) */
 } cook_params;
+#define COOK_FITNESS_CPU_MEM_BIN_PACKER 0
+#define COOK_FITNESS_CPU_BIN_PACKER 1
+#define COOK_FITNESS_MEMORY_BIN_PACKER 2
+#define COOK_FITNESS_CPU_MEM_SPREADER 3
+#define COOK_FITNESS_CPU_SPREADER 4
+#define COOK_FITNESS_MEMORY_SPREADER 5
+#define COOK_FITNESS_N 6
 
 /* ---- resource 4-vector used for quotas and usage: {count, cpus, mem, gpus} (tools.clj:883-889) ---------- */
 typedef struct cook_usage {
@@ -252,6 +271,8 @@ typedef struct cook_preemption { /* one preemption decision (rebalancer.clj:384-
 int cook_engine_create(const cook_params* params, int device_id, cook_engine** out);
 void cook_engine_destroy(cook_engine* e);
 int cook_engine_set_params(cook_engine* e, const cook_params* params);
+/* e == NULL: why the calling thread's last cook_engine_create refused its params; "null engine" when it did not (a create that
+ * failed for a device reason included: its code is all it reports) */
 const char* cook_last_error(const cook_engine* e);
 const char* cook_version(void);
 /* Layout version of the structs and buffer sizes of this header (cook_jobs / cook_offers / cook_offer_params / COOK_WHY_SLOTS changed
@@ -904,7 +925,8 @@ int cook_match_stats(cook_engine* e, uint32_t out[16]);
    hosts, unique group, gpu}, 4 ports / named scalars, 8 balanced / attribute-equals groups or more than 16 pending members of a group, 16 gpu maps with
    several entries / max-tasks-per-host / reserved hosts / two offers of one host / attribute values >= 256, 32 too many classes, gpu kinds or offers
    for one workgroup's LDS, 64 job cpus values outside the 8 levels, 128 a job asking for nothing, 0x10000 good-enough-fitness < 1, COOK_CLASSFIT=0 or
-   offers built on the device), [39] reserved (0); [40..59] class-ordered best fit, the last match: jobs visited, matched, of them on an offer the call
+   offers built on the device, 0x20000 a cook_params.fitness other than 0), [39] matches of this engine that match_algo 0 / 2 / 3 would have placed in window rounds and
+   the serial sweep placed because the pool's fitness is a spreader (cook_params.fitness 3..5), since the engine was created; [40..59] class-ordered best fit, the last match: jobs visited, matched, of them on an offer the call
    had placed on before (overlay lane), offers opened, of them full at once, placements on gpu hosts, epochs, chunk scans, exact turns (several offers
    within 2^-37 of the best: the literal fitness decided), summary re-computations, [50] reserved, batches of 64 jobs, overlay lanes dropped full,
    [53..56] 100 MHz ticks: the launch, its prologue, the epochs' merges, the bookkeeper's batch pre-checks; [57..63] reserved (0) */
