@@ -399,6 +399,38 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueue(JNIEnv* env, jclass c,
   if (bad) return COOK_E_INVALID;
   return defer ? cook_cycle_run_queue_rank(H(h), &s, (uint32_t)num_considerable) : cook_cycle_run_queue(H(h), &s, (uint32_t)num_considerable);
 }
+/* cycleRunQueue with the carry (cook_cycle_run_queue_carry; defer != 0: cook_cycle_run_queue_carry_multi for this one pool, the placement
+ * then runs in cycleMatchMulti): carry_offers / carry_usage = 1 move the last cycle's kept placements into the staged offers (then offers
+ * must be null) / the staged user state on the device; tokens_left: direct buffer of n_users int64 that replaces the staged token counts,
+ * or null (tokens staged: one is spent per kept job). */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueueCarry(JNIEnv* env, jclass c, jlong h, jint num_considerable, jint remove_mode,
+                                                               jint n_last_offers, jobject offer_skipped, jint m, jobject offer_dims,
+                                                               jobjectArray offers, jint n_groups, jobjectArray groups, jint carry_offers,
+                                                               jint carry_usage, jint n_users, jobject tokens_left, jint defer) {
+  int bad = 0;
+  cook_offers o = offers_of(env, m, dims_of(env, offer_dims, &bad), offers, &bad);
+  cook_groups g = groups_of(env, n_groups, groups, &bad);
+  cook_queue_step s;
+  cook_queue_carry cy;
+  (void)c;
+  s.offer_skipped = BUFN(const uint8_t, offer_skipped, n_last_offers > 0 ? n_last_offers : 0);
+  s.remove_mode = (uint32_t)remove_mode;
+  s.n_offer_skipped = (uint32_t)(n_last_offers > 0 ? n_last_offers : 0);
+  s.offers = offers ? &o : 0;
+  s.groups = groups ? &g : 0;
+  cy.offers = (uint32_t)carry_offers;
+  cy.usage = (uint32_t)carry_usage;
+  cy.tokens_left = BUFN(const int64_t, tokens_left, n_users > 0 ? n_users : 0);
+  if (bad) return COOK_E_INVALID;
+  if (defer) {
+    cook_engine* e = H(h);
+    const cook_queue_step* sp = &s;
+    const cook_queue_carry* cp = &cy;
+    const uint32_t k = (uint32_t)num_considerable;
+    return cook_cycle_run_queue_carry_multi(&e, 1, &sp, &cp, &k);
+  }
+  return cook_cycle_run_queue_carry(H(h), &s, &cy, (uint32_t)num_considerable);
+}
 /* the running usage of n staged engines of one device in ONE call (cook_rank_pool_usage_multi): usage_out = direct buffer of n cook_usage */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_rankPoolUsageMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n, jobject usage_out) {
   cook_engine* es[64];

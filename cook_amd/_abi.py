@@ -130,6 +130,22 @@ class CookQueueStep(C.Structure):  # cook_cycle_run_queue*
                 ("groups", C.POINTER(CookGroups))]
 
 
+class CookQueueCarry(C.Structure):  # cook_cycle_run_queue_carry*
+    _fields_ = [("offers", C.c_uint32), ("usage", C.c_uint32), ("tokens_left", _i64p)]
+
+
+class QueueCarry:
+    """What a queue cycle carries from the last cycle's kept placements (cook_queue_carry): offers -> into the staged offers, usage ->
+    into the staged user state; tokens_left [users] replaces the staged token counts (None with tokens staged: one is spent per kept job)."""
+
+    def __init__(self, offers=False, usage=False, tokens_left=None):
+        self.offers, self.usage = int(offers), int(usage)
+        self.tokens_left = _arr(tokens_left, np.int64)
+
+    def as_struct(self) -> CookQueueCarry:
+        return CookQueueCarry(self.offers, self.usage, _ptr(self.tokens_left, _i64p))
+
+
 class CookRebalanceParams(C.Structure):
     _fields_ = [("safe_dru_threshold", C.c_double), ("min_dru_diff", C.c_double),
                 ("max_preemption", C.c_int32), ("reserved", C.c_int32)]

@@ -60,6 +60,7 @@ struct SweepBufs;      // sweep_host.hpp
 struct UnschedBufs;    // unscheduled_host.hpp
 struct UsageBufs;      // usage_host.hpp
 struct QueueBufs;      // queue_host.hpp
+struct CarryBufs;      // carry_host.hpp
 
 }  // namespace
 
@@ -190,6 +191,7 @@ struct cook_engine {
   std::vector<uint32_t> h_g_key;
   std::vector<int32_t> h_g_min;
   std::unique_ptr<QueueBufs> qb;               // (allocated on first use)
+  std::unique_ptr<CarryBufs> cyb;              // the carry of a queue cycle (allocated on first use)
 
   // ---- rebalancer state (allocated on first use) ----
   std::unique_ptr<RebalBufs> rb;
@@ -289,6 +291,7 @@ static std::atomic<int> g_engines_on_device[64];
 #include "cycle_update.hpp"
 #include "user_stats_host.hpp"
 #include "autoscale_host.hpp"
+#include "carry_host.hpp"      // a queue cycle's carry: needs the staged user state (considerable_host.hpp)
 #include "queue_host.hpp"
 #include "sweep_host.hpp"
 #include "unscheduled_host.hpp"
@@ -568,6 +571,27 @@ int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_que
       [&](uint32_t i) {
         cook_engine* e = engines[i];
         const unsigned K = cycle_queue_part(e, steps ? steps[i] : nullptr, num_considerable[i]);
+        cycle_match(e, K, /*defer=*/true);
+      },
+      /*rank_part=*/true);
+}
+// ... with the carry (carry_host.hpp): the kept placements into the staged offers and the staged user state, inside the advance
+int cook_cycle_run_queue_carry(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, uint32_t num_considerable) {
+  return cycle_run_one(e, [&] { return cycle_queue_part(e, step, num_considerable, carry); }, /*defer=*/false);
+}
+int cook_cycle_run_queue_carry_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
+                                     const uint32_t* num_considerable) {
+  if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
+  auto step = [&](uint32_t i) { return steps ? steps[i] : nullptr; };
+  auto carry = [&](uint32_t i) { return carries ? carries[i] : nullptr; };
+  return run_pools_batched(
+      engines, n,
+      [&](uint32_t i) {
+        return cycle_run_one(engines[i], [&] { return cycle_queue_part(engines[i], step(i), num_considerable[i], carry(i)); }, /*defer=*/true);
+      },
+      [&](uint32_t i) {
+        cook_engine* e = engines[i];
+        const unsigned K = cycle_queue_part(e, step(i), num_considerable[i], carry(i));
         cycle_match(e, K, /*defer=*/true);
       },
       /*rank_part=*/true);

@@ -3,7 +3,7 @@
 // The advance enqueues everything over the OLD queue length (mark, scan, compact, the group fold, then the uploads of the step's offers
 // and groups, which the stream orders behind the kernels that still read the old offers) and reads two words back — the number of
 // jobs removed and of cotasks folded in — in ONE synchronisation; the new queue length is the only value the host needs before it
-// sizes the considerable filters' launches.
+// sizes the considerable filters' launches.  A carry (carry_host.hpp) is enqueued in the same place, over the same old rows.
 #pragma once
 #include "queue_kernels.hpp"
 
@@ -26,10 +26,11 @@ void queue_reset_groups(cook_engine* e) {
 }
 
 // everything that can refuse a step, before anything changes
-void queue_check_step(cook_engine* e, const cook_queue_step* s) {
+void queue_check_step(cook_engine* e, const cook_queue_step* s, const cook_queue_carry* c = nullptr) {
   if (!e->cycle_staged || !e->q_valid || !e->rank_done || !e->match_done)
     e->fail(COOK_E_STATE, "cook_cycle_run_queue needs a completed cycle (cook_cycle_run, cook_cycle_run_rank* + cook_cycle_match_multi or a queue "
                           "cycle) with no cook_cycle_stage / cook_cycle_update / cook_rank* / cook_considerable / cook_match_stage since");
+  carry_check(e, s, c);
   if (!s) return;
   if (s->remove_mode > 1u) e->fail(COOK_E_INVALID, "cook_queue_step.remove_mode: 0 = the kept matches, 1 = every considered job");
   if (s->offer_skipped && s->n_offer_skipped != e->M)
@@ -56,8 +57,8 @@ void queue_check_step(cook_engine* e, const cook_queue_step* s) {
 }
 
 // steps 1-3 of a queue cycle (cookmatch.h): the last cycle's jobs leave the queue, their cotasks join the groups, fresh offers
-void queue_advance(cook_engine* e, const cook_queue_step* s) {
-  queue_check_step(e, s);
+void queue_advance(cook_engine* e, const cook_queue_step* s, const cook_queue_carry* c = nullptr) {
+  queue_check_step(e, s, c);
   const auto t_call = std::chrono::steady_clock::now();
   e->q_valid = false;  // from here on the queue is being edited: a call that fails below leaves no standing queue (cycle_take_part sets it again)
   QueueBufs& b = bufs(e->qb);
@@ -78,6 +79,7 @@ void queue_advance(cook_engine* e, const cook_queue_step* s) {
     const uint32_t* j_index = e->j_index.ptr();
     KM<q_mark_removed, 256>(e, "q_mark_removed", div_up(k, 256), e->q_last_pos, j2o, k, n, skipped, (unsigned)(s && s->remove_mode == 1u), j_index,
         in.j_group, G, (unsigned)fold, removed, add_cnt, cnt);
+    if (c) carry_enqueue(e, c, skipped, k);  // (the carried offer columns are the staged ones from here: the fold below reads hosts and attributes, which stay)
     // ---- the queue: stable compaction, back into the resident buffer ----------------------------------------------------------------
     b.scan.ensure(n);
     uint32_t* tmp = b.ranked_tmp.ensure(n);
@@ -125,7 +127,9 @@ void queue_advance(cook_engine* e, const cook_queue_step* s) {
     e->cf_group_run_total = nr;
   }
   if (s && s->offers) match_stage_offers(e, s->offers, false);
-  if (advance || (s && (s->groups || s->offers))) sync(e);  // (the host arrays of the step are read until here)
+  carry_tokens(e, c);
+  if (advance || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
+  if (c) carry_finish(e);
   if (advance) {
     unsigned h[2] = {0, 0};
     std::memcpy(h, e->h_scratch, 8);

@@ -304,6 +304,15 @@ class Engine:
     def cycle_run_queue_rank(self, num_considerable: int, **step):
         self.cycle_run_queue(num_considerable, defer=True, **step)
 
+    def cycle_run_queue_carry(self, num_considerable: int, carry: Optional[A.QueueCarry] = None, **step):
+        """cycle_run_queue with the carry (cook_cycle_run_queue_carry): before the last cycle's jobs leave the queue, its kept placements
+        are subtracted from the staged offers (carry.offers; then no `offers` in the step) and added to the staged user state
+        (carry.usage), on the device, in considered order.  carry None: exactly cycle_run_queue."""
+        st, keep = self._queue_step(**step)
+        cs = carry.as_struct() if carry is not None else None
+        self._chk(self._lib.cook_cycle_run_queue_carry(self._h, C.byref(st), C.byref(cs) if cs is not None else None, int(num_considerable)))
+        del keep
+
     def cycle_fetch(self, out=None):
         """-> (ranked task indices, job_to_offer by rank position, head matched).  `out` = (u32 buffer, i32 buffer) to fetch into
         (e.g. page-locked arrays of a PinnedArena, each with room for every pending task): views of them are returned."""
@@ -794,6 +803,27 @@ def cycle_run_queue_multi(engines: Sequence[Engine], num_considerable, steps: Op
             if e._lib.cook_last_error(e._h):
                 e._chk(rc)
         engines[0]._chk(rc)
+
+
+def cycle_run_queue_carry_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None,
+                                carries: Optional[Sequence[Optional[A.QueueCarry]]] = None):
+    """cycle_run_queue_multi with one carry per engine (cook_cycle_run_queue_carry_multi; None: no carry for that pool); cycle_match_multi
+    places them.  A pool whose step or carry is refused stays as it was and raises after the others have gone on."""
+    if not engines:
+        return
+    n = len(engines)
+    arr = (C.c_void_p * n)(*[e._h for e in engines])
+    ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
+    assert len(ks) == n
+    ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
+    steps = list(steps) if steps is not None else [None] * n
+    carries = list(carries) if carries is not None else [None] * n
+    assert len(steps) == n and len(carries) == n
+    built = [e._queue_step(**(s or {})) for e, s in zip(engines, steps)]
+    cs = [c.as_struct() if c is not None else None for c in carries]
+    ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
+    cptrs = (C.c_void_p * n)(*[C.addressof(c) if c is not None else None for c in cs])
+    _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_carry_multi(arr, n, ptrs, cptrs, ks))
 
 
 def cycle_match_multi(engines: Sequence[Engine]):

@@ -498,10 +498,11 @@ int cook_cycle_fetch(cook_engine* e, uint32_t* ranked_pending_idx, uint32_t* n_r
  *     what the reference sees once the launched instances are in the DB (constraints.clj:553-566).  The order inside a group's list
  *     is not defined (unique, balanced and attribute-equals read it as a set / as counts).
  *  3. Offers.  offers non-NULL replaces the staged offers wholesale (as cook_cycle_delta.offers).  NULL leaves them as they are, which
- *     only describes the cluster when step 1 removed nothing: placements are NOT subtracted from the offers.
+ *     only describes the cluster when step 1 removed nothing: these entry points do not subtract placements from the offers
+ *     (cook_cycle_run_queue_carry below does, on the device).
  *  4. Considerable -> take num_considerable -> match over Q, exactly as a rank cycle does over the rank's output: the user state is
  *     whatever cook_cycle_set_considerable staged last (refresh usage and tokens between cycles with that call: it does not invalidate
- *     Q), the eligible mask follows the job rows, reserved hosts stay as staged, all placement forms apply unchanged.
+ *     Q; or let cook_cycle_run_queue_carry add the kept placements to the staged usage on the device), the eligible mask follows the job rows, reserved hosts stay as staged, all placement forms apply unchanged.
  * Afterwards cook_cycle_fetch / cook_cycle_fetch_considerable / cook_match_explain / cook_match_metrics / cook_cycle_autoscale describe
  * THIS cycle: ranked_pending_idx is the current Q (task indices, the index space of the rank), n_ranked its length, rank_pos positions
  * in it.  cook_user_stats / cook_unscheduled / cook_usage_breakdown keep describing the last RANK (they read the per-user order, which a
@@ -530,6 +531,44 @@ int cook_cycle_run_queue_rank(cook_engine* e, const cook_queue_step* step, uint3
  * engine's error that is not COOK_OK; a pool whose step was refused stays as it was, the others go on.  cook_cycle_match_multi accepts any
  * mix of engines prepared by a rank call and by a queue call. */
 int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const uint32_t* num_considerable);
+
+/* ---- THE CARRY: a queue cycle that moves the last cycle's kept placements into the staged offers and the staged user state ----------
+ * In the reference neither is the caller's arithmetic: Fenzo keeps its leases and per-host running totals across scheduleOnce calls
+ * (getTaskAssigner, scheduler.clj:877-881), a host's remainder returns as a smaller offer, and generate-user-usage-map (:711-727) sees
+ * the launched jobs as running.  The carry runs inside step 1 of a queue cycle, over the OLD offers and the OLD considered jobs, before
+ * they leave the queue, with no synchronisation of its own.  A KEPT placement is job_to_offer >= 0 with the offer not skipped: the
+ * predicate of step 1 and of the groups' fold.  remove_mode does not change what is carried; unmatched considered jobs carry nothing.
+ * Order rule (oracle-defined, like the winner rule): every sum runs over the kept placements in CONSIDERED order (= rank order), the
+ * order in which the placement itself accumulated "assigned this call"; strictly left to right, x = x + r one job after another, fp64,
+ * no re-association.  The result does not depend on the placement form: it is computed from job_to_offer alone.
+ *  offers = 1.  For offer v, with A_c, A_m, A_n, A_ports, A_s[s] the left-to-right sums (each from 0) of its kept jobs' cpus, mem,
+ *     count, positive port counts and non-NaN named scalars: cpus -= A_c, mem -= A_m, run_cpus += A_c, run_mem += A_m, run_count += A_n,
+ *     num_tasks += A_n, ports -= A_ports, scalars[s] -= A_s[s].  For a k8s offer, job after job in considered order: a kept job with
+ *     gpus > 0 subtracts its gpus from the gpu_count slot whose model equals the job's; a kept job with disk_request >= 0 subtracts it
+ *     from the disk_space slot of its disk_type; no such slot: nothing changes.  run_cpus / run_mem / run_count / num_tasks / ports that
+ *     were staged as NULL (all 0) come into existence first.  A named scalar the offers have no column for stays absent (total 0).
+ *     max_tasks, attributes, host, location, host_start_s, k8s and the model / type ids are untouched.  The carried offers ARE the staged
+ *     offers from then on, exactly as a wholesale replacement would be, through later cycles and ranks until replaced.  The engine
+ *     writes a copy of its own: neither the caller's arrays nor the rows of cook_offers_run (cook_cycle_stage_built_offers) are written.
+ *  usage = 1.  For user u the sums of its kept jobs in considered order are added to the staged arrays: usage_count[u] += count,
+ *     usage_cpus[u] / usage_mem[u] / usage_gpus[u] += the left-to-right sums (each from 0) of cpus / mem / gpus.  With pool_usage_given
+ *     the pool usage grows by the same four quantities summed over ALL kept jobs in considered order; otherwise the engine keeps
+ *     summing the users itself.  Tokens: tokens_left non-NULL replaces the staged counts and nothing is spent (the host has done both);
+ *     tokens_left NULL with tokens staged: tokens[u] -= kept jobs of u (the spend; the refill with time stays with the host).
+ *     tokens_left is honoured whatever the two flags say.  Quotas, enforce_rate_limit and the eligible mask stay as staged.
+ * Refused before anything changes: offers = 1 together with step->offers, a flag above 1, tokens_left while the staged state has no
+ * limiter (COOK_E_INVALID); usage = 1 or tokens_left without a staged user state (COOK_E_STATE).
+ * Not carried, the host's to tell: finished tasks and new hosts (step->offers / cook_cycle_update), the time-based token refill
+ * (tokens_left).  carry NULL, or both flags 0 and no tokens: exactly cook_cycle_run_queue / _multi. */
+typedef struct cook_queue_carry {
+  uint32_t offers;            /* 1: carry the kept placements into the staged offers (then step->offers must be NULL) */
+  uint32_t usage;             /* 1: carry them into the staged user state (needs cook_cycle_set_considerable staged)   */
+  const int64_t* tokens_left; /* optional [users]: replaces the staged token counts (the host's refill); NULL: see above */
+} cook_queue_carry;
+int cook_cycle_run_queue_carry(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, uint32_t num_considerable);
+/* as cook_cycle_run_queue_multi (then cook_cycle_match_multi); steps / carries NULL or an entry NULL: defaults */
+int cook_cycle_run_queue_carry_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps,
+                                     const cook_queue_carry* const* carries, const uint32_t* num_considerable);
 
 /* ---- REBALANCE: replaces init-state + the rebalance loop's decisions ---------------------------------------
  * (rebalancer.clj:222-266, 320-407, 270-309, 434-467; dru.clj:128-144).

@@ -9,7 +9,13 @@ tests/queue_cases.py (the engine's job_to_offer as given for the removal: the pl
 advance alone: the host's wall time in it, its one synchronisation included (cook_match_stats_ex [31], median over the timed cycles,
 summed over the pools), and the sum of its kernels from cook_kernel_timings in a profiled pass of its own.  One JSON line per
 configuration.
-    python scripts/bench_queue.py [--steps 50] [--warmup 5] [--k-all] [--out results/queue.json]"""
+The carry (cook_cycle_run_queue_carry*), --carry: two legs of the same content on the same build in the same process.
+Leg one is a queue cycle with offers = usage = 1 and no upload.  Leg two is a queue cycle whose host reads job_to_offer and the
+considered positions back and supplies the same next offers through step->offers and the same user state through
+cook_cycle_set_considerable (the host's own arithmetic between the two — here tests/carry_oracle.py, from leg one's results — is NOT
+timed: a JVM host would do it faster than Python does).  Episodes of one rank cycle and CARRY_CYCLES queue cycles from the same staged
+state, the queue cycles timed; both legs must place every job identically, cycle for cycle, or the run fails.
+    python scripts/bench_queue.py [--steps 50] [--warmup 5] [--k-all] [--carry | --carry-only] [--out results/queue.json]"""
 import argparse
 import copy
 import json
@@ -25,11 +31,14 @@ sys.path.insert(0, ROOT)
 
 from cook_amd import _abi as A  # noqa: E402
 from cook_amd import workload  # noqa: E402
-from cook_amd.engine import Engine, cycle_match_multi, cycle_run_queue_multi, cycle_run_rank_multi  # noqa: E402
+from cook_amd.engine import Engine, cycle_match_multi, cycle_run_queue_carry_multi, cycle_run_queue_multi, cycle_run_rank_multi  # noqa: E402
 from tests import autoscale_cases as AS  # noqa: E402
+from tests import carry_oracle as CO  # noqa: E402
 from tests import queue_cases as S  # noqa: E402
 
 Q_OFFERS = 120  # offers of a queue cycle: well below K, so that every cycle keeps matches and leaves considered jobs unmatched
+CARRY_CYCLES = 4  # queue cycles per episode of the carry legs (K = all: 1, the first cycle places whatever fits)
+CARRY = ("carry_keys", "carry_seg_bounds", "carry_fold_offers", "carry_fold_users", "carry_fold_pool")
 ADVANCE = ("q_mark_removed", "q_queue_scan", "q_compact_ranked", "q_group_scan", "q_fold_offsets", "q_fold_copy_old", "q_fold_append")
 
 
@@ -107,8 +116,107 @@ def run(name, pools, k, steps, warmup):
             "queue_len_first_last": [[int(len(g[0].Q)), int(len(g[-1].Q))] for g in got]}
 
 
+def run_carry(name, pools, k, steps, warmup):
+    """the two legs of the carry; -> one result row"""
+    params = A.default_params()
+    n = len(pools)
+    states = [AS.random_state(pl, 40 + i, tokens=False, pool_quota=False) for i, pl in enumerate(pools)]
+    ks = [k if k else pl.pending_jobs.n for pl in pools]
+    cyc = CARRY_CYCLES if k else 1
+    episodes = max(1, -(-(warmup + steps) // cyc))
+    both = A.QueueCarry(offers=True, usage=True)
+
+    def rank(engines):
+        if n == 1:
+            engines[0].cycle_run(ks[0])
+        else:
+            cycle_run_rank_multi(engines, ks)
+            cycle_match_multi(engines)
+
+    def episode(engines, step, record):
+        """restage the offers and the user state, rank, cyc queue cycles through step(c); -> their wall times"""
+        for e, pl, (st, el) in zip(engines, pools, states):
+            e.cycle_update(offers=pl.offers)
+            e.cycle_set_considerable(st, el)
+        rank(engines)
+        if record is not None:
+            record.append([S.fetch(e, False) for e in engines])
+        ts = []
+        for c in range(1, cyc + 1):
+            t0 = time.perf_counter()
+            step(engines, c)
+            ts.append(time.perf_counter() - t0)
+            if record is not None:
+                record.append([S.fetch(e, False) for e in engines])
+        return ts
+
+    def leg(step, want_launches=False):
+        engines = [Engine(params) for _ in pools]
+        try:
+            for e, pl in zip(engines, pools):
+                e.cycle_stage(pl.tasks, pl.users, pl.pending_jobs, pl.offers, pl.groups)
+            first, ts = [], []
+            for ep in range(episodes):
+                ts += episode(engines, step, first if ep == 0 else None)
+            launches = None
+            if want_launches:  # the advance's launches, counted in a profiled episode of its own
+                for e in engines:
+                    e.set_profiling(True)
+                episode(engines, step, None)
+                launches = round(sum(nl for e in engines for nm, (_, nl) in e.kernel_timings().items() if nm in ADVANCE + CARRY) / cyc / n, 1)
+            return first, ts[warmup:], launches
+        finally:
+            for e in engines:
+                e.close()
+
+    def step_carry(engines, c):
+        if n == 1:
+            engines[0].cycle_run_queue_carry(ks[0], both)
+        else:
+            cycle_run_queue_carry_multi(engines, ks, None, [both] * n)
+            cycle_match_multi(engines)
+
+    got1, t1, launches = leg(step_carry, want_launches=True)
+    # what the host of leg two supplies: the oracle's carry of leg one's own placements (untimed)
+    supply = [[None] * (cyc + 1) for _ in pools]
+    for i, (pl, (st, el)) in enumerate(zip(pools, states)):
+        offers, state = pl.offers, st
+        jq_of = np.cumsum(pl.tasks.pending) - 1
+        for c in range(1, cyc + 1):
+            g = got1[c - 1][i]
+            jobs = pl.pending_jobs.take(jq_of[g.Q[g.pos]])
+            hit = g.j2o >= 0
+            offers, state = CO.carry_offers(offers, jobs, g.j2o, hit), CO.carry_usage(state, jobs, hit, spend=False)
+            supply[i][c] = (offers, state, el)
+
+    def step_host(engines, c):
+        for i, e in enumerate(engines):  # the read-back a host needs before it can do the arithmetic
+            e.cycle_fetch()
+            e.cycle_fetch_considerable()
+            e.cycle_set_considerable(supply[i][c][1], supply[i][c][2])
+        if n == 1:
+            engines[0].cycle_run_queue(ks[0], offers=supply[0][c][0])
+        else:
+            cycle_run_queue_multi(engines, ks, [dict(offers=supply[i][c][0]) for i in range(n)])
+            cycle_match_multi(engines)
+
+    got2, t2, _ = leg(step_host)
+    for c, (a, b) in enumerate(zip(got1, got2)):
+        for i in range(n):
+            assert np.array_equal(a[i].Q, b[i].Q) and np.array_equal(a[i].pos, b[i].pos) and np.array_equal(a[i].j2o, b[i].j2o), \
+                f"{name}: the legs differ in cycle {c}, pool {i}"
+    kept = [[int((g[i].j2o >= 0).sum()) for g in got1] for i in range(n)]
+    assert all(x > 0 for row in kept for x in row[:-1]), "a timed cycle has no kept placement to carry"
+    cm, hm = median_ms(t1), median_ms(t2)
+    return {"config": name + ", carry", "pools": n, "K": k or "all", "timed_cycles": len(t1), "carry_cycle_ms": cm, "host_supplied_cycle_ms": hm,
+            "carry_over_host": round(cm / hm, 3), "advance_launches_per_pool_without_sort_passes": launches, "advance_syncs": 1,
+            "identical_placements": True, "kept_per_cycle": kept}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--carry", action="store_true", help="also the two legs of the carry")
+    ap.add_argument("--carry-only", action="store_true", help="only the two legs of the carry")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--k-all", action="store_true")
@@ -118,8 +226,12 @@ def main():
     c4 = [workload.make_pool(spec, p) for p in range(spec.pools)]
     rows = []
     for k in [1000] + ([0] if args.k_all else []):
-        rows.append(run("one C4 pool", c4[:1], k, args.steps, args.warmup))
-        rows.append(run("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
+        if not args.carry_only:
+            rows.append(run("one C4 pool", c4[:1], k, args.steps, args.warmup))
+            rows.append(run("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
+        if args.carry or args.carry_only:
+            rows.append(run_carry("one C4 pool", c4[:1], k, args.steps, args.warmup))
+            rows.append(run_carry("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
     for r in rows:
         print(json.dumps(r), flush=True)
     if args.out:

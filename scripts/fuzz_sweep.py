@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Seeded random sweep of the engine against the oracle (TEST TOOL): small random configurations of rank / cycle / match / explain /
-cycle update and of the rebalancer, both match_algo values, eval split caps, ports / named scalars, k8s gpu maps with several entries.
+cycle update and of the rebalancer, both match_algo values, eval split caps, ports / named scalars, k8s gpu maps with several entries;
+`--carry N`: queue cycles with and without the carry (cook_cycle_run_queue / cook_cycle_run_queue_carry) against tests/carry_oracle.py,
+from random draws of their own (the other legs' draws do not depend on N).
 `--emu` runs the SIMT-emulator build on the CPU, otherwise libcookmatch.so on the GPU.  Prints one line; exit 1 on the first
 difference (with the configuration that produced it)."""
 import argparse
@@ -20,6 +22,7 @@ def main():
     ap.add_argument("--rebalance", type=int, default=60, help="rebalancer configurations")
     ap.add_argument("--multi", type=int, default=0, help="multi-pool configurations (2-8 random pools through ONE cook_cycle_match_multi: served walkers with "
                                                           "1-3 serve streams, or lockstep launches; pools that disagree on good-enough / K)")
+    ap.add_argument("--carry", type=int, default=0, help="queue-cycle configurations: random pools, user states, skipped offers, remove modes, carry flags, token refills")
     ap.add_argument("--emu", action="store_true")
     ap.add_argument("--scale", type=float, default=1.0, help="size factor of the configurations")
     ap.add_argument("--algo", type=int, default=-1, help="force cook_params.match_algo (default: drawn per configuration)")
@@ -119,6 +122,43 @@ def main():
         except AssertionError as ex:
             print("FAIL rebalance", it, kw, str(ex)[:300])
             sys.exit(1)
+    crng = np.random.default_rng([args.seed, 0xCA22])  # its own stream: the legs above draw what they drew before this leg existed
+    for it in range(args.carry):
+        from tests import autoscale_cases as AS
+        from tests import carry_cases as K
+        from tests import carry_oracle as O
+        from tests import queue_cases as S
+        kw = dict(seed=int(crng.integers(1, 1 << 30)), n_pending=int(crng.integers(1, int(700 * sc))), n_running=int(crng.integers(0, int(150 * sc))),
+                  n_users=int(crng.integers(1, 30)), n_offers=int(crng.integers(1, int(120 * sc))), gpus=bool(crng.integers(0, 2)),
+                  constraints=bool(crng.integers(0, 2)), fractional=bool(crng.integers(0, 2)))
+        p = A.default_params(good_enough_fitness=float(crng.choice([1.0, 1.0, 0.8])), match_algo=int(crng.choice([0, 1, 2, 3])))
+        pool = synth.make_pool(**kw)
+        with_state = bool(crng.integers(0, 4) != 0)
+        st, el = AS.random_state(pool, int(crng.integers(1, 1 << 20)), fractional=kw["fractional"], tokens=bool(crng.integers(0, 2)),
+                                 enforce=bool(crng.integers(0, 2)), pool_quota=bool(crng.integers(0, 2))) if with_state else (None, None)
+        k = int(crng.integers(1, kw["n_pending"] + 1))
+        cycles = [O.cycle(k, state=st, eligible=el)]
+        for c in range(1, 5):
+            fresh = bool(crng.integers(0, 5) == 0)
+            cy = O.cycle(k, carry=bool(crng.integers(0, 5) != 0), carry_offers=bool(crng.integers(0, 4) != 0) and not fresh,
+                         carry_usage=with_state and bool(crng.integers(0, 4) != 0), remove_mode=int(crng.integers(0, 4) == 0),
+                         offers=S.fresh_offers(int(crng.integers(1, 1 << 30)), int(crng.integers(1, int(120 * sc))), gpus=kw["gpus"],
+                                               constraints=kw["constraints"]) if fresh else None)
+            cy.draw_skip, cy.draw_tokens = crng.random(), crng.random()
+            cycles.append(cy)
+        m_last = pool.offers.n  # offer_skipped describes the offers of the cycle before
+        for cy in cycles[1:]:
+            if cy.draw_skip < 0.4:
+                cy.offer_skipped = (crng.random(m_last) < 0.3).astype(np.uint8)
+            if cy.carry and with_state and st.tokens_left is not None and cy.draw_tokens < 0.3:
+                cy.tokens_left = crng.integers(0, 40, st.n).astype(np.int64)
+            if cy.offers is not None:
+                m_last = cy.offers.n
+        try:
+            S.compare(K.run_engine(make_engine, p, pool, cycles), O.oracle(p, pool, cycles), cycles)
+        except AssertionError as ex:
+            print("FAIL carry", it, kw, p.match_algo, p.good_enough_fitness, k, str(ex)[:300])
+            sys.exit(1)
     guard = ""
     if args.guard:
         import gc
@@ -130,7 +170,7 @@ def main():
             print(f"FAIL guard: {hits} writes outside a device buffer (COOK_GUARD lines on stderr)")
             sys.exit(1)
         guard = ", COOK_GUARD=1: no write outside a device buffer"
-    print(f"fuzz ok: {args.match} match / cycle configurations, {args.multi} multi-pool configurations, {args.rebalance} rebalancer configurations, seed {args.seed}, "
+    print(f"fuzz ok: {args.match} match / cycle configurations, {args.multi} multi-pool configurations, {args.rebalance} rebalancer configurations, {args.carry} queue-cycle configurations, seed {args.seed}, "
           f"{'emulator' if args.emu else 'gpu'}{guard}")
 
 
