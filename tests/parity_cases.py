@@ -154,14 +154,33 @@ def user_usage_parity(make_engine, pool: synth.Pool, n_users):
     return got
 
 
-def match_parity(make_engine, jobs, offers, groups, params, reserved=()):
+# classfit_refused (match_stats): why a call that asked for the class-ordered form kept the window rounds — the CF_X_* bits of classfit.hpp, and
+# CF_REFUSED_HOST where cf_setup's own checks (classfit_host.hpp) answered before any set-up launch
+CF_X_NUMBERS, CF_X_JOB_SLOW, CF_X_XRES, CF_X_GROUP, CF_X_OFFER, CF_X_SHAPE, CF_X_LEVELS, CF_X_ZERO = 1, 2, 4, 8, 16, 32, 64, 128
+CF_REFUSED_HOST = 0x10000
+
+
+def classfit_expect(algo, refused=0):
+    """the keyword arguments of match_parity that state how a match_algo 3 call must be placed: by the class-ordered form (refused = 0) or by
+    the window rounds with exactly this refusal word; nothing for the other forms"""
+    return dict(expect_form=0 if refused else 3, expect_refused=refused) if algo == 3 else {}
+
+
+def match_parity(make_engine, jobs, offers, groups, params, reserved=(), expect_form=None, expect_refused=None):
+    """expect_form / expect_refused: what match_stats() must say about HOW the call was placed (placement_form: 0 window rounds, 1 serial
+    sweep, 3 class-ordered best fit; classfit_refused: the CF_X_* word of classfit.hpp, CF_REFUSED_HOST for the host's pre-check)"""
     with make_engine(params) as e:
         j2o, fail, head = e.match(jobs, offers, groups, reserved)
+        stt = e.match_stats()
     o_j2o, o_fail, o_head = pyoracle.match(params, jobs, offers, groups, reserved)
     bad = np.nonzero(j2o != o_j2o)[0]
     assert len(bad) == 0, f"assignment differs first at job {bad[:5]}: {j2o[bad[:5]]} vs {o_j2o[bad[:5]]}"
     assert np.array_equal(fail, o_fail)
     assert head == o_head
+    if expect_form is not None:
+        assert stt["placement_form"] == expect_form, (stt["placement_form"], hex(stt["classfit_refused"]))
+    if expect_refused is not None:
+        assert stt["classfit_refused"] == expect_refused, (stt["placement_form"], hex(stt["classfit_refused"]))
     return j2o
 
 
@@ -460,35 +479,42 @@ def slow_constraint_case(seed, n, m):
     return jobs, offers, groups
 
 
-def multi_pool_parity(make_engine, pools, params, k, rank_batched=True):
+def multi_pool_parity(make_engine, pools, params, k, rank_batched=True, cycles=1, with_stats=False):
     """The rank part of every pool — ONE cook_cycle_run_rank_multi for all of them (rank_batched: the pools' flows side by side, the same
     kernel of several pools in one launch) or cook_cycle_run_rank per pool — + ONE cook_cycle_match_multi for all of them
-    == cook_cycle_run on each pool == oracle."""
+    == cook_cycle_run on each pool == oracle.  cycles: that many cycles on the resident inputs, each checked.  with_stats: -> (the last
+    cycle's results, per cycle every engine's match_stats() behind the match)."""
     from cook_amd.engine import cycle_match_multi, cycle_run_rank_multi
     engines = [make_engine(params) for _ in pools]
+    rounds, stats = [], []
     try:
         for e, pool in zip(engines, pools):
             e.cycle_stage(pool.tasks, pool.users, pool.pending_jobs, pool.offers, pool.groups)
-            if not rank_batched:
-                e.cycle_run_rank(k)
-        if rank_batched:
-            cycle_run_rank_multi(engines, k)
-            st = engines[0].match_stats()
-            assert st["rank_batch_pools"] == len(engines) or len(engines) == 1, st
-        cycle_match_multi(engines)
-        got = [e.cycle_fetch() for e in engines]
-        cycle_match_multi(engines)  # nothing deferred any more: a no-op, not an error
+        for _ in range(cycles):
+            if rank_batched:
+                cycle_run_rank_multi(engines, k)
+                st = engines[0].match_stats()
+                assert st["rank_batch_pools"] == len(engines) or len(engines) == 1, st
+            else:
+                for e in engines:
+                    e.cycle_run_rank(k)
+            cycle_match_multi(engines)
+            stats.append([e.match_stats() for e in engines])
+            rounds.append([e.cycle_fetch() for e in engines])
+            cycle_match_multi(engines)  # nothing deferred any more: a no-op, not an error
     finally:
         for e in engines:
             e.close()
-    for (ranked, j2o, head), pool in zip(got, pools):
+    for pi, pool in enumerate(pools):
         o_ranked, _ = pyoracle.rank(params, pool.tasks, pool.users)
-        assert np.array_equal(ranked, o_ranked)
         pend_ord = np.cumsum(pool.tasks.pending) - 1
         kk = min(k, len(o_ranked))
         o_j2o, _, o_head = pyoracle.match(params, pool.pending_jobs.take(pend_ord[o_ranked[:kk]]), pool.offers, pool.groups)
-        assert np.array_equal(j2o, o_j2o) and head == o_head
-    return got
+        for cyc, got in enumerate(rounds):
+            ranked, j2o, head = got[pi]
+            assert np.array_equal(ranked, o_ranked), (pi, cyc)
+            assert np.array_equal(j2o, o_j2o) and head == o_head, (pi, cyc)
+    return (rounds[-1], stats) if with_stats else rounds[-1]
 
 
 def rank_batch_parity(make_engine, cases, k, n_users=0, min_grouped=1):

@@ -9,6 +9,9 @@ import pytest
 from cook_amd import _abi as A
 from cook_amd import synth
 from cook_amd.engine import Engine
+from tests import classfit_batches_cases as CB
+from tests import classfit_limits_cases as CL
+from tests import classfit_phase1_cases as C1
 from tests import parity_cases as P
 
 
@@ -62,3 +65,22 @@ def test_rank_tie_tiles_of_several_items_per_thread(make_engine, monkeypatch):
         b = P.rank_parity(make_engine, pool, A.default_params(max_over_quota_jobs=10))
         monkeypatch.delenv("COOK_RANK_RADIX")
         assert np.array_equal(a, b)
+
+
+# ---- the class-ordered walk (match_algo 3) in its shipped shape: 1024 threads — sixteen waves, replica waves beside the class waves — and an
+# overlay of 64 lanes, where the everyday emulated build runs 512 threads and 8 lanes
+@pytest.mark.parametrize("name", list(C1.CASES))
+def test_classfit_batch_end_summary_pass(make_engine, name):
+    C1.check_case(make_engine, name)
+
+
+@pytest.mark.parametrize("name", ["classes", "kinds", "groups", "levels", "equals"])
+def test_classfit_limit_pair(make_engine, name):
+    """the limit pairs of tests/classfit_limits_cases.py that are cheap here (140 openers are exactly two epochs of this overlay)"""
+    CL.run_pair(make_engine, name)
+
+
+def test_classfit_epoch_and_exact_turn_behind_a_boundary(make_engine):
+    """the epoch case of tests/classfit_batches_cases.py at 16 times its size, the smallest at which this overlay ends two epochs (about 70 s
+    here a shift: one shift; the GPU file runs every shift at 24 times)"""
+    CB.epoch_and_exact_turn_behind_a_boundary(make_engine, 0, scale=16)

@@ -89,7 +89,9 @@ ALGOS = pytest.mark.parametrize("algo", [0, 1, 3], ids=["default", "serial", "cl
 def test_match_parity_c2(make_engine, ge, algo):
     # BASELINE config C2: cpus+mem only, 5k offers; K = first 3000 pending jobs in input order
     pool = synth.make_pool(seed=21, n_pending=3000, n_running=100, n_users=200, n_offers=5000)
-    P.match_parity(make_engine, pool.pending_jobs, pool.offers, None, A.default_params(good_enough_fitness=ge, match_algo=algo))
+    # (match_algo 3: the class-ordered form takes the call at good-enough 1.0 only; below it cf_setup answers before any set-up launch)
+    P.match_parity(make_engine, pool.pending_jobs, pool.offers, None, A.default_params(good_enough_fitness=ge, match_algo=algo),
+                   **P.classfit_expect(algo, 0 if ge == 1.0 else P.CF_REFUSED_HOST))
 
 
 @ALGOS
@@ -97,7 +99,8 @@ def test_match_parity_c3_constraints(make_engine, algo):
     # BASELINE config C3 shape: host/attribute constraints + gpu dimension + unique groups (scaled to oracle-seconds)
     pool = synth.make_pool(seed=22, n_pending=4000, n_running=1000, n_users=200, n_offers=2000, gpus=True, constraints=True)
     j2o = P.match_parity(make_engine, pool.pending_jobs, pool.offers, pool.groups,
-                         A.default_params(good_enough_fitness=1.0, match_algo=algo), reserved=(3, 7, 150))
+                         A.default_params(good_enough_fitness=1.0, match_algo=algo), reserved=(3, 7, 150),
+                         **P.classfit_expect(algo, P.CF_REFUSED_HOST))  # reserved hosts: the host's own check
     assert (j2o >= 0).sum() > 500
 
 
@@ -106,7 +109,7 @@ def test_match_fills_cluster_then_fails(make_engine, algo):
     # more demand than capacity: the tail of the queue must fail exactly like the oracle (fail codes included)
     pool = synth.make_pool(seed=23, n_pending=6000, n_running=0, n_users=50, n_offers=200)
     p = A.default_params(good_enough_fitness=1.0, match_algo=algo)
-    j2o = P.match_parity(make_engine, pool.pending_jobs, pool.offers, None, p)
+    j2o = P.match_parity(make_engine, pool.pending_jobs, pool.offers, None, p, **P.classfit_expect(algo))
     assert (j2o < 0).sum() > 1000
 
 
@@ -148,13 +151,15 @@ def test_match_group_types(make_engine, algo):
                       minimum=np.array([0, 3, 10, 0, 0, 0], dtype=np.int32),
                       run_hosts=[[1, 2], [3], [], [], [5, 6], []],
                       run_attrs=[[0, 0], [int(attr[3, 0])], [], [], [int(attr[5, 0]), int(attr[6, 0])], []])
-    P.match_parity(make_engine, jobs, offers, groups, A.default_params(good_enough_fitness=1.0, match_algo=algo))
+    P.match_parity(make_engine, jobs, offers, groups, A.default_params(good_enough_fitness=1.0, match_algo=algo),
+                   **P.classfit_expect(algo, P.CF_X_GROUP))  # balanced and attribute-equals groups
 
 
 @ALGOS
 def test_match_constraints_beyond_the_fast_paths(make_engine, algo):
     jobs, offers, groups = P.slow_constraint_case(9, 3000, 800)
-    j2o = P.match_parity(make_engine, jobs, offers, groups, A.default_params(good_enough_fitness=1.0, match_algo=algo))
+    j2o = P.match_parity(make_engine, jobs, offers, groups, A.default_params(good_enough_fitness=1.0, match_algo=algo),
+                         **P.classfit_expect(algo, P.CF_X_JOB_SLOW))
     assert (j2o >= 0).sum() > 300
 
 
@@ -611,8 +616,21 @@ def test_xres_known_answers(make_engine):
 def test_match_ports_scalars_maps(make_engine, kw, algo):
     kw = dict(kw)
     jobs, offers, groups = P.xres_random_case(kw.pop("seed"), kw.pop("n"), kw.pop("m"), **kw)
-    j2o = P.match_parity(make_engine, jobs, offers, groups, A.default_params(match_algo=algo))
+    # (the default good-enough fitness is 0.8, and four of the five cases ask for ports or scalars: cf_setup's own check either way)
+    j2o = P.match_parity(make_engine, jobs, offers, groups, A.default_params(match_algo=algo), **P.classfit_expect(algo, P.CF_REFUSED_HOST))
     assert (j2o >= 0).sum() > 20 and (j2o < 0).sum() > 5
+
+
+def test_match_ports_scalars_refused_at_good_enough_one(make_engine):
+    """ports / scalars alone keep a match_algo 3 call out of the class-ordered form (cf_setup's `has_x`): at good-enough 1.0 nothing else in this
+    call does (no reserved hosts, one offer a host)"""
+    jobs, offers, groups = P.xres_random_case(71, 6000, 400)
+    P.match_parity(make_engine, jobs, offers, groups, A.default_params(good_enough_fitness=1.0, match_algo=3), **P.classfit_expect(3, P.CF_REFUSED_HOST))
+    # the same jobs asking for neither get past cf_setup's own checks: the requests are what it refused.  (The set-up launches then find more
+    # than 48 classes — the offers have no running tasks, so every (cpus, mem) is a pair of totals of its own — and say so.)
+    assert len(set(zip(offers.cpus.tolist(), offers.mem.tolist()))) > 48
+    P.match_parity(make_engine, A.Jobs(cpus=jobs.cpus, mem=jobs.mem), offers, None, A.default_params(good_enough_fitness=1.0, match_algo=3),
+                   **P.classfit_expect(3, P.CF_X_SHAPE))
 
 
 @pytest.mark.parametrize("ge", [0.8, 0.4])
