@@ -1,6 +1,6 @@
 // classfit_host.hpp — host orchestration of the class-ordered best fit (classfit.hpp): when it is taken, its set-up, its launch.  Included by
 // engine.hip inside its anonymous namespace, behind launch.hpp and g_engines_on_device; match_host.hpp attempts it for one pool,
-// cook_cycle_match_multi runs the deferred walks of a device's pools in one launch.
+// cook_cycle_match_multi runs the walks that are set up (cook_engine::Placement) for a device's pools in one launch.
 
 // ---- class-ordered best fit (classfit.hpp): set-up, eligibility, launch --------------------------------------------------------------------
 // match_algo 3 asks for the class-ordered best fit.  match_algo 0 (the engine's choice) takes it when six or more engines share the device: its walks need no
@@ -76,17 +76,17 @@ static void cf_prof_print(const uint32_t* q) {
   (void)q;
 #endif
 }
-// cf_walk for the given engines (pools of one device) on `stream`, their group chains, the books of each
+// cf_walk for the given engines (pools of one device, each with a walk set up) on `stream`, their group chains, the books of each
 void cf_run(cook_engine* lead, cook_engine* const* es, unsigned n, hipStream_t stream) {
   cook_engine* e = lead;
   for (unsigned i0 = 0; i0 < n; i0 += (unsigned)CF_PACK) {
     const unsigned c = std::min<unsigned>(CF_PACK, n - i0);
     CfPack pk{};
-    for (unsigned x = 0; x < (unsigned)CF_PACK; ++x) pk.c[x] = es[i0 + (x < c ? x : 0u)]->deferred_cf;
+    for (unsigned x = 0; x < (unsigned)CF_PACK; ++x) pk.c[x] = es[i0 + (x < c ? x : 0u)]->placement.walk;
     KLS("cf_walk", stream, cf_walk, c, CF_THREADS, pk);
   }
   for (unsigned i = 0; i < n; ++i) {
-    const CfPoolCtx& c = es[i]->deferred_cf;
+    const CfPoolCtx& c = es[i]->placement.walk;
     const unsigned G = es[i]->last_in.G;
     if (G) KLS("cf_group_chains", stream, cf_group_chains, div_up(G, 256), 256, c.b, c.st, G);
   }
@@ -94,8 +94,8 @@ void cf_run(cook_engine* lead, cook_engine* const* es, unsigned n, hipStream_t s
   if (!lead->h_cf) COOK_HIP(hipHostMalloc((void**)&lead->h_cf, 64 * SLOT, hipHostMallocDefault));  // (at most 64 pools: pools_set_up, match_host.hpp)
   for (unsigned i = 0; i < n; ++i) {
     char* slot = lead->h_cf + i * SLOT;
-    COOK_HIP(hipMemcpyAsync(slot, es[i]->deferred_cf.st.summary, 16, hipMemcpyDeviceToHost, stream));
-    COOK_HIP(hipMemcpyAsync(slot + 16, es[i]->deferred_cf.b.ctl->stats, 48 * 4, hipMemcpyDeviceToHost, stream));
+    COOK_HIP(hipMemcpyAsync(slot, es[i]->placement.walk.st.summary, 16, hipMemcpyDeviceToHost, stream));
+    COOK_HIP(hipMemcpyAsync(slot + 16, es[i]->placement.walk.b.ctl->stats, 48 * 4, hipMemcpyDeviceToHost, stream));
   }
   COOK_HIP(hipStreamSynchronize(stream));
   for (unsigned i = 0; i < n; ++i) {
@@ -107,10 +107,6 @@ void cf_run(cook_engine* lead, cook_engine* const* es, unsigned n, hipStream_t s
     WinCtl c{};
     c.matched = sum[0], c.head_matched = sum[1], c.rounds = sum[2], c.head = x->last_in.K, c.visited_sum = x->cf_stats[CFS_WALKED];
     c.t_seq = x->cf_stats[CFS_TICKS_TOTAL], c.t_setup = x->cf_stats[CFS_TICKS_PROLOGUE];
-    x->last_ctl = c;
-    x->last_form = 3;
-    x->has_deferred_cf = false;
-    x->has_deferred = false;
-    x->match_done = true;
+    x->placement_complete(3, c);
   }
 }

@@ -537,8 +537,7 @@ void cycle_update(cook_engine* e, UpdateBufs& ub, const cook_cycle_delta* d) {
   e->K = P2;
   in.K = P2;
   e->rank_done = false;
-  e->match_done = false;
-  e->has_deferred = false;
+  e->placement_drop();
   if (d->offers) {
     offers_block_commit(e, ub, d->offers, offers_plan);
     sync(e);

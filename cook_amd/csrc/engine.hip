@@ -125,7 +125,7 @@ struct cook_engine {
   unsigned n_ranked = 0;
 
   // ---- match state ----
-  bool match_staged = false, match_done = false;
+  bool match_staged = false;
   unsigned K = 0, M = 0, G = 0, Kjobs = 0;
   DArr<double> j_scal[3], o_scal[3], m_xscal;
   DArr<int32_t> j_ports, o_ports, m_xports;
@@ -151,10 +151,19 @@ struct cook_engine {
   DArr<WinCtl> w_ctl;
   DArr<RoundLog> w_rlog;
   DArr<PoolCtx> w_pctx;      // contexts of a multi-pool match led by this engine
-  PoolCtx deferred{};        // this engine's match, set up but not run (cook_cycle_run_rank)
-  bool has_deferred = false;
-  unsigned deferred_k = 0;
-  WinCtl deferred_c0{};
+  // Where this pool's match is.  A set-up (cook_cycle_run_rank) waits for cook_cycle_match_multi with what its form needs; placement_drop and
+  // placement_complete are the ways out of a set-up and the only writers of NONE and DONE.
+  struct Placement {
+    enum State { NONE, ROUNDS, WALK, DONE } state = NONE;  // nothing; window rounds set up; class-ordered walk set up; a match has run
+    PoolCtx rounds{};  // ROUNDS: the pool's context, ...
+    WinCtl c0{};       // ... the control block its rounds start from (after a served match that gave up: where lockstep rounds go on),
+    unsigned k = 0;    // ... its jobs, and whether it needs the GE launches (good-enough-fitness < 1)
+    bool ge = false;
+    CfPoolCtx walk{};  // WALK
+  } placement;
+  bool match_ran() const { return placement.state == Placement::DONE; }
+  void placement_drop() { placement.state = Placement::NONE; }  // before the tables a set-up points into change: the set-up is forgotten, no match has run
+  void placement_complete(unsigned form, const WinCtl& c) { last_ctl = c, last_form = form, placement.state = Placement::DONE; }
   WinCtl* h_multi = nullptr;  // pinned: the pools' WinCtl read-backs
   // served walkers (match_rounds_served): the two streams of a served match led by this engine, its control blocks, what it did
   static constexpr unsigned kMaxServers = 4;
@@ -172,7 +181,6 @@ struct cook_engine {
   void* h_inbuf = nullptr;  // pinned staging copy of MatchIn
   WinCtl last_ctl{};
   bool groups_simple = true;  // no balanced / attribute-equals group staged (cook_match_stage)
-  bool deferred_ge = false;   // the deferred call needs the GE launches (good-enough-fitness < 1)
   MatchIn min{};
   bool cycle_staged = false;
   unsigned cycle_considered = 0;
@@ -180,7 +188,7 @@ struct cook_engine {
   // since (cook_cycle_autoscale reads all three)
   bool cycle_cons_ran = false;
   // ---- the standing queue of the queue cycles (queue_host.hpp): `ranked` is the queue a match cycle may consume — the last cycle took its
-  // jobs from it and nothing has shifted or dropped the rows it points at since (with rank_done and match_done: that cycle is complete)
+  // jobs from it and nothing has shifted or dropped the rows it points at since (with rank_done and a match that has run: that cycle is complete)
   bool q_valid = false;
   const uint32_t* q_last_pos = nullptr;  // device: rank positions of the last cycle's considered jobs; null: 0 .. cycle_considered - 1
   bool q_groups_own = false;             // min.g_run_* point at a queue cycle's table; the staged one is q_sg_*
@@ -219,8 +227,6 @@ struct cook_engine {
   DArr<CfJob> cf_jobs;
   uint32_t cf_max_host = 0xFFFFFFFFu;   // greatest host id of the staged offers; 0xFFFFFFFF: not known (offers built on the device)
   uint32_t cf_group_run_total = 0;      // running cotasks over all staged groups
-  bool has_deferred_cf = false;         // this engine's match is set up for cf_walk and waits for cook_cycle_match_multi
-  CfPoolCtx deferred_cf{};
   unsigned last_form = 0;               // how the last match was placed: 0 window rounds, 1 serial sweep, 3 class-ordered best fit
   unsigned spread_serial_calls = 0;     // matches that match_algo 0 / 2 / 3 would have placed in window rounds and the sweep placed: a spreader (cook_match_stats_ex [39])
   unsigned cf_inelig = 0;               // why the last match that asked for class-ordered best fit did not get it (CF_X_* bits; 0x10000: switched off / the host's checks)
@@ -480,7 +486,7 @@ int cook_match_fetch(cook_engine* e, int32_t* job_to_offer, uint32_t* fail_code,
 int cook_match_count(cook_engine* e, uint32_t* n_jobs) {
   return guarded(e, [&] {
     if (!n_jobs) e->fail(COOK_E_INVALID, "cook_match_count: null n_jobs");
-    if (!e->match_done) e->fail(COOK_E_STATE, "cook_match_count before a match has run");
+    if (!e->match_ran()) e->fail(COOK_E_STATE, "cook_match_count before a match has run");
     *n_jobs = e->cycle_considered;
   });
 }
@@ -645,13 +651,20 @@ int cook_cycle_match_multi(cook_engine** engines, uint32_t n) {
   if (!engines || n == 0 || !engines_valid(engines, n, false)) return COOK_E_INVALID;
   cook_engine* lead = engines[0];
   return guarded(lead, [&] {
+    pools_check(engines, n);
     StageTimer tm(lead, 2, &lead->match_ms);
-    // the pools that are placed by class-ordered best fit (classfit.hpp): ONE launch, a workgroup per pool
-    const std::vector<cook_engine*> cf = pools_set_up(engines, n, &cook_engine::has_deferred_cf);
-    if (!cf.empty()) cf_run(lead, cf.data(), (unsigned)cf.size(), lead->stream);
-    // served walkers (one persistent walker workgroup per pool beside serve launches); lockstep launches when switched off, for more
-    // pools than a served call takes, or to finish a served match that gave up
-    if (!(served_enabled() && match_rounds_served(engines, n))) match_rounds_multi(engines, n);
+    try {
+      // the pools that are placed by class-ordered best fit (classfit.hpp): ONE launch, a workgroup per pool
+      const std::vector<cook_engine*> cf = pools_set_up(engines, n, cook_engine::Placement::WALK);
+      if (!cf.empty()) cf_run(lead, cf.data(), (unsigned)cf.size(), lead->stream);
+      // served walkers (one persistent walker workgroup per pool beside serve launches); lockstep launches when switched off, for more
+      // pools than a served call takes, or to finish a served match that gave up
+      if (!(served_enabled() && match_rounds_served(engines, n))) match_rounds_multi(engines, n);
+    } catch (...) {
+      // launches have run, no set-up describes its tables any more: every engine of the call is back to "no match ran" (cook_cycle_fetch: COOK_E_STATE)
+      for (uint32_t i = 0; i < n; ++i) engines[i]->placement_drop();
+      throw;
+    }
     tm.stop();
     for (uint32_t i = 1; i < n; ++i) engines[i]->match_ms = lead->match_ms;  // one joint sequence of launches
     prof_collect(lead);
@@ -716,7 +729,7 @@ int cook_cycle_set_considerable(cook_engine* e, const cook_user_state* us, const
 int cook_cycle_fetch_considerable(cook_engine* e, uint32_t* rank_pos, uint32_t* n_out) {
   if (n_out) *n_out = 0;
   return guarded(e, [&] {
-    if (!e->match_done) e->fail(COOK_E_STATE, "cook_cycle_fetch_considerable before cook_cycle_run");
+    if (!e->match_ran()) e->fail(COOK_E_STATE, "cook_cycle_fetch_considerable before cook_cycle_run");
     const unsigned K = e->cycle_considered;
     if (e->cb && e->cb->cycle_on) {
       if (K && rank_pos) copy_async(e, rank_pos, e->cb->result, (size_t)K * 4, hipMemcpyDeviceToHost);

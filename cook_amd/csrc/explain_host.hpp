@@ -30,7 +30,7 @@ MatchState explain_state(cook_engine* e, unsigned K) {
 }
 
 void match_explain(cook_engine* e, ExplainBufs& x, const uint32_t* job_pos, unsigned n, uint32_t* counts) {
-  if (!e->match_done || !e->last_in_valid) e->fail(COOK_E_STATE, "cook_match_explain before a match ran");
+  if (!e->match_ran() || !e->last_in_valid) e->fail(COOK_E_STATE, "cook_match_explain before a match ran");
   if (n && (!job_pos || !counts)) e->fail(COOK_E_INVALID, "cook_match_explain: null job positions / counts");
   const MatchIn in = e->last_in;
   const unsigned K = in.K, M = in.M;
@@ -91,7 +91,7 @@ void resource_stats(cook_engine* e, ExplainBufs& x, const double* a, const doubl
 
 void match_metrics(cook_engine* e, ExplainBufs& x, cook_cycle_metrics* out, uint32_t* user_considerable, uint32_t* user_matched,
                    unsigned n_users, int64_t* job_gpus_by_model, int64_t* offer_gpus_by_model, unsigned n_models) {
-  if (!e->match_done || !e->last_in_valid) e->fail(COOK_E_STATE, "cook_match_metrics before a match ran");
+  if (!e->match_ran() || !e->last_in_valid) e->fail(COOK_E_STATE, "cook_match_metrics before a match ran");
   if (!out) e->fail(COOK_E_INVALID, "cook_match_metrics: null output");
   const MatchIn in = e->last_in;
   const unsigned K = in.K, M = in.M;

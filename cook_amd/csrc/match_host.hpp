@@ -1,7 +1,10 @@
 // match_host.hpp — host orchestration of the match (cook_match_*, and the match of a cycle): staging of jobs, offers and groups; one pool's
 // placement in named pieces (match_run_device); the pools of a device in lockstep rounds (match_rounds_multi).  Included by engine.hip
 // inside its anonymous namespace, behind launch.hpp, classfit_host.hpp (cf_setup, cf_run) and g_engines_on_device; expects match_kernels.hpp
-// and match_v2.hpp.  served_host.hpp and the side features use its staging and pools_set_up / match_finish_rounds / pack_args.
+// and match_v2.hpp.  served_host.hpp and the side features use its staging and pools_set_up / pools_gather / pools_read_ctl /
+// match_finish_rounds / pack_args.  Where a pool's match is, is ONE member of the engine (cook_engine::Placement): match_defer and
+// match_try_classfit enter a set-up; the ways out are placement_drop (match_run_device, match_stage_inputs, cycle_update, a
+// cook_cycle_match_multi that failed after its first launch) and placement_complete (match_finish_rounds, cf_run, the sweep and K = 0).
 
 // The placement walk keeps one LDS byte per offer of the pool.  A pool in a lockstep chain runs the good-enough flavour of the kernels
 // whenever ANY pool of its chain has good-enough < 1 (match_rounds_multi), so the table must leave room for segments in both.
@@ -85,6 +88,7 @@ void match_stage_inputs(cook_engine* e, const cook_jobs* j, const cook_offers* o
   if (j->group && g)
     for (unsigned k = 0; k < K; ++k)
       if (j->group[k] != COOK_NONE_U32 && j->group[k] >= G) e->fail(COOK_E_INVALID, "cook_match_stage: group id out of range");
+  e->placement_drop();  // (the columns below may move: a set-up would point at freed ones)
   MatchIn& in = e->min;
   std::memset(&in, 0, sizeof(in));
   in.K = K;
@@ -170,7 +174,6 @@ void match_stage_inputs(cook_engine* e, const cook_jobs* j, const cook_offers* o
   e->M = M;
   e->G = G;
   e->match_staged = true;
-  e->match_done = false;
 }
 
 // the state a match call starts from, in ONE launch (nine memsets before round 5: each is a launch, and the set-up of a pool's match sits
@@ -232,9 +235,8 @@ static void launch_round(cook_engine* e, const MatchIn& in, const MatchState& st
   KL("match_resolve2", match_resolve2<GE>, 1, MV_RTHREADS, st, vb);
 }
 
-// after the last round: statistics, the optional per-round log, the summary words of cook_*_fetch
+// after the last round: statistics, the optional per-round log, the summary words of cook_*_fetch; the pool's placement is complete
 void match_finish_rounds(cook_engine* e, const MatchState& st, const V2Buf& vb, const WinCtl& hc, hipStream_t stream) {
-  e->last_ctl = hc;
   const char* rlog_path = std::getenv("COOK_ROUND_LOG");
   if (rlog_path && vb.round_log) {
     std::vector<RoundLog> h(std::min(hc.rounds, MV_ROUND_LOG_CAP));
@@ -267,6 +269,7 @@ void match_finish_rounds(cook_engine* e, const MatchState& st, const V2Buf& vb, 
   std::memcpy(e->h_scratch, sum, 16);
   COOK_HIP(hipMemcpyAsync(st.summary, e->h_scratch, 16, hipMemcpyHostToDevice, stream));
   COOK_HIP(hipStreamSynchronize(stream));
+  e->placement_complete(0, hc);
 }
 
 // ---- one pool's match, in named pieces (match_run_device below puts them together) ------------------------------------------------------
@@ -363,10 +366,9 @@ static bool match_try_classfit(cook_engine* e, const MatchIn& in, const MatchSta
     e->cf_inelig = CF_X_FITNESS;
     return false;
   }
-  if (!cf_setup(e, in, (const MatchIn*)vb.in_dev, st, vb.jr, vb.jcons, vb.oa, vb.ob, e->deferred_cf)) return false;
+  if (!cf_setup(e, in, (const MatchIn*)vb.in_dev, st, vb.jr, vb.jcons, vb.oa, vb.ob, e->placement.walk)) return false;
   e->cycle_considered = in.K;
-  e->match_done = false;
-  e->has_deferred_cf = true;
+  e->placement.state = cook_engine::Placement::WALK;
   if (defer) return true;
   cook_engine* one[1] = {e};
   cf_run(e, one, 1, e->stream);
@@ -375,15 +377,11 @@ static bool match_try_classfit(cook_engine* e, const MatchIn& in, const MatchSta
 // set up only: cook_cycle_match_multi runs the rounds of several pools together
 static void match_defer(cook_engine* e, const MatchIn& in, const MatchState& st, const V2Buf& vb, const WinCtl& c0, bool ge) {
   sync(e);
-  e->deferred.in = in;
-  e->deferred.st = st;
-  e->deferred.vb = vb;
-  e->deferred_k = in.K;
-  e->deferred_c0 = c0;
-  e->deferred_ge = ge;
-  e->has_deferred = true;
+  cook_engine::Placement& p = e->placement;
+  p.rounds.in = in, p.rounds.st = st, p.rounds.vb = vb;
+  p.c0 = c0, p.k = in.K, p.ge = ge;
+  p.state = cook_engine::Placement::ROUNDS;
   e->cycle_considered = in.K;
-  e->match_done = false;
 }
 
 // -DCOOK_EVAL_TRACE (timing-study build, scripts/eval_trace.py): the waves' phase stamps of the evaluation of round COOK_EVAL_TRACE_ROUND, to
@@ -466,6 +464,7 @@ static void match_run_rounds(cook_engine* e, const MatchIn& in, const MatchState
 // One pool's match of the first K staged jobs (j_index: which, null: 0 .. K - 1).  defer: set up only, cook_cycle_match_multi places it
 // with the other pools of the device.
 void match_run_device(cook_engine* e, unsigned K, const uint32_t* j_index, bool defer = false) {
+  e->placement_drop();  // (whatever was set up and not run: this match takes its state and its buffers)
   MatchIn in = e->min;
   in.K = K;
   in.j_index = j_index;
@@ -475,7 +474,6 @@ void match_run_device(cook_engine* e, unsigned K, const uint32_t* j_index, bool 
   e->last_in = in;
   e->last_in_valid = true;
   const MatchState st = match_state_setup(e, in);
-  e->has_deferred = false;
   e->cf_inelig = 0;  // (stats word 38 speaks of THIS match: set below or by match_try_classfit where the class-ordered form was asked for and refused)
   const int algo = e->params.match_algo;
   if (!(algo == 0 || algo == 1 || algo == 2 || algo == 3))
@@ -483,6 +481,8 @@ void match_run_device(cook_engine* e, unsigned K, const uint32_t* j_index, bool 
   // A spreader's fitness FALLS on the offer a job lands on, so the window rounds' rule "a touched offer that is still feasible beats every
   // untouched offer behind it" is false for it: such a pool is placed by the sweep, as match_algo 1
   const bool spread = fitness_is_spreader(e);
+  WinCtl no_rounds{};  // the counts of a match without rounds: the sweep keeps none, K = 0 has none
+  no_rounds.head = K;
   if (spread && algo != 1) {
     ++e->spread_serial_calls;
     if (algo == 3 || (algo == 0 && classfit_by_default(e))) e->cf_inelig = CF_X_FITNESS;
@@ -491,14 +491,11 @@ void match_run_device(cook_engine* e, unsigned K, const uint32_t* j_index, bool 
     constexpr int SERIAL_THREADS = COOK_SHAPE(1024, 256);
     auto k_match = match_serial<SERIAL_THREADS>;
     KL("match_serial", k_match, 1, SERIAL_THREADS, in, st);
-    e->last_form = 1;
-    e->has_deferred_cf = false;
+    e->placement_complete(1, no_rounds);
   } else if (K > 0) {  // window rounds (only they, and the class-ordered walk, run several pools in one launch: defer)
     match_check_offer_count(e, in.M);
     const bool ge = in.good_enough < 1.0;
     const V2Buf vb = match_v2_setup(e, in, st, ge);
-    e->last_form = 0;
-    e->has_deferred_cf = false;
     if ((algo == 3 || (algo == 0 && classfit_by_default(e))) && match_try_classfit(e, in, st, vb, defer)) return;
     const WinCtl c0 = first_window(e, K);
     std::memcpy(e->h_scratch, &c0, sizeof(c0));
@@ -510,53 +507,71 @@ void match_run_device(cook_engine* e, unsigned K, const uint32_t* j_index, bool 
     std::memcpy(e->h_scratch, sum, 16);
     copy_async(e, st.summary, e->h_scratch, 16, hipMemcpyHostToDevice);
     sync(e);
+    e->placement_complete(0, no_rounds);  // (window rounds, none of them)
   }
   e->cycle_considered = K;
-  e->match_done = true;
 }
 
-// The engines of one cook_cycle_match_multi call: all on the lead's device, every one with a match set up or finished (what
-// cook_cycle_run_rank leaves).  -> those with `flag` (has_deferred: window rounds, has_deferred_cf: a class-ordered walk) set, in the
-// call's order; at most 64 (the slots of the lead's page-locked read-back blocks h_multi and h_cf)
-std::vector<cook_engine*> pools_set_up(cook_engine* const* es, unsigned n, bool cook_engine::*flag) {
+// The engines of one cook_cycle_match_multi call, checked BEFORE its first launch (a refusal leaves every engine as it was): all on the lead's device,
+// each with a match set up or finished (what cook_cycle_run_rank leaves), at most 64 of either form (the slots of the lead's page-locked blocks h_multi, h_cf)
+void pools_check(cook_engine* const* es, unsigned n) {
   cook_engine* lead = es[0];
-  std::vector<cook_engine*> live;
+  unsigned rounds = 0, walks = 0;
   for (unsigned i = 0; i < n; ++i) {
     if (!es[i] || es[i]->device != lead->device) lead->fail(COOK_E_INVALID, "cook_cycle_match_multi: engines must share one device");
-    if (es[i]->*flag) live.push_back(es[i]);
-    else if (!es[i]->has_deferred && !es[i]->has_deferred_cf && !es[i]->match_done) lead->fail(COOK_E_STATE, "cook_cycle_match_multi before cook_cycle_run_rank");
+    const auto st = es[i]->placement.state;
+    if (st == cook_engine::Placement::NONE) lead->fail(COOK_E_STATE, "cook_cycle_match_multi before cook_cycle_run_rank");
+    rounds += st == cook_engine::Placement::ROUNDS, walks += st == cook_engine::Placement::WALK;
   }
-  if (live.size() > 64) lead->fail(COOK_E_INVALID, "cook_cycle_match_multi: at most 64 pools per call");
+  if (rounds > 64 || walks > 64) lead->fail(COOK_E_INVALID, "cook_cycle_match_multi: at most 64 pools per call");
+}
+// -> those of them whose match is in `state` (ROUNDS: window rounds set up, WALK: a class-ordered walk set up), in the call's order
+std::vector<cook_engine*> pools_set_up(cook_engine* const* es, unsigned n, cook_engine::Placement::State state) {
+  std::vector<cook_engine*> live;
+  for (unsigned i = 0; i < n; ++i)
+    if (es[i]->placement.state == state) live.push_back(es[i]);
   return live;
+}
+
+// What a launch for several pools needs of them: the contexts in the launch's order, the widest eval grid, and whether some pool runs with good-enough-fitness
+// below 1: the GE launches for the whole chain then (a pool at 1.0 in it is placed by best fit all the same, from the GE shape's shorter best-fit lists)
+struct PoolsOfLaunch { std::vector<PoolCtx> hctx; unsigned cmax = 1; bool any_ge = false; };
+static PoolsOfLaunch pools_gather(cook_engine* lead, const std::vector<cook_engine*>& live) {
+  if (!lead->h_multi) COOK_HIP(hipHostMalloc((void**)&lead->h_multi, 64 * sizeof(WinCtl), hipHostMallocDefault));
+  PoolsOfLaunch g;
+  for (const cook_engine* e : live) {
+    g.hctx.push_back(e->placement.rounds);
+    g.cmax = std::max(g.cmax, e->placement.rounds.vb.C);
+    g.any_ge = g.any_ge || e->placement.ge;
+  }
+  return g;
+}
+// the pools' control blocks as the device has them now, read back on `stream` (which it synchronises) -> hc
+static void pools_read_ctl(cook_engine* lead, const std::vector<PoolCtx>& hctx, std::vector<WinCtl>& hc, hipStream_t stream) {
+  const unsigned L = (unsigned)hctx.size();
+  for (unsigned x = 0; x < L; ++x) COOK_HIP(hipMemcpyAsync(&lead->h_multi[x], hctx[x].vb.ctl, sizeof(WinCtl), hipMemcpyDeviceToHost, stream));
+  COOK_HIP(hipStreamSynchronize(stream));
+  hc.assign(lead->h_multi, lead->h_multi + L);
 }
 
 // The placements of n engines (pools of one rank, same device) in lockstep rounds on the lead engine's stream.
 void match_rounds_multi(cook_engine** es, unsigned n) {
   cook_engine* lead = es[0];
-  const std::vector<cook_engine*> live = pools_set_up(es, n, &cook_engine::has_deferred);
+  const std::vector<cook_engine*> live = pools_set_up(es, n, cook_engine::Placement::ROUNDS);
   const unsigned L = (unsigned)live.size();
   if (L == 0) return;
-  if (!lead->h_multi) COOK_HIP(hipHostMalloc((void**)&lead->h_multi, 64 * sizeof(WinCtl), hipHostMallocDefault));
-  std::vector<PoolCtx> hctx(L);
+  const PoolsOfLaunch g = pools_gather(lead, live);
+  const std::vector<PoolCtx>& hctx = g.hctx;
   std::vector<WinCtl> hc(L);
-  unsigned cmax = 1;
-  for (unsigned x = 0; x < L; ++x) {
-    cook_engine* e = live[x];
-    hctx[x] = e->deferred;
-    hc[x] = e->deferred_c0;
-    cmax = std::max(cmax, e->deferred.vb.C);
-  }
+  for (unsigned x = 0; x < L; ++x) hc[x] = live[x]->placement.c0;
   PoolCtx* dctx = lead->w_pctx.ensure(L);
   COOK_HIP(hipMemcpyAsync(dctx, hctx.data(), L * sizeof(PoolCtx), hipMemcpyHostToDevice, lead->stream));
   COOK_HIP(hipStreamSynchronize(lead->stream));  // hctx is pageable
   cook_engine* e = lead;                         // KL times / launches on the lead engine
-  bool any_ge = false;  // some pool of the launch runs with good-enough-fitness below 1: the GE launches for the whole chain (a pool at
-                        // 1.0 in it is placed by best fit all the same, from the GE shape's shorter best-fit lists)
-  for (unsigned x = 0; x < L; ++x) any_ge = any_ge || live[x]->deferred_ge;
   unsigned batch = 8, guard = 0;
   auto all_done = [&] {
     for (unsigned x = 0; x < L; ++x)
-      if (hc[x].head < live[x]->deferred_k) return false;
+      if (hc[x].head < live[x]->placement.k) return false;
     return true;
   };
   // up to MV_PACK pools: their contexts travel in the kernel arguments (match_v2.hpp: PoolPack)
@@ -569,48 +584,35 @@ void match_rounds_multi(cook_engine** es, unsigned n) {
   }
   auto round = [&](auto ge_tag) {
     constexpr bool GE = decltype(ge_tag)::value;
-    if (packed && L <= 2u) {
-      KL("match_eval2", (match_eval2_pack<GE, 2>), dim3(cmax, MV_JG, L), COOK_WAVE * MV_EW, pk2);
-      KL("match_merge2", (match_merge2_pack<GE, 2>), dim3(MV_MERGE_BLOCKS, 1, L), COOK_WAVE * MV_MW, pk2);
-      KL("match_resolve2", (match_resolve2_pack<GE, 2>), dim3(1, 1, L), MV_RTHREADS, pk2);
-    } else if (packed) {
-      KL("match_eval2", (match_eval2_pack<GE, MV_PACK>), dim3(cmax, MV_JG, L), COOK_WAVE * MV_EW, pk4);
-      KL("match_merge2", (match_merge2_pack<GE, MV_PACK>), dim3(MV_MERGE_BLOCKS, 1, L), COOK_WAVE * MV_MW, pk4);
-      KL("match_resolve2", (match_resolve2_pack<GE, MV_PACK>), dim3(1, 1, L), MV_RTHREADS, pk4);
-    } else {
-      KL("match_eval2", match_eval2_multi<GE>, dim3(cmax, MV_JG, L), COOK_WAVE * MV_EW, (const PoolCtx*)dctx);
-      KL("match_merge2", match_merge2_multi<GE>, dim3(MV_MERGE_BLOCKS, 1, L), COOK_WAVE * MV_MW, (const PoolCtx*)dctx);
-      KL("match_resolve2", match_resolve2_multi<GE>, dim3(1, 1, L), MV_RTHREADS, (const PoolCtx*)dctx);
-    }
+    auto launch3 = [&](auto eval, auto merge, auto resolve, const auto& arg) {
+      KL("match_eval2", eval, dim3(g.cmax, MV_JG, L), COOK_WAVE * MV_EW, arg);
+      KL("match_merge2", merge, dim3(MV_MERGE_BLOCKS, 1, L), COOK_WAVE * MV_MW, arg);
+      KL("match_resolve2", resolve, dim3(1, 1, L), MV_RTHREADS, arg);
+    };
+    if (packed && L <= 2u) launch3(match_eval2_pack<GE, 2>, match_merge2_pack<GE, 2>, match_resolve2_pack<GE, 2>, pk2);
+    else if (packed) launch3(match_eval2_pack<GE, MV_PACK>, match_merge2_pack<GE, MV_PACK>, match_resolve2_pack<GE, MV_PACK>, pk4);
+    else launch3(match_eval2_multi<GE>, match_merge2_multi<GE>, match_resolve2_multi<GE>, (const PoolCtx*)dctx);
   };
   while (!all_done()) {
     for (unsigned r = 0; r < batch; ++r) {
-      if (any_ge) round(std::true_type{});
+      if (g.any_ge) round(std::true_type{});
       else round(std::false_type{});
     }
     const std::vector<WinCtl> prev = hc;
-    for (unsigned x = 0; x < L; ++x)
-      COOK_HIP(hipMemcpyAsync(&lead->h_multi[x], hctx[x].vb.ctl, sizeof(WinCtl), hipMemcpyDeviceToHost, lead->stream));
-    COOK_HIP(hipStreamSynchronize(lead->stream));
+    pools_read_ctl(lead, hctx, hc, lead->stream);
     double est = 0;
     for (unsigned x = 0; x < L; ++x) {
-      hc[x] = lead->h_multi[x];
-      const unsigned K = live[x]->deferred_k;
+      const unsigned K = live[x]->placement.k;
       if (hc[x].head < K) est = std::max(est, rounds_left(K, hc[x], prev[x]));
     }
     batch = next_batch(est);
     if (++guard > 1000000u) lead->fail(COOK_E_STATE, "cook_cycle_match_multi: placement made no progress");
   }
-  for (unsigned x = 0; x < L; ++x) {
-    cook_engine* ex = live[x];
-    match_finish_rounds(ex, hctx[x].st, hctx[x].vb, hc[x], lead->stream);
-    ex->has_deferred = false;
-    ex->match_done = true;
-  }
+  for (unsigned x = 0; x < L; ++x) match_finish_rounds(live[x], hctx[x].st, hctx[x].vb, hc[x], lead->stream);
 }
 
 void match_fetch(cook_engine* e, unsigned K, int32_t* job_to_offer, uint32_t* fail_code, uint8_t* head_matched) {
-  if (!e->match_done) e->fail(COOK_E_STATE, "cook_match_fetch before cook_match_run");
+  if (!e->match_ran()) e->fail(COOK_E_STATE, "cook_match_fetch before cook_match_run");
   if (job_to_offer && K) copy_async(e, job_to_offer, e->m_j2o.ptr(), (size_t)K * 4, hipMemcpyDeviceToHost);
   if (fail_code && K) copy_async(e, fail_code, e->m_fail.ptr(), (size_t)K * 4, hipMemcpyDeviceToHost);
   copy_async(e, e->h_scratch, e->m_summary.ptr(), 16, hipMemcpyDeviceToHost);

@@ -27,7 +27,7 @@ void queue_reset_groups(cook_engine* e) {
 
 // everything that can refuse a step, before anything changes
 void queue_check_step(cook_engine* e, const cook_queue_step* s, const cook_queue_carry* c = nullptr) {
-  if (!e->cycle_staged || !e->q_valid || !e->rank_done || !e->match_done)
+  if (!e->cycle_staged || !e->q_valid || !e->rank_done || !e->match_ran())
     e->fail(COOK_E_STATE, "cook_cycle_run_queue needs a completed cycle (cook_cycle_run, cook_cycle_run_rank* + cook_cycle_match_multi or a queue "
                           "cycle) with no cook_cycle_stage / cook_cycle_update / cook_rank* / cook_considerable / cook_match_stage since");
   carry_check(e, s, c);

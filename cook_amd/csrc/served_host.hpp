@@ -1,5 +1,6 @@
-// served_host.hpp — the pools of a device placed by served walkers (match_v2.hpp "served walkers"): the other form of cook_cycle_match_multi.
-// Included by engine.hip inside its anonymous namespace, behind match_host.hpp (pools_set_up, match_finish_rounds, pack_args).
+// served_host.hpp — the pools of a device placed by served walkers (match_v2_served.hpp): the other form of cook_cycle_match_multi.
+// Included by engine.hip inside its anonymous namespace, behind match_host.hpp (pools_set_up, pools_gather, pools_read_ctl,
+// match_finish_rounds — which completes a pool's placement —, pack_args).
 
 // COOK_MATCH_SERVED=0: cook_cycle_match_multi always runs its pools in lockstep launches (match_rounds_multi); default: served walkers
 static bool served_enabled() {
@@ -23,12 +24,12 @@ static unsigned long long env_ticks(const char* name, double dflt_us) {
 }
 
 // The placements of n engines (pools of one rank, same device) by persistent walkers — one workgroup per pool, ONE launch — beside
-// serve iterations (evaluation + merge for the pools that asked) on a second stream: match_v2.hpp "served walkers".  -> false: the
+// serve iterations (evaluation + merge for the pools that asked) on a second stream: match_v2_served.hpp.  -> false: the
 // served match gave up (a walker was not served in time); the pools are in a consistent state and the caller finishes them in lockstep.
 bool match_rounds_served(cook_engine** es, unsigned n) {
   cook_engine* lead = es[0];
   cook_engine* e = lead;  // KL / KLS time and launch on the lead engine
-  const std::vector<cook_engine*> live = pools_set_up(es, n, &cook_engine::has_deferred);
+  const std::vector<cook_engine*> live = pools_set_up(es, n, cook_engine::Placement::ROUNDS);
   const unsigned L = (unsigned)live.size();
   lead->served = cook_engine::ServedStats{};
   if (L == 0) return true;
@@ -44,7 +45,6 @@ bool match_rounds_served(cook_engine** es, unsigned n) {
     COOK_HIP(hipStreamCreateWithPriority(&lead->s_walk, hipStreamNonBlocking, prio_greatest));
     COOK_HIP(hipHostMalloc((void**)&lead->h_serve, MAXS * sizeof(ServeHost), hipHostMallocDefault));
   }
-  if (!lead->h_multi) COOK_HIP(hipHostMalloc((void**)&lead->h_multi, 64 * sizeof(WinCtl), hipHostMallocDefault));
   // SERVERS: streams of serve iterations, each for its own share of the pools (pool x -> server x mod S).  An iteration is a chain of
   // latency-bound launches that leaves most of the chip idle (a window of 300 jobs is 980 waves for 4 096 slots), so two or three of
   // them side by side serve the walkers sooner than one; the walkers' launch makes S + 1 streams.
@@ -53,14 +53,8 @@ bool match_rounds_served(cook_engine** es, unsigned n) {
   S = std::min(std::min(S, MAXS), L);
   for (unsigned sv = 0; sv < S; ++sv)
     if (!lead->s_serve[sv]) COOK_HIP(hipStreamCreateWithFlags(&lead->s_serve[sv], hipStreamNonBlocking));
-  std::vector<PoolCtx> hctx(L);
-  unsigned cmax = 1;
-  bool any_ge = false;
-  for (unsigned x = 0; x < L; ++x) {
-    hctx[x] = live[x]->deferred;
-    cmax = std::max(cmax, hctx[x].vb.C);
-    any_ge = any_ge || live[x]->deferred_ge;
-  }
+  const PoolsOfLaunch g = pools_gather(lead, live);
+  const std::vector<PoolCtx>& hctx = g.hctx;
   PoolCtx* dctx = lead->w_pctx.ensure(L);
   ServeSlot* slots = lead->w_slots.ensure(L);
   ServeCtl* sctl = lead->w_sctl.ensure(MAXS);
@@ -120,12 +114,12 @@ bool match_rounds_served(cook_engine** es, unsigned n) {
     constexpr bool GE = decltype(ge_tag)::value;
     hipStream_t st_ = lead->s_serve[one_stream ? 0u : sv];
     const unsigned it = launched[sv];  // the iteration's number picks its latch list (ServeLatch)
-    KLS("match_serve_eval", st_, match_serve_eval<GE>, dim3(cmax, MV_JG, zmax), COOK_WAVE * MV_EW, (const PoolCtx*)dctx, (const ServeCtl*)(sctl + sv), it);
+    KLS("match_serve_eval", st_, match_serve_eval<GE>, dim3(g.cmax, MV_JG, zmax), COOK_WAVE * MV_EW, (const PoolCtx*)dctx, (const ServeCtl*)(sctl + sv), it);
     KLS("match_serve_merge", st_, match_serve_merge<GE>, dim3(MV_MERGE_BLOCKS, 1, zmax), COOK_WAVE * MV_MW, (const PoolCtx*)dctx, sctl + sv, slots, hh + sv, poll, it);
     ++launched[sv];
   };
-  auto launch_walkers = [&] { any_ge ? walkers(std::true_type{}) : walkers(std::false_type{}); };
-  auto launch_serve = [&](unsigned sv) { any_ge ? serve(std::true_type{}, sv) : serve(std::false_type{}, sv); };
+  auto launch_walkers = [&] { g.any_ge ? walkers(std::true_type{}) : walkers(std::false_type{}); };
+  auto launch_serve = [&](unsigned sv) { g.any_ge ? serve(std::true_type{}, sv) : serve(std::false_type{}, sv); };
   volatile ServeHost* vh = hh;
   auto all_done = [&] {
     for (unsigned sv = 0; sv < S; ++sv)
@@ -178,12 +172,11 @@ bool match_rounds_served(cook_engine** es, unsigned n) {
     if (stuck) lead->fail(COOK_E_STATE, "cook_cycle_match_multi: the serve launches stopped finishing");
   }
   // what the pools reached
-  std::vector<WinCtl> hc(L);
-  for (unsigned x = 0; x < L; ++x) COOK_HIP(hipMemcpyAsync(&lead->h_multi[x], hctx[x].vb.ctl, sizeof(WinCtl), hipMemcpyDeviceToHost, s0));
+  std::vector<WinCtl> hc;
   COOK_HIP(hipMemcpyAsync(hs.data(), sctl, S * sizeof(ServeCtl), hipMemcpyDeviceToHost, s0));
   static const bool serve_trace = std::getenv("COOK_SERVE_TRACE") != nullptr;
   if (serve_trace) COOK_HIP(hipMemcpyAsync(hslots.data(), slots, L * sizeof(ServeSlot), hipMemcpyDeviceToHost, s0));
-  COOK_HIP(hipStreamSynchronize(s0));
+  pools_read_ctl(lead, hctx, hc, s0);  // (synchronises s0: the two copies above have arrived too)
   if (serve_trace) {  // the walkers' and the servers' own accounts of the call (100 MHz ticks -> microseconds)
     for (unsigned x = 0; x < L; ++x)
       std::fprintf(stderr, "SERVETRACE pool %u: %u windows waited for, %.1f us each from request to lists, %.1f us from the end of a round to its request\n", x,
@@ -197,9 +190,8 @@ bool match_rounds_served(cook_engine** es, unsigned n) {
   }
   bool complete = true;
   for (unsigned x = 0; x < L; ++x) {
-    hc[x] = lead->h_multi[x];
-    live[x]->deferred_c0 = hc[x];  // (where a lockstep continuation would start)
-    complete = complete && hc[x].head >= live[x]->deferred_k;
+    live[x]->placement.c0 = hc[x];  // (where a lockstep continuation would start)
+    complete = complete && hc[x].head >= live[x]->placement.k;
   }
   lead->served.mode = stepping ? 2u : 1u;
   lead->served.pools = L;
@@ -214,11 +206,6 @@ bool match_rounds_served(cook_engine** es, unsigned n) {
     lead->served.fell_back = 1;
     return false;
   }
-  for (unsigned x = 0; x < L; ++x) {
-    cook_engine* ex = live[x];
-    match_finish_rounds(ex, hctx[x].st, hctx[x].vb, hc[x], s0);
-    ex->has_deferred = false;
-    ex->match_done = true;
-  }
+  for (unsigned x = 0; x < L; ++x) match_finish_rounds(live[x], hctx[x].st, hctx[x].vb, hc[x], s0);
   return true;
 }
