@@ -6,17 +6,28 @@
 // and without constraints whose candidates are all on the board and acceptable, no second offer inside the guard band, and not the placement that
 // ends an epoch.  Anything else leaves with status 1 BEFORE any state has changed, and the C++ step does it.
 //
+// CF_ASM_DECIDER_RUN is a RUN of such steps: one behind the other inside one asm statement, until the batch's todo mask is empty or a step is not plain.
+// The state of the walk stays in the fixed registers below from step to step (the compiler's wrapper builds them once per run and reads them back once);
+// what does not change per step is not computed per step: the overlay lane's offer's attribute bytes stay in v[114:115] (loaded at the run's head and where
+// a lane opens; the C++ step reads them from LDS), the board's row moves on by one row with a compare-and-select for the wrap, and the next job's slot,
+// tag and head word are made in the issue slots the wave maximum's DPP wait states leave empty.
+// The loop adds no wait, no barrier and no word another wave reads: a step's LDS stores and their order (head word, member zeroed, removal count, log
+// entry) are the single step's, so the class waves see the sequence of words they saw, and the exactness arguments of DESIGN.md 4b hold as they are.
+//
 // Registers (physical, bound by the asm constraints in classfit_walk.hpp):
 //   v[64:79]  the lane: v64 valid, v65 offer, v[66:67] 0.5 / Tc, v[68:69] 0.5 / Tm, v70 class, v71 free cpus, v72 free mem, v73 removals of "its" class wave
-//             so far (lanes 58..63), v74 / v75 the last two removed positions, v76 the batch's results (lane = batch slot)
-//   v[80:87]  v80 / v81 / v82 the batch's jobs: cpus, mem, meta (lane = batch slot), v83 the lane's column of the board (bytes), v84 the lane number
+//             so far (lanes 58..63), v74 / v75 the last two removed positions, v76 the batch's results (lane = batch slot), v77 IN / OUT LDS address of the next log entry
+//   v[80:87]  v80 / v81 / v82 the batch's jobs: cpus, mem, meta (lane = batch slot), v83 LDS address of the lane's column of the board's row 0, v84 the lane number,
+//             v85 / v86 the batch's jobs' EQUALS constraints (two per word), v87 LDS address of the fixed records (CfFixed)
 //   s[36:43]  s36 matched so far, s37 least free cpus of any offer, s[38:39] jobs of the batch some offer lacks room for, s40 least free mem,
-//             s41 OUT status: 0 nobody takes the job, 1 not a plain step (nothing changed), 2 placed (one log entry written)
-//   s[44:51]  s44 batch lane of the job, s45 the tag a candidate must carry (job << 12 | generation << 8), s46 LDS address of the board's row, s47 the
-//             head word, s48 LDS address of the log entry, s49 / s50 least cpus / mem any job asks for, s51 LDS address of the fixed records (CfFixed)
-//   s[52:59]  s[52:53] the candidate lanes whose class wave holds hosts without gpus, s[54:55] the overlay's lanes, s56 LDS address of the offers' attribute bytes
-//             (v85 / v86: the batch's jobs' EQUALS constraints, two per word)
-//   clobbered: v[88:119], s[60:83], vcc, scc
+//             s41 OUT status: 0 the run took every job of todo, 1 the first job of todo is not a plain step (nothing of that step has changed),
+//             s[42:43] IN / OUT todo: the batch's walked jobs not decided yet
+//   s[44:51]  s44 batch lane of the job, s45 the tag a candidate must carry (job << 12 | generation << 8), s47 the head word (the run makes the three),
+//             s46 IN the board's row of the first step as a byte offset (cur_ord modulo the rows, times the row's size; the run moves it on),
+//             s49 / s50 least cpus / mem any job asks for, s51 LDS address of the fixed records (CfFixed)
+//   s[52:59]  s[52:53] the candidate lanes whose class wave holds hosts without gpus, s[54:55] the overlay's lanes, s56 LDS address of the offers' attribute
+//             bytes, s57 IN / OUT cur_ord (the walked ordinal of the first job of todo), s59 first job of the batch << 12 | generation << 8
+//   clobbered: v[88:119], s[60:86], vcc, scc
 // Offsets into CfFixed (static_asserts in classfit_walk.hpp): ctrl 13728, class table 9472 (56 bytes a class, 0.5 / Tc at 32), the arrays' start 15280.
 #pragma once
 // the board's rows (CF_SLOTS_N, classfit_walk.hpp) move everything behind the board in CfFixed: the offsets as strings, per row count
@@ -27,6 +38,7 @@
 #define CF_O_CLS32 "9504"
 #define CF_SLOT_SHIFT "9"
 #define CF_SLOT_N "12"
+#define CF_ROW_END "3072"  // the board's size in bytes
 #elif CF_SLOTS_N == 24
 #define CF_O_CTRL "16800"
 #define CF_O_CTRL4 "16804"
@@ -34,27 +46,41 @@
 #define CF_O_CLS32 "12576"
 #define CF_SLOT_SHIFT "10"
 #define CF_SLOT_N "24"
+#define CF_ROW_END "6144"
 #else
 #error "CF_SLOTS_N: 12 or 24"
 #endif
 #ifndef CF_ASM_WAIT_READS
 #define CF_ASM_WAIT_READS "30"  // (measured on a C4 pool: 44.64 / 44.05 / 43.86 ms at 4 / 12 / 30)
 #endif
-#define CF_ASM_MAX_STEP(ctrl) "v_max_f32_dpp v113, v113, v113 " ctrl "\n\ts_nop 1\n\t"
-#define CF_ASM_DECIDER_STEP                                                                                                             \
-  "v_readlane_b32 s60, v80, s44\n\t"                                                                                                    \
-  "v_readlane_b32 s61, v81, s44\n\t"                                                                                                    \
-  "v_readlane_b32 s62, v82, s44\n\t"                                                                                                    \
-  "s_mov_b32 s41, 1\n\t"                                                                                                                \
-  "s_and_b32 s63, s62, 0xffff00ff\n\t" /* a gpu kind, novel hosts, a group: not a plain step (EQUALS constraints are) */                                                                                                  \
-  "s_cmp_lg_u32 s63, 0\n\t"                                                                                                             \
-  "s_cbranch_scc1 9f\n\t"                                                                                                               \
+#ifdef CF_DELAY_D  // robustness study: a slow decider
+#define CF_ASM_DELAY_D "s_sleep 6\n\t"
+#else
+#define CF_ASM_DELAY_D
+#endif
+#define CF_ASM_DECIDER_RUN \
+  /* ---- once per run: the live lanes' offers' attribute bytes (the read lands under the first step's board read); the first job's slot, tag and head word */ \
+  "v_lshl_add_u32 v114, v65, 3, s56\n\t" \
+  "ds_read_b64 v[114:115], v114\n\t" \
+  "s_ff1_i32_b64 s44, s[42:43]\n\t" \
+  "s_lshl_b32 s45, s44, 12\n\t" \
+  "s_add_u32 s45, s45, s59\n\t" \
+  "s_lshl_b32 s47, s57, 8\n\t" \
+  "s_or_b32 s47, s47, s44\n\t" \
+  "s_mov_b32 s41, 1\n\t" /* the status of every way out but the run's end */ \
+  /* ---- a step.  s44 / s45 / s47 are this job's (the step before, or the lines above, made them) */ \
+  "0:\n\t" \
+  "v_readlane_b32 s60, v80, s44\n\t" \
+  "v_readlane_b32 s61, v81, s44\n\t" \
+  "v_readlane_b32 s62, v82, s44\n\t" \
+  "s_and_b32 s63, s62, 0xffff00ff\n\t" /* a gpu kind, novel hosts, a group: not a plain step (EQUALS constraints are) */ \
+  "s_cmp_lg_u32 s63, 0\n\t" \
+  "s_cbranch_scc1 9f\n\t" \
   /* the head word; the candidates' entries */                                                                                         \
   "v_mov_b32_e32 v88, s47\n\t"                                                                                                          \
-  "v_mov_b32_e32 v89, s51\n\t"                                                                                                          \
   "v_add_u32_e32 v100, s46, v83\n\t"                                                                                                    \
   "s_mov_b64 exec, 1\n\t"                                                                                                               \
-  "ds_write_b32 v89, v88 offset:" CF_O_CTRL4 "\n\t"                                                                                              \
+  "ds_write_b32 v87, v88 offset:" CF_O_CTRL4 "\n\t"                                                                                              \
   "s_mov_b64 exec, -1\n\t"                                                                                                              \
   "s_mov_b32 s82, " CF_ASM_WAIT_READS "\n\t" /* reads of the entries before a missing answer makes this the C++ step's job */             \
   "1:\n\t"                                                                                                                              \
@@ -62,9 +88,6 @@
   "ds_read_b64 v[94:95], v100 offset:8\n\t"                                                                                             \
   "ds_read_b128 v[96:99], v100 offset:16\n\t"                                                                                           \
   "ds_read_b32 v93, v100\n\t"                                                                                                           \
-  "v_lshlrev_b32_e32 v114, 3, v65\n\t" /* the lane's offer's attribute bytes (read whatever the job: two instructions and an LDS slot) */ \
-  "v_add_u32_e32 v114, s56, v114\n\t"                                                                                                   \
-  "ds_read_b64 v[114:115], v114\n\t"                                                                                                    \
   /* the overlay's fitness while the loads fly: 1 - ((fc - c) * 0.5 / Tc + (fm - m) * 0.5 / Tm) */                                      \
   "v_subrev_u32_e32 v101, s60, v71\n\t"                                                                                                 \
   "v_subrev_u32_e32 v102, s61, v72\n\t"                                                                                                 \
@@ -181,26 +204,37 @@
   "v_cndmask_b32_e64 v111, v99, v105, s[54:55]\n\t"                                                                                     \
   "v_cndmask_b32_e64 v110, 0, v110, s[64:65]\n\t"                                                                                       \
   "v_cndmask_b32_e64 v111, 0, v111, s[64:65]\n\t"                                                                                       \
-  "v_cvt_f32_f64_e32 v112, v[110:111]\n\t"                                                                                              \
-  "s_nop 0\n\t"                                                                                                                         \
-  "v_mov_b32_e32 v113, v112\n\t"                                                                                                        \
-  "s_nop 1\n\t"                                                                                                                         \
-  CF_ASM_MAX_STEP("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")                                                                     \
-  CF_ASM_MAX_STEP("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")                                                                     \
-  CF_ASM_MAX_STEP("row_half_mirror row_mask:0xf bank_mask:0xf")                                                                         \
-  CF_ASM_MAX_STEP("row_mirror row_mask:0xf bank_mask:0xf")                                                                              \
-  CF_ASM_MAX_STEP("row_bcast:15 row_mask:0xa bank_mask:0xf")                                                                            \
-  CF_ASM_MAX_STEP("row_bcast:31 row_mask:0xc bank_mask:0xf")                                                                            \
-  "v_readlane_b32 s63, v113, 63\n\t"                                                                                                    \
-  "s_mov_b32 s41, 0\n\t"                                                                                                                \
-  "s_cmp_eq_u32 s63, 0\n\t"                                                                                                             \
-  "s_cbranch_scc1 9f\n\t" /* nobody takes it */                                                                                         \
-  "s_mov_b32 s41, 1\n\t"                                                                                                                \
-  "v_cmp_eq_f32_e64 s[78:79], s63, v112\n\t"                                                                                            \
-  "v_add_f32_e32 v108, 0x35000000, v112\n\t" /* + 2^-21 */                                                                              \
-  "v_cmp_le_f32_e64 s[76:77], s63, v108\n\t"                                                                                            \
-  "v_and_b32_e32 v109, 0x40000000, v95\n\t"                                                                                             \
-  "v_cmp_ne_u32_e64 s[70:71], 0, v109\n\t"                                                                                              \
+  "v_cvt_f32_f64_e32 v112, v[110:111]\n\t" \
+  /* the wave maximum: a DPP step reads v113 two wait states behind the instruction that wrote it.  Independent instructions hold those slots: the NEXT job's */ \
+  /* slot (s[84:85] = todo without this job, s86), head word (s47) and tag (s45), the board's next row (s46), and this step's band and tie-flag masks. */ \
+  /* None of them is state the C++ step reads: a step that leaves with status 1 behind this point leaves todo, cur_ord, the minima and the log as they were. */ \
+  "s_mov_b64 s[84:85], s[42:43]\n\t" \
+  "v_mov_b32_e32 v113, v112\n\t" \
+  "s_bitset0_b64 s[84:85], s44\n\t" \
+  "s_add_u32 s46, s46, 256\n\t" \
+  "v_max_f32_dpp v113, v113, v113 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t" \
+  "s_ff1_i32_b64 s86, s[84:85]\n\t" \
+  "s_add_u32 s62, s57, 1\n\t" \
+  "v_max_f32_dpp v113, v113, v113 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t" \
+  "s_cmp_eq_u32 s46, " CF_ROW_END "\n\t" \
+  "s_cselect_b32 s46, 0, s46\n\t" \
+  "v_max_f32_dpp v113, v113, v113 row_half_mirror row_mask:0xf bank_mask:0xf\n\t" \
+  "s_lshl_b32 s62, s62, 8\n\t" \
+  "s_or_b32 s47, s62, s86\n\t" \
+  "v_max_f32_dpp v113, v113, v113 row_mirror row_mask:0xf bank_mask:0xf\n\t" \
+  "s_lshl_b32 s63, s86, 12\n\t" \
+  "s_add_u32 s45, s59, s63\n\t" \
+  "v_max_f32_dpp v113, v113, v113 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
+  "v_add_f32_e32 v108, 0x35000000, v112\n\t" \
+  "v_and_b32_e32 v109, 0x40000000, v95\n\t" \
+  "v_max_f32_dpp v113, v113, v113 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
+  "v_cmp_ne_u32_e64 s[70:71], 0, v109\n\t" \
+  "s_nop 0\n\t" \
+  "v_readlane_b32 s63, v113, 63\n\t" \
+  "s_cmp_eq_u32 s63, 0\n\t" \
+  "s_cbranch_scc1 8f\n\t" /* nobody takes it */ \
+  "v_cmp_eq_f32_e64 s[78:79], s63, v112\n\t" \
+  "v_cmp_le_f32_e64 s[76:77], s63, v108\n\t" /* v108: the lane's fitness + 2^-21 */ \
   "s_and_b64 s[76:77], s[76:77], s[64:65]\n\t" /* lanes whose fitness may round to the greatest */                                     \
   "s_bcnt1_i32_b64 s62, s[76:77]\n\t"                                                                                                   \
   "s_cmp_gt_u32 s62, 1\n\t"                                                                                                             \
@@ -221,11 +255,10 @@
   "v_cmp_eq_u32_e64 vcc, s82, v84\n\t"                                                                                                  \
   "v_mov_b32_e32 v88, s67\n\t"                                                                                                          \
   "v_mov_b32_e32 v89, s70\n\t"                                                                                                          \
-  "s_cmp_lt_u32 s67, s49\n\t"                                                                                                           \
-  "s_cselect_b32 s71, 1, 0\n\t"                                                                                                         \
-  "s_cmp_lt_u32 s70, s50\n\t"                                                                                                           \
-  "s_cselect_b32 s62, 1, 0\n\t"                                                                                                         \
-  "s_or_b32 s71, s71, s62\n\t"                                                                                                          \
+  "s_cmp_lt_u32 s67, s49\n\t" \
+  "s_cselect_b32 s71, 1, 0\n\t" \
+  "s_cmp_lt_u32 s70, s50\n\t" \
+  "s_cselect_b32 s71, 1, s71\n\t" \
   "v_cndmask_b32_e32 v71, v71, v88, vcc\n\t"                                                                                            \
   "v_cndmask_b32_e32 v72, v72, v89, vcc\n\t"                                                                                            \
   "s_cmp_lg_u32 s71, 0\n\t"                                                                                                             \
@@ -248,51 +281,48 @@
   "s_and_b32 s73, s77, 0xffff\n\t"                                                                                                      \
   "s_lshr_b32 s81, s77, 16\n\t"                                                                                                         \
   "s_sub_u32 s80, s82, 57\n\t"                                                                                                          \
-  "s_cmp_lt_u32 s67, s49\n\t"                                                                                                           \
-  "s_cselect_b32 s71, 1, 0\n\t"                                                                                                         \
-  "s_cmp_lt_u32 s70, s50\n\t"                                                                                                           \
-  "s_cselect_b32 s62, 1, 0\n\t"                                                                                                         \
-  "s_or_b32 s71, s71, s62\n\t"                                                                                                          \
+  "s_cmp_lt_u32 s67, s49\n\t" \
+  "s_cselect_b32 s71, 1, 0\n\t" \
+  "s_cmp_lt_u32 s70, s50\n\t" \
+  "s_cselect_b32 s71, 1, s71\n\t" \
   "s_bcnt1_i32_b64 s62, s[68:69]\n\t"                                                                                                   \
   "s_cmp_lg_u32 s71, 0\n\t"                                                                                                             \
   "s_cbranch_scc1 6f\n\t"                                                                                                               \
   "s_cmp_ge_u32 s62, " CF_ASM_EPOCH_LIVE "\n\t"                                                                                          \
   "s_cbranch_scc1 9f\n\t" /* the placement that fills the overlay: the epoch's end is the C++ step's */                                 \
   "6:\n\t"                                                                                                                              \
-  "s_lshl_b32 s62, s73, 3\n\t"                                                                                                          \
-  "s_add_u32 s62, s62, s51\n\t"                                                                                                         \
-  "s_lshl_b32 s63, s80, 2\n\t"                                                                                                          \
-  "s_add_u32 s63, s63, s51\n\t"                                                                                                         \
-  "s_add_u32 s78, s78, 1\n\t"                                                                                                           \
-  "v_mov_b32_e32 v88, 0\n\t"                                                                                                            \
-  "v_mov_b32_e32 v89, 0\n\t"                                                                                                            \
-  "v_mov_b32_e32 v90, s62\n\t"                                                                                                          \
-  "v_mov_b32_e32 v91, s63\n\t"                                                                                                          \
+  "s_lshl_b32 s62, s73, 3\n\t" \
+  "s_lshl_b32 s63, s80, 2\n\t" \
+  "s_add_u32 s78, s78, 1\n\t" \
+  "v_mov_b32_e32 v88, 0\n\t" \
+  "v_mov_b32_e32 v89, 0\n\t" \
+  "v_add_u32_e32 v90, s62, v87\n\t" \
+  "v_add_u32_e32 v91, s63, v87\n\t" \
   "v_mov_b32_e32 v100, s78\n\t"                                                                                                         \
   "s_mov_b64 exec, 1\n\t"                                                                                                               \
   "ds_write_b64 v90, v[88:89] offset:" CF_O_ARR "\n\t"                                                                                         \
   "ds_write_b32 v91, v100 offset:" CF_O_CTRL4 "\n\t"                                                                                             \
   "s_mov_b64 exec, -1\n\t"                                                                                                              \
   "v_cmp_eq_u32_e64 vcc, s82, v84\n\t"                                                                                                  \
-  "v_mov_b32_e32 v101, s73\n\t"                                                                                                         \
-  "s_nop 0\n\t"                                                                                                                         \
-  "v_cndmask_b32_e32 v75, v75, v74, vcc\n\t"                                                                                            \
-  "v_cndmask_b32_e32 v74, v74, v101, vcc\n\t"                                                                                           \
-  "v_cndmask_b32_e32 v73, v73, v100, vcc\n\t"                                                                                           \
-  "s_lshl_b32 s62, s80, 8\n\t"                                                                                                          \
+  "v_mov_b32_e32 v101, s73\n\t" \
+  "s_lshl_b32 s62, s80, 8\n\t" \
+  "v_cndmask_b32_e32 v75, v75, v74, vcc\n\t" \
+  "v_cndmask_b32_e32 v74, v74, v101, vcc\n\t" \
+  "v_cndmask_b32_e32 v73, v73, v100, vcc\n\t" \
   "s_lshl_b32 s63, s81, 12\n\t"                                                                                                         \
   "s_or_b32 s72, s44, s62\n\t"                                                                                                          \
   "s_or_b32 s72, s72, s63\n\t"                                                                                                          \
   "s_cmp_lg_u32 s71, 0\n\t"                                                                                                             \
   "s_cbranch_scc1 7f\n\t" /* dead at once: nothing opens */                                                                             \
-  "s_mul_i32 s62, s79, 56\n\t"                                                                                                          \
-  "s_add_u32 s62, s62, s51\n\t"                                                                                                         \
-  "v_mov_b32_e32 v90, s62\n\t"                                                                                                          \
-  "ds_read_b128 v[116:119], v90 offset:" CF_O_CLS32 "\n\t"                                                                                        \
+  "s_mul_i32 s62, s79, 56\n\t" \
+  "v_add_u32_e32 v90, s62, v87\n\t" \
+  "ds_read_b128 v[116:119], v90 offset:" CF_O_CLS32 "\n\t"  \
+  "v_mov_b32_e32 v88, s66\n\t" \
+  "v_lshl_add_u32 v102, v88, 3, s56\n\t" /* the new lane's offer's attribute bytes: one more read under the wait below */  \
+  "ds_read_b64 v[102:103], v102\n\t"                                                                                        \
   "s_andn2_b64 s[62:63], s[54:55], s[68:69]\n\t"                                                                                        \
   "s_ff1_i32_b64 s83, s[62:63]\n\t"                                                                                                     \
   "v_cmp_eq_u32_e64 vcc, s83, v84\n\t"                                                                                                  \
-  "v_mov_b32_e32 v88, s66\n\t"                                                                                                          \
   "v_mov_b32_e32 v89, s79\n\t"                                                                                                          \
   "v_mov_b32_e32 v91, s67\n\t"                                                                                                          \
   "v_mov_b32_e32 v101, s70\n\t"                                                                                                         \
@@ -305,7 +335,9 @@
   "v_cndmask_b32_e32 v66, v66, v116, vcc\n\t"                                                                                           \
   "v_cndmask_b32_e32 v67, v67, v117, vcc\n\t"                                                                                           \
   "v_cndmask_b32_e32 v68, v68, v118, vcc\n\t"                                                                                           \
-  "v_cndmask_b32_e32 v69, v69, v119, vcc\n\t"                                                                                           \
+  "v_cndmask_b32_e32 v69, v69, v119, vcc\n\t"  \
+  "v_cndmask_b32_e32 v114, v114, v102, vcc\n\t" \
+  "v_cndmask_b32_e32 v115, v115, v103, vcc\n\t"                                                                                           \
   /* ---- the books of a placement: the result, the jobs behind it some offer has no room for any more, the least free values, the log */ \
   "7:\n\t"                                                                                                                              \
   "v_cmp_eq_u32_e64 vcc, s44, v84\n\t"                                                                                                  \
@@ -323,13 +355,22 @@
   "v_mov_b32_e32 v88, s72\n\t"                                                                                                          \
   "v_mov_b32_e32 v89, s73\n\t"                                                                                                          \
   "v_mov_b32_e32 v90, s64\n\t"                                                                                                          \
-  "v_mov_b32_e32 v91, s65\n\t"                                                                                                          \
-  "v_mov_b32_e32 v100, s48\n\t"                                                                                                         \
-  "s_mov_b64 exec, 1\n\t"                                                                                                               \
-  "ds_write_b128 v100, v[88:91]\n\t"                                                                                                    \
-  "s_mov_b64 exec, -1\n\t"                                                                                                              \
-  "s_mov_b32 s41, 2\n\t"                                                                                                                \
-  "9:\n\t"
+  "v_mov_b32_e32 v91, s65\n\t" \
+  "s_mov_b64 exec, 1\n\t" \
+  "ds_write_b128 v77, v[88:91]\n\t" \
+  "s_mov_b64 exec, -1\n\t" \
+  "v_add_u32_e32 v77, 32, v77\n\t" /* the next log entry */ \
+  /* ---- the next job, or the run's end */ \
+  "8:\n\t" \
+  CF_ASM_DELAY_D \
+  "s_mov_b64 s[42:43], s[84:85]\n\t" \
+  "s_mov_b32 s44, s86\n\t" \
+  "s_add_u32 s57, s57, 1\n\t" \
+  "s_cmp_lg_u64 s[42:43], 0\n\t" \
+  "s_cbranch_scc1 0b\n\t" \
+  "s_mov_b32 s41, 0\n\t" \
+  "9:\n\t" \
+  "s_waitcnt lgkmcnt(0)\n\t" /* (a read of a step that left, or of the run's head, must not land in a register the compiler has back) */
 
 // ---- a class wave's PLAIN answer ------------------------------------------------------------------------------------------------------------------------------
 // One pass of a class wave that holds ONE class: the three words the decider writes, the jobs of the set's other waves skipped, the run-ahead limit, the job,

@@ -72,6 +72,7 @@ bool cf_setup(cook_engine* e, const MatchIn& in, const MatchIn* in_dev, const Ma
 static void cf_prof_print(const uint32_t* q) {
 #ifdef CF_PROF
   std::fprintf(stderr, "CFPROF (x16 shader cycles) decider: slow steps %u (candidates %u evaluation %u commit %u) plain steps %u in %u walk-total %u | class wave 1: poll %u answer %u answers %u idle %u idles %u | class wave 2: poll %u answer %u answers %u idle %u idles %u | walk ticks(100MHz) %u | batch boundaries: decider %u, batches without a walked job %u\n", q[27], q[24], q[25], q[26], q[28], q[29], q[31], q[32], q[33], q[35], q[36], q[37], q[40], q[41], q[43], q[44], q[45], q[CFS_TICKS_WALK], q[30], q[38]);
+  std::fprintf(stderr, "CFPROF plain steps %u, C++ steps %u; steps that left the plain form: gpu kind %u, novel hosts %u, group %u, answer missing after the re-reads %u, guard band %u, epoch end %u\n", q[46], q[47], q[34] & 65535u, q[34] >> 16, q[39] & 65535u, q[39] >> 16, q[42] & 65535u, q[42] >> 16);
 #else
   (void)q;
 #endif

@@ -34,9 +34,15 @@
 #ifdef CF_PROF  // timing-study build: shader cycles (s_memtime) per phase of the decider's steps and of class wave 1's answers, to CfCtl::stats[24..]
 #define CF_PROF_T(x) const unsigned long long x = __builtin_readcyclecounter()
 #define CF_PROF_ADD(i, d) prof[i] += (unsigned long long)(d)
+// why a step left the plain form (the C++ steps of the GPU build are exactly these): 0 a gpu kind, 1 novel hosts, 2 a group, 3 an answer missing after the
+// re-reads, 4 two candidates inside the guard band (or a tie flag), 5 the placement that ends an epoch.  The job's own reasons come first, then 4, 5, and 3 is the rest.
+#define CF_PROF_WHY(n) why = why == 3u ? (n) : why
+#define CF_PROF_LEAVE() (why < 4u ? leave_a += 1ull << (16u * why) : leave_b += 1ull << (16u * (why - 4u)))  // 16 bits a reason (a C4 pool has 3.5k such steps)
 #else
 #define CF_PROF_T(x) ((void)0)
 #define CF_PROF_ADD(i, d) ((void)0)
+#define CF_PROF_WHY(n) ((void)0)
+#define CF_PROF_LEAVE() ((void)0)
 #endif
 
 #ifndef CF_AHEAD
@@ -386,6 +392,7 @@ static_assert(offsetof(CfFixed, pw) % 16 == 0 && offsetof(CfFixed, aw) % 16 == 0
 #define CF_ASM_EPOCH_LIVE "57"
 #include "classfit_asm.hpp"
 static_assert(CF_EPOCH_AT == 58 && CF_OVL == 58, "classfit_asm.hpp: the overlay's size");
+static_assert(sizeof(CfEnt) * 8u == 256u && sizeof(CfEnt) * 8u * CF_SLOTS == 3072u + (CF_SLOTS - 12u) * 256u, "classfit_asm.hpp: a row of the board is 256 bytes, CF_ROW_END the board's size");
 static_assert(offsetof(CfFixed, ctrl) == 13728 + (CF_SLOTS - 12) * 256 && offsetof(CfFixed, cls) == 9472 + (CF_SLOTS - 12) * 256 && sizeof(CfFixed) == 15280 + (CF_SLOTS - 12) * 256 && sizeof(CfClass) == 56 && offsetof(CfClass, hTc) == 32 &&
                   offsetof(CfClass, hTm) == 40 && offsetof(CfEnt, pos) == 8 && offsetof(CfEnt, cid) == 12 && offsetof(CfEnt, fc) == 16 && offsetof(CfEnt, fa) == 24 && sizeof(CfEnt) == 32 &&
                   sizeof(CfLog) == 32 && offsetof(CfLog, ofc) == 8,
@@ -457,6 +464,7 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
   unsigned long long tk_epoch = 0, tk_books = 0, tk_walk = 0, tk_phase1 = 0;
 #ifdef CF_PROF
   unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bnd0 = 0ull;
+  unsigned long long leave_a = 0ull, leave_b = 0ull;
 #endif
   auto job_of = [&](unsigned s) -> CfJobU {
     CfJobU J;
@@ -581,15 +589,13 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
 #if COOK_HAS_ASM_WALK
         // the lane's state and the batch's jobs as the hand-placed step holds them (classfit_asm.hpp)
         cf_u32x16 ST = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-        cf_u32x8 JB = {jc, jm, jmeta, clw * 32u, lane, jeq0, jeq1, 0u};
-        const unsigned long long rel0 = cook_ballot(!isov & ((my_kinds & 1u) != 0u)), ovm = cf_below(CF_OVL);
-        const cf_u32x8 MK = {wave_uniform_u32((unsigned)rel0), wave_uniform_u32((unsigned)(rel0 >> 32)), wave_uniform_u32((unsigned)ovm), wave_uniform_u32((unsigned)(ovm >> 32)),
-                             wave_uniform_u32(cook_lds_off(S.attr8)), 0u, 0u, 0u};
         const unsigned a_board = wave_uniform_u32(cook_lds_off(S.board)), a_log = wave_uniform_u32(cook_lds_off(S.log));
+        cf_u32x8 JB = {jc, jm, jmeta, a_board + clw * (unsigned)sizeof(CfEnt), lane, jeq0, jeq1, a_board};
+        const unsigned long long rel0 = cook_ballot(!isov & ((my_kinds & 1u) != 0u)), ovm = cf_below(CF_OVL);
         auto st_pack = [&] {
           const unsigned long long hc = (unsigned long long)__double_as_longlong(o.hTc), hm = (unsigned long long)__double_as_longlong(o.hTm);
           ST[0] = o.valid, ST[1] = o.id, ST[2] = (unsigned)hc, ST[3] = (unsigned)(hc >> 32), ST[4] = (unsigned)hm, ST[5] = (unsigned)(hm >> 32), ST[6] = o.cls, ST[7] = o.fc, ST[8] = o.fm,
-          ST[9] = nrm, ST[10] = rm1, ST[11] = rm2, ST[12] = (unsigned)res;
+          ST[9] = nrm, ST[10] = rm1, ST[11] = rm2, ST[12] = (unsigned)res, ST[13] = a_log + logn * (unsigned)sizeof(CfLog);
         };
         auto st_unpack = [&] {
           o.valid = ST[0], o.id = ST[1], o.hTc = __longlong_as_double((long long)((unsigned long long)ST[3] << 32 | ST[2])),
@@ -602,33 +608,28 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
           todo = wave_uniform_u64(todo), cur_ord = wave_uniform_u32(cur_ord), logn = wave_uniform_u32(logn), matched = wave_uniform_u32(matched), gen = wave_uniform_u32(gen);
           minfc_all = wave_uniform_u32(minfc_all), minfm_all = wave_uniform_u32(minfm_all), b1m = wave_uniform_u64(b1m);
 #if COOK_HAS_ASM_WALK
-          {  // plain steps, one behind the other, as long as they are plain (classfit_asm.hpp); the step that is not is the C++ step's below
+          if (todo != 0ull) {  // a run of plain steps, one behind the other inside ONE asm statement (classfit_asm.hpp); the step that is not plain is the C++ step's below.
+            // The run holds todo, cur_ord, the log address (ST[13], the same in every lane), matched, the minima and b1m in fixed registers from step to step: built here once per run, read back once.
+            // It adds no wait, no barrier and no word another wave reads — the class waves see the words of the single steps, in their order.
             st_pack();
             CF_PROF_T(f0);
-            while (todo != 0ull) {
-              const unsigned fs = (unsigned)__ffsll(todo) - 1u;
 #define CF_U(x) wave_uniform_u32((unsigned)(x))
-              cf_u32x8 SC = {CF_U(matched), CF_U(minfc_all), CF_U(b1m), CF_U(b1m >> 32), CF_U(minfm_all), 1u, 0u, 0u};
-              const cf_u32x8 AR = {CF_U(fs), CF_U((base + fs) << 12 | (gen & 15u) << 8), CF_U(a_board + cf_slot(cur_ord) * 8u * (unsigned)sizeof(CfEnt)), CF_U(fs | cur_ord << 8),
-                                   CF_U(a_log + logn * (unsigned)sizeof(CfLog)), CF_U(cmin), CF_U(mmin), a_board};
+            cf_u32x8 SC = {CF_U(matched), CF_U(minfc_all), CF_U(b1m), CF_U(b1m >> 32), CF_U(minfm_all), 1u, CF_U(todo), CF_U(todo >> 32)};
+            cf_u32x8 AR = {0u, 0u, CF_U(cf_slot(cur_ord) * 8u * (unsigned)sizeof(CfEnt)), 0u, 0u, CF_U(cmin), CF_U(mmin), a_board};
+            cf_u32x8 MK = {CF_U(rel0), CF_U(rel0 >> 32), CF_U(ovm), CF_U(ovm >> 32), CF_U(cook_lds_off(S.attr8)), CF_U(cur_ord), 0u, CF_U(base << 12 | (gen & 15u) << 8)};
+            asm volatile(CF_ASM_DECIDER_RUN
+                         : "+{v[64:79]}"(ST), "+{s[36:43]}"(SC), "+{s[44:51]}"(AR), "+{s[52:59]}"(MK)
+                         : "{v[80:87]}"(JB)
+                         : "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108",
+                           "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69",
+                           "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "s84", "s85", "s86", "vcc", "scc", "memory");
+            matched = CF_U(SC[0]), minfc_all = CF_U(SC[1]), minfm_all = CF_U(SC[4]);
+            b1m = wave_uniform_u64((unsigned long long)SC[3] << 32 | SC[2]);
+            todo = wave_uniform_u64((unsigned long long)SC[7] << 32 | SC[6]);
+            logn = (CF_U(ST[13]) - a_log) / (unsigned)sizeof(CfLog);
+            CF_PROF_ADD(4, CF_U(MK[5]) - cur_ord);  // (the run's plain steps: nothing is counted per step)
+            cur_ord = CF_U(MK[5]);
 #undef CF_U
-              asm volatile(CF_ASM_DECIDER_STEP
-                           : "+{v[64:79]}"(ST), "+{s[36:43]}"(SC)
-                           : "{v[80:87]}"(JB), "{s[44:51]}"(AR), "{s[52:59]}"(MK)
-                           : "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "v96", "v97", "v98", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108",
-                             "v109", "v110", "v111", "v112", "v113", "v114", "v115", "v116", "v117", "v118", "v119", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69",
-                             "s70", "s71", "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", "vcc", "scc", "memory");
-#ifdef CF_DELAY_D  // robustness study: a slow decider
-              __builtin_amdgcn_s_sleep(6);
-#endif
-              const unsigned status = wave_uniform_u32(SC[5]);
-              if (status == 1u) break;
-              matched = wave_uniform_u32(SC[0]), minfc_all = wave_uniform_u32(SC[1]), minfm_all = wave_uniform_u32(SC[4]);
-              b1m = wave_uniform_u64((unsigned long long)SC[3] << 32 | SC[2]);
-              logn += status >> 1;
-              todo &= todo - 1ull, ++cur_ord;
-              CF_PROF_ADD(4, 1);
-            }
             CF_PROF_T(f1);
             CF_PROF_ADD(5, f1 - f0);
             WAIT_LDS();  // (the hand-placed step's LDS stores are not on the compiler's books: nothing of them is in flight behind this point)
@@ -651,6 +652,9 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
           const unsigned Jc = (unsigned)wave_read_lane((int)jc, (int)s), Jm = (unsigned)wave_read_lane((int)jm, (int)s), meta = (unsigned)wave_read_lane((int)jmeta, (int)s);
           const unsigned kind = meta & 255u;
           const unsigned want = (base + s) << 12 | (gen & 15u) << 8;
+#ifdef CF_PROF
+          unsigned why = kind != 0u ? 0u : ((meta >> 16) & 15u) ? 1u : ((meta >> 20) & 1u) ? 2u : 3u;
+#endif
           // the candidates of the class waves into lanes 58..63 (every lane reads an entry: no branch on the lane)
           const CfEnt* e = &S.board[cf_slot(ord) * 8u + clw];
           const bool relevant = !isov && kind < 32u && ((my_kinds >> (kind & 31u)) & 1u);
@@ -705,11 +709,13 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
           CF_PROF_ADD(1, p2 - p1);
           CF_PROF_ADD(3, 1);
           if (!(mx > 0.0f)) {  // nobody takes it
+            CF_PROF_LEAVE();
             todo &= todo - 1ull, ++cur_ord;
             continue;
           }
           unsigned l0 = (unsigned)__ffsll(eqm) - 1u;
           if ((nearm & (nearm - 1ull)) != 0ull || ambm != 0ull) {  // rare: the doubles decide whether the guard band holds several
+            CF_PROF_WHY(4u);
             const unsigned long long mxb = wave_max_u64((unsigned long long)__double_as_longlong(fa));
             const double f0 = __longlong_as_double((long long)mxb);
             l0 = (unsigned)__ffsll(__ballot(ok && (unsigned long long)__double_as_longlong(fa) == mxb)) - 1u;
@@ -718,6 +724,7 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
             if (amb) {  // the literal fitness decides: every wave in lockstep
               md = CFM_EXACT;
               if (lane == 0) S.misc[CFX_EX_LANE] = s, S.misc[CFX_FMAX_LO] = (unsigned)mxb, S.misc[CFX_FMAX_HI] = (unsigned)(mxb >> 32), st_wg(&S.ctrl[0], md);
+              CF_PROF_LEAVE();
               break;
             }
           }
@@ -784,8 +791,10 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
           }
           md = wave_uniform_u32(md);  // (a scalar for the compiler too: as a vector value it makes this loop's exit divergent and every counter carried out of it a vector register)
           if (md == CFM_EPOCH) {
+            CF_PROF_WHY(5u);
             if (lane == 0) S.misc[CFX_EX_LANE] = s, S.misc[CFX_LOGN] = logn, st_wg(&S.ctrl[0], md);
           }
+          CF_PROF_LEAVE();
           CF_PROF_T(p3);
           CF_PROF_ADD(2, p3 - p2);
         }
@@ -1303,7 +1312,10 @@ static __device__ __forceinline__ void cf_walk_role(const CfLds& S, const MatchS
   if (is_books && lane == 0) ctl->stats[CFS_TICKS_PRECHECK] = (uint32_t)tk_books, ctl->stats[CFS_FLIPS] = st_flips, ctl->stats[CFS_HWID_BOOKS] = cook_hw_id();
 #ifdef CF_PROF
   if (lane == 0 && (is_decider || (is_class_wave && lw >= 1u && lw <= 2u && rep == 0u)))
-    for (int i = 0; i < 8; ++i) ctl->stats[24 + 8 * (is_decider ? 0u : lw) + i] = (uint32_t)(prof[i] >> 4);  // units of 16 cycles
+    for (int i = 0; i < 8; ++i)
+      if (is_decider || (i != 2 && i != 7 && !(lw == 2u && i == 6))) ctl->stats[24 + 8 * (is_decider ? 0u : lw) + i] = (uint32_t)(prof[i] >> 4);  // units of 16 cycles
+  if (lane == 0 && is_decider)  // the decider's leave reasons, 16 bits each, in the words the class waves' counters leave free
+    ctl->stats[34] = (uint32_t)leave_a, ctl->stats[39] = (uint32_t)(leave_a >> 32), ctl->stats[42] = (uint32_t)leave_b, ctl->stats[46] = (uint32_t)prof[4], ctl->stats[47] = (uint32_t)prof[3];  // (the two step counts once more, not in sixteens)
 #endif
 #undef n_cls
 #undef n_kind
