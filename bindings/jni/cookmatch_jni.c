@@ -639,6 +639,43 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleAutoscale(JNIEnv* env, jclass c
   if ((p.n_exclude && !p.exclude_task) || (cap && !out)) return COOK_E_INVALID;
   return CHECKED(cook_cycle_autoscale(H(h), &p, out, (uint32_t)cap, info));
 }
+/* cycleAutoscale for n engines of one device in ONE call (cook_cycle_autoscale_multi).  params = direct buffer of n cook_autoscale_params
+ * (max_jobs, n_exclude, scale_factor read; the pointer fields ignored); n_offers = direct buffer of n jint; offer_skipped / exclude /
+ * task_idx_out = arrays of n direct buffers (a null array or element: none): n_offers[i] bytes, n_exclude task indices, caps[i] uint32 slots;
+ * caps = direct buffer of n jint; info_out = direct buffer of n cook_autoscale_info or null; rc_out = direct buffer of n jint or null */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleAutoscaleMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n,
+                                                                jobject params, jobject n_offers, jobjectArray offer_skipped,
+                                                                jobjectArray exclude, jobjectArray task_idx_out, jobject caps,
+                                                                jobject info_out, jobject rc_out) {
+  cook_engine* es[64];
+  cook_autoscale_params ps[64];
+  const cook_autoscale_params* pp[64];
+  uint32_t* outs[64];
+  uint32_t cs[64];
+  int bad = 0;
+  const jint cnt = n > 0 ? n : 0;
+  const int64_t* hs = BUFN(const int64_t, handles, cnt);
+  const cook_autoscale_params* in = BUFN(const cook_autoscale_params, params, cnt);
+  const int32_t* no = BUFN(const int32_t, n_offers, cnt);
+  const int32_t* cp = BUFN(const int32_t, caps, cnt);
+  cook_autoscale_info* info = BUFN(cook_autoscale_info, info_out, cnt);
+  int* rcs = BUFN(int, rc_out, cnt);
+  jint i;
+  (void)c;
+  if (bad || !hs || !in || !no || !cp || n <= 0 || n > 64) return COOK_E_INVALID;
+  for (i = 0; i < n; ++i) {
+    if (no[i] < 0 || cp[i] < 0 || in[i].n_exclude > 0x7fffffffu) return COOK_E_INVALID;
+    es[i] = H(hs[i]);
+    ps[i] = in[i];
+    ps[i].offer_skipped = EL(const uint8_t, offer_skipped, i, no[i]);
+    ps[i].exclude_task = EL(const uint32_t, exclude, i, ps[i].n_exclude);
+    outs[i] = EL(uint32_t, task_idx_out, i, cp[i]);
+    cs[i] = (uint32_t)cp[i];
+    pp[i] = &ps[i];
+    if ((ps[i].n_exclude && !ps[i].exclude_task) || (cs[i] && !outs[i])) return COOK_E_INVALID;
+  }
+  return CHECKED(cook_cycle_autoscale_multi(es, (uint32_t)n, pp, outs, cs, info, rcs));
+}
 
 /* ---- the task killers over the running set (cook_sweep_running) -------------------------------------------------------------------
  * rows = n-entry columns {start_ms int64, unknown uint8, max_runtime_ms int64, cancelled uint8, group uint32} (null elements allowed as
@@ -837,6 +874,38 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_matchMetrics(JNIEnv* env, jclass c, 
   int64_t *jg = BUFN(int64_t, job_gpus_out, (uint64_t)n_gpu_models + 1u), *og = BUFN(int64_t, offer_gpus_out, (uint64_t)n_gpu_models + 1u);
   (void)c;
   return CHECKED(cook_match_metrics(H(h), m, uc, um, (uint32_t)n_users, jg, og, (uint32_t)n_gpu_models));
+}
+/* matchMetrics for n engines of one device in ONE call (cook_match_metrics_multi).  metrics_out = direct buffer of n cook_cycle_metrics;
+ * n_users / n_gpu_models = direct buffers of n jint; user_considerable_out / user_matched_out (n_users[i] uint32 each) and job_gpus_out /
+ * offer_gpus_out (n_gpu_models[i] + 1 int64 each) = arrays of n direct buffers, a null array or element: left out; rc_out = n jint or null */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_matchMetricsMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n,
+                                                              jobject metrics_out, jobject n_users, jobjectArray user_considerable_out,
+                                                              jobjectArray user_matched_out, jobject n_gpu_models, jobjectArray job_gpus_out,
+                                                              jobjectArray offer_gpus_out, jobject rc_out) {
+  cook_engine* es[64];
+  cook_metrics_req rq[64];
+  int bad = 0;
+  const jint cnt = n > 0 ? n : 0;
+  const int64_t* hs = BUFN(const int64_t, handles, cnt);
+  cook_cycle_metrics* ms = BUFN(cook_cycle_metrics, metrics_out, cnt);
+  const int32_t* nu = BUFN(const int32_t, n_users, cnt);
+  const int32_t* nm = BUFN(const int32_t, n_gpu_models, cnt);
+  int* rcs = BUFN(int, rc_out, cnt);
+  jint i;
+  (void)c;
+  if (bad || !hs || !ms || !nu || !nm || n <= 0 || n > 64) return COOK_E_INVALID;
+  for (i = 0; i < n; ++i) {
+    if (nu[i] < 0 || nm[i] < 0) return COOK_E_INVALID;
+    es[i] = H(hs[i]);
+    rq[i].out = &ms[i];
+    rq[i].user_considerable = EL(uint32_t, user_considerable_out, i, nu[i]);
+    rq[i].user_matched = EL(uint32_t, user_matched_out, i, nu[i]);
+    rq[i].n_users = (uint32_t)nu[i];
+    rq[i].n_gpu_models = (uint32_t)nm[i];
+    rq[i].job_gpus_by_model = EL(int64_t, job_gpus_out, i, (uint64_t)nm[i] + 1u);
+    rq[i].offer_gpus_by_model = EL(int64_t, offer_gpus_out, i, (uint64_t)nm[i] + 1u);
+  }
+  return CHECKED(cook_match_metrics_multi(es, (uint32_t)n, rq, rcs));
 }
 /* the rows of the last offersRun as the offers of a match / cycle, in place on the device */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_matchStageBuiltOffers(JNIEnv* env, jclass c, jlong h, jint k, jint n_scalars, jobjectArray jobs,

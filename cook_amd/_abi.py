@@ -874,6 +874,13 @@ class CookCycleMetrics(C.Structure):
                 ("reserved", C.c_uint32 * 2), ("jobs", CookResourceStats), ("offer_stats", CookResourceStats)]
 
 
+class CookMetricsReq(C.Structure):
+    """cook_metrics_req: the arguments of cook_match_metrics for one engine of a cook_match_metrics_multi call"""
+    _fields_ = [("out", C.POINTER(CookCycleMetrics)), ("user_considerable", C.POINTER(C.c_uint32)), ("user_matched", C.POINTER(C.c_uint32)),
+                ("n_users", C.c_uint32), ("n_gpu_models", C.c_uint32), ("job_gpus_by_model", C.POINTER(C.c_int64)),
+                ("offer_gpus_by_model", C.POINTER(C.c_int64))]
+
+
 CONSTRAINT_MESSAGES = {  # unscheduled.clj:71-75 constraint-name->message
     "novel_host_constraint": "Job already ran on this host.",
     "gpu_host_constraint": "Host has no GPU support.",

@@ -121,6 +121,7 @@ struct cook_engine {
   uint32_t* permC = nullptr;  // final global order
   // the last cook_cycle_run_rank_multi led by this engine: pools, launches, of them for several pools, operations issued alone, synchronisations
   unsigned batch_stats[5] = {0, 0, 0, 0, 0};
+  unsigned any_batch_stats[5] = {0, 0, 0, 0, 0};  // the same five of the last pool batch of ANY call led by this engine (cook_batch_stats)
   DArr<uint32_t> permC1, permC2;
   unsigned n_ranked = 0;
 
@@ -217,6 +218,7 @@ struct cook_engine {
   std::unique_ptr<UsageBufs> ugb;      // cook_usage_breakdown* (allocated on first use)
   MatchIn last_in{};  // the MatchIn of the last match run (K, j_index as used)
   bool last_in_valid = false;
+  bool v_in_is_last = false;  // v_in holds last_in on the device (the window rounds' set-up of the last match uploaded it)
   unsigned rlog_id = 0;  // suffix of this engine's COOK_ROUND_LOG file
   DArr<uint32_t> j_user;
   bool has_j_user = false;
@@ -747,6 +749,20 @@ int cook_cycle_autoscale(cook_engine* e, const cook_autoscale_params* p, uint32_
     prof_collect(e);
   });
 }
+// ... for every pool of a GPU: one flow per pool in a pool batch; the argument checks run inside the flows (per-engine errors)
+int cook_cycle_autoscale_multi(cook_engine** engines, uint32_t n, const cook_autoscale_params* const* params, uint32_t* const* task_idx,
+                               const uint32_t* cap, cook_autoscale_info* info, int* rc) {
+  if (!engines || n == 0 || !params || !cap) return COOK_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i)
+    if (!engines[i] || !params[i]) return COOK_E_INVALID;
+  if (!engines_valid(engines, n, false)) return COOK_E_INVALID;
+  auto out = [&](uint32_t i) { return task_idx ? task_idx[i] : nullptr; };  // (a missing array with cap[i] > 0: engine i's own "null task_idx")
+  if (info)
+    for (uint32_t i = 0; i < n; ++i) info[i] = cook_autoscale_info{};
+  return run_pools_batched(
+      engines, n, [&](uint32_t i) { return cook_cycle_autoscale(engines[i], params[i], out(i), cap[i], info ? &info[i] : nullptr); },
+      [&](uint32_t i) { cycle_autoscale(engines[i], params[i], out(i), cap[i], info ? &info[i] : nullptr); }, /*rank_part=*/false, rc);
+}
 
 int cook_sweep_running(cook_engine* e, const cook_running_set* tasks, const cook_straggler_groups* groups, const cook_sweep_params* p,
                        uint8_t* reason, uint32_t* idx, uint32_t cap, double* group_threshold_s, cook_sweep_info* info) {
@@ -812,6 +828,28 @@ int cook_match_metrics(cook_engine* e, cook_cycle_metrics* out, uint32_t* user_c
     match_metrics(e, bufs(e->xb), out, user_considerable, user_matched, n_users, job_gpus_by_model, offer_gpus_by_model, n_gpu_models);
     prof_collect(e);
   });
+}
+int cook_match_metrics_multi(cook_engine** engines, uint32_t n, const cook_metrics_req* req, int* rc) {
+  if (!engines || n == 0 || !req) return COOK_E_INVALID;
+  if (!engines_valid(engines, n, false)) return COOK_E_INVALID;
+  return run_pools_batched(
+      engines, n,
+      [&](uint32_t i) {
+        const cook_metrics_req& r = req[i];
+        return cook_match_metrics(engines[i], r.out, r.user_considerable, r.user_matched, r.n_users, r.job_gpus_by_model, r.offer_gpus_by_model,
+                                  r.n_gpu_models);
+      },
+      [&](uint32_t i) {
+        const cook_metrics_req& r = req[i];
+        match_metrics(engines[i], bufs(engines[i]->xb), r.out, r.user_considerable, r.user_matched, r.n_users, r.job_gpus_by_model,
+                      r.offer_gpus_by_model, r.n_gpu_models);
+      },
+      /*rank_part=*/false, rc);
+}
+int cook_batch_stats(const cook_engine* lead, uint32_t out[5]) {
+  if (!lead || !out) return COOK_E_INVALID;
+  for (unsigned k = 0; k < 5u; ++k) out[k] = lead->any_batch_stats[k];
+  return COOK_OK;
 }
 
 int cook_offers_stage(cook_engine* e, const cook_nodes* nodes, const cook_pods* pods, const cook_offer_params* params) {

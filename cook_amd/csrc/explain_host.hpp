@@ -4,12 +4,14 @@
 #pragma once
 
 struct ExplainBufs {
-  DArr<uint64_t> key, kc, km;
+  DArr<uint64_t> key, kc, km, okc, okm;  // kc / km: the jobs' sort keys, okc / okm: the offers'
   DArr<uint32_t> permA, permB, ostart, oend, pos, counts, user_cons, user_match;
   DArr<double> jc, jm, out;  // out: 16 doubles of ResourceStats x 2
   DArr<uint32_t> largest;
   DArr<SumU4> scan;
   DArr<unsigned long long> jgpus, ogpus;
+  DArr<MatchIn> in_dev;  // the last match's inputs, uploaded by cook_match_metrics when the engine holds no copy of them on the device
+  MatchIn in_host{};     // ... and what that copy reads (it stays as it is until the call's next synchronisation)
 };
 
 MatchState explain_state(cook_engine* e, unsigned K) {
@@ -67,33 +69,35 @@ void match_explain(cook_engine* e, ExplainBufs& x, const uint32_t* job_pos, unsi
   sync(e);
 }
 
-// resource-maps->stats of two columns (cpus, mem) of n rows resident on the device -> 8 doubles + 2 indices at out / largest
-void resource_stats(cook_engine* e, ExplainBufs& x, const double* a, const double* b, const uint64_t* ka, const uint64_t* kb, unsigned n,
-                    double* out /* device: total a, total b, p50 a, p95 a, p100 a, p50 b, p95 b, p100 b */, uint32_t* largest) {
-  x.scan.ensure(n);
+// resource-maps->stats of two columns (cpus, mem) of n rows resident on the device, in the two halves that stand on either side of the
+// read-back of the varying-bits masks.  First half: the totals -> out[0..1], and the masks of both key columns -> dmask[0..1].
+void resource_stats_totals(cook_engine* e, ExplainBufs& x, const double* a, const double* b, const uint64_t* ka, const uint64_t* kb, unsigned n,
+                           double* out, unsigned long long* dmask) {
   seg_scan<SumU4>(e, "metrics_total_scan", LoadPair{a, b}, (const uint8_t*)nullptr, n, x.scan.ptr(), e->tmpU4);
-  KL("metrics_totals", metrics_totals, 1, 1024, (const SumU4*)x.scan.ptr(), a, b, n, out + 0, out + 1);
-  x.permA.ensure(n);
-  x.permB.ensure(n);
+  KM<metrics_totals, 1024>(e, "metrics_totals", 1, (const SumU4*)x.scan.ptr(), a, b, n, out + 0, out + 1);
+  const unsigned g = std::min(div_up(n, 256), 64u);
+  KM<radix_varying_bits, 256>(e, "radix_varying_bits", g, ka, n, dmask + 0, g);
+  KM<radix_varying_bits, 256>(e, "radix_varying_bits", g, kb, n, dmask + 1, g);
+}
+// second half: the stable sort of either column by its key under the mask read back -> p50, p95, p100 at out[2..7], the largest-by indices
+void resource_stats_sorted(cook_engine* e, ExplainBufs& x, const double* a, const double* b, const uint64_t* ka, const uint64_t* kb, unsigned n,
+                           const unsigned long long* mask, double* out, uint32_t* largest) {
   const unsigned g = div_up(n, 256);
   for (int col = 0; col < 2; ++col) {
-    const uint64_t* key = col ? kb : ka;
-    unsigned long long* dmask = e->d_scratch64.ensure(8);
-    memset_async(e, dmask, 0, 8);
-    KM<radix_varying_bits, 256>(e, "radix_varying_bits", std::min(g, 64u), key, n, dmask, std::min(g, 64u));
-    readback64(e, 1);
-    const unsigned long long mask = e->h_scratch[0];
     KM<iota_u32, 256>(e, "iota", g, x.permA.ptr(), n);
-    const uint32_t* perm = radix_sort_masked(e, key, mask, x.permA.ptr(), x.permA.ptr(), x.permB.ptr(), n);
-    KL("metrics_pick", metrics_pick, 1, 64, perm, col ? b : a, n, out + 2 + 3 * col, out + 3 + 3 * col, out + 4 + 3 * col, largest + col);
+    const uint32_t* perm = radix_sort_masked(e, col ? kb : ka, mask[col], x.permA.ptr(), x.permA.ptr(), x.permB.ptr(), n);
+    KM<metrics_pick, 64>(e, "metrics_pick", 1, perm, col ? b : a, n, out + 2 + 3 * col, out + 3 + 3 * col, out + 4 + 3 * col, largest + col);
   }
 }
 
+// Two stream synchronisations however many columns are sorted: everything up to the four varying-bits masks (job cpus, job mem, offer cpus,
+// offer mem), ONE read-back of the masks, the four sorts and the picks, ONE read-back of the results.  Every kernel goes through KM, so the
+// flows of several pools (cook_match_metrics_multi) share both synchronisations and launch the same kernel once.
 void match_metrics(cook_engine* e, ExplainBufs& x, cook_cycle_metrics* out, uint32_t* user_considerable, uint32_t* user_matched,
                    unsigned n_users, int64_t* job_gpus_by_model, int64_t* offer_gpus_by_model, unsigned n_models) {
   if (!e->match_ran() || !e->last_in_valid) e->fail(COOK_E_STATE, "cook_match_metrics before a match ran");
   if (!out) e->fail(COOK_E_INVALID, "cook_match_metrics: null output");
-  const MatchIn in = e->last_in;
+  const MatchIn& in = e->last_in;
   const unsigned K = in.K, M = in.M;
   const bool want_users = user_considerable || user_matched;
   if (want_users && !e->has_j_user) e->fail(COOK_E_INVALID, "cook_match_metrics: per-user counts need the jobs' user column staged");
@@ -102,36 +106,49 @@ void match_metrics(cook_engine* e, ExplainBufs& x, cook_cycle_metrics* out, uint
   const double nan = std::numeric_limits<double>::quiet_NaN();
   cook_resource_stats empty{0.0, 0.0, nan, nan, nan, nan, nan, nan, COOK_NONE_U32, COOK_NONE_U32};
   out->jobs = out->offer_stats = empty;
+  // every buffer before the first launch (inside a pool batch a buffer that grows waits for what its flow has recorded)
   x.out.ensure(16);
   x.largest.ensure(4);
   x.user_cons.ensure(std::max(1u, n_users));
   x.user_match.ensure(std::max(1u, n_users));
   x.jgpus.ensure(n_models + 1u);
   x.ogpus.ensure(n_models + 1u);
+  x.jc.ensure(K), x.jm.ensure(K), x.kc.ensure(K), x.km.ensure(K);  // the job side's and the offer side's own key columns:
+  x.okc.ensure(M), x.okm.ensure(M);                                // all four masks are formed before the first sort
+  x.scan.ensure(std::max(K, M)), x.permA.ensure(std::max(K, M)), x.permB.ensure(std::max(K, M));
+  unsigned long long* dmask = e->d_scratch64.ensure(8);
+  // the last match's inputs on the device: the copy the window rounds' set-up left there, or one uploaded now
+  const MatchIn* din = e->v_in.ptr();
+  if ((K || M) && !e->v_in_is_last) {
+    x.in_host = in;
+    h2d(e, x.in_dev, &x.in_host, 1);
+    din = x.in_dev.ptr();
+  }
   memset_async(e, x.user_cons.ptr(), 0, (size_t)std::max(1u, n_users) * 4);
   memset_async(e, x.user_match.ptr(), 0, (size_t)std::max(1u, n_users) * 4);
   memset_async(e, x.jgpus.ptr(), 0, (size_t)(n_models + 1u) * 8);
   memset_async(e, x.ogpus.ptr(), 0, (size_t)(n_models + 1u) * 8);
   unsigned* d_sched = e->d_counters.ptr() + 14;
   memset_async(e, d_sched, 0, 4);
+  memset_async(e, dmask, 0, 4 * 8);
   if (K) {
-    x.jc.ensure(K);
-    x.jm.ensure(K);
-    x.kc.ensure(std::max(K, M));
-    x.km.ensure(std::max(K, M));
-    KL("metrics_gather_jobs", metrics_gather_jobs, div_up(K, 256), 256, in, x.jc.ptr(), x.jm.ptr(), x.kc.ptr(), x.km.ptr());
-    resource_stats(e, x, x.jc.ptr(), x.jm.ptr(), x.kc.ptr(), x.km.ptr(), K, x.out.ptr(), x.largest.ptr());
-    KL("metrics_job_counts", metrics_job_counts, div_up(K, 256), 256, in, (const int32_t*)st.job_to_offer,
-       want_users ? (const uint32_t*)e->j_user.ptr() : (const uint32_t*)nullptr, n_users, x.user_cons.ptr(), x.user_match.ptr(), n_models,
-       job_gpus_by_model ? x.jgpus.ptr() : (unsigned long long*)nullptr);
+    KM<metrics_gather_jobs, 256>(e, "metrics_gather_jobs", div_up(K, 256), din, x.jc.ptr(), x.jm.ptr(), x.kc.ptr(), x.km.ptr());
+    resource_stats_totals(e, x, x.jc.ptr(), x.jm.ptr(), x.kc.ptr(), x.km.ptr(), K, x.out.ptr(), dmask);
+    KM<metrics_job_counts, 256>(e, "metrics_job_counts", div_up(K, 256), din, (const int32_t*)st.job_to_offer,
+        want_users ? (const uint32_t*)e->j_user.ptr() : (const uint32_t*)nullptr, n_users, x.user_cons.ptr(), x.user_match.ptr(), n_models,
+        job_gpus_by_model ? x.jgpus.ptr() : (unsigned long long*)nullptr);
   }
   if (M) {
-    x.kc.ensure(std::max(K, M));
-    x.km.ensure(std::max(K, M));
-    KL("metrics_keys", metrics_keys, div_up(M, 256), 256, in.o_cpus, in.o_mem, M, x.kc.ptr(), x.km.ptr());
-    resource_stats(e, x, in.o_cpus, in.o_mem, x.kc.ptr(), x.km.ptr(), M, x.out.ptr() + 8, x.largest.ptr() + 2);
-    KL("metrics_offer_counts", metrics_offer_counts, div_up(M, 256), 256, (const int32_t*)st.acount, M, d_sched, in.o_gpu_model,
-       in.o_gpu_count, in.gpu_slots ? in.gpu_slots : 1u, n_models, offer_gpus_by_model ? x.ogpus.ptr() : (unsigned long long*)nullptr);
+    KM<metrics_keys, 256>(e, "metrics_keys", div_up(M, 256), in.o_cpus, in.o_mem, M, x.okc.ptr(), x.okm.ptr());
+    resource_stats_totals(e, x, in.o_cpus, in.o_mem, x.okc.ptr(), x.okm.ptr(), M, x.out.ptr() + 8, dmask + 2);
+    KM<metrics_offer_counts, 256>(e, "metrics_offer_counts", div_up(M, 256), (const int32_t*)st.acount, M, d_sched, in.o_gpu_model,
+        in.o_gpu_count, in.gpu_slots ? in.gpu_slots : 1u, n_models, offer_gpus_by_model ? x.ogpus.ptr() : (unsigned long long*)nullptr);
+  }
+  if (K || M) {
+    readback64(e, 4);
+    const unsigned long long mask[4] = {e->h_scratch[0], e->h_scratch[1], e->h_scratch[2], e->h_scratch[3]};
+    if (K) resource_stats_sorted(e, x, x.jc.ptr(), x.jm.ptr(), x.kc.ptr(), x.km.ptr(), K, mask, x.out.ptr(), x.largest.ptr());
+    if (M) resource_stats_sorted(e, x, in.o_cpus, in.o_mem, x.okc.ptr(), x.okm.ptr(), M, mask + 2, x.out.ptr() + 8, x.largest.ptr() + 2);
   }
   double h[16];
   uint32_t hl[4];

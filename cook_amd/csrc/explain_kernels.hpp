@@ -6,6 +6,7 @@
 //  * the match-cycle metrics (scheduler.clj:1210-1280 handle-match-cycle-metrics, :547-600 jobs->stats / offers->stats).
 #pragma once
 #include "common.hpp"
+#include "multi.hpp"  // COOK_KERNEL: the metrics kernels are launched through KM
 #include "match_kernels.hpp"
 
 // slots of a summary row (cookmatch.h COOK_WHY_*)
@@ -211,8 +212,11 @@ struct ResourceStatsDev {  // cook_resource_stats
 };
 
 // the considerable jobs' resource columns in match order (jobs->resource-maps, scheduler.clj:511-545) + their sort keys
-__global__ void __launch_bounds__(256) metrics_gather_jobs(MatchIn in, double* __restrict__ cpus, double* __restrict__ mem,
-                                                           uint64_t* __restrict__ kc, uint64_t* __restrict__ km) {
+// (COOK_KERNELs, launched through KM: the same kernel of several pools is one cook_multi launch.  The call's MatchIn is too large for a batched
+// argument pack and is read through a pointer to its copy on the device.)
+COOK_KERNEL void metrics_gather_jobs(const MatchIn* __restrict__ inp, double* __restrict__ cpus, double* __restrict__ mem,
+                                     uint64_t* __restrict__ kc, uint64_t* __restrict__ km) {
+  const MatchIn& in = *inp;
   const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= in.K) return;
   const unsigned jj = in.j_index ? in.j_index[k] : k;
@@ -222,8 +226,8 @@ __global__ void __launch_bounds__(256) metrics_gather_jobs(MatchIn in, double* _
   kc[k] = f64_key(c);
   km[k] = f64_key(m);
 }
-__global__ void __launch_bounds__(256) metrics_keys(const double* __restrict__ a, const double* __restrict__ b, unsigned n,
-                                                    uint64_t* __restrict__ ka, uint64_t* __restrict__ kb) {
+COOK_KERNEL void metrics_keys(const double* __restrict__ a, const double* __restrict__ b, unsigned n, uint64_t* __restrict__ ka,
+                              uint64_t* __restrict__ kb) {
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) {
     ka[i] = f64_key(a[i]);
@@ -236,8 +240,8 @@ struct LoadPair {  // (cpus, mem) as a tracked SumU4 element
 };
 // nearest-rank percentiles of a stably sorted permutation (task_stats.clj:59-80): index ceil(p n / 100) - 1 in exact
 // arithmetic, as the reference's ratio arithmetic gives; :largest-by = the LAST of the stable sort (scheduler.clj:563-568)
-__global__ void metrics_pick(const uint32_t* __restrict__ perm, const double* __restrict__ val, unsigned n, double* __restrict__ p50,
-                             double* __restrict__ p95, double* __restrict__ p100, uint32_t* __restrict__ largest) {
+COOK_KERNEL void metrics_pick(const uint32_t* __restrict__ perm, const double* __restrict__ val, unsigned n, double* __restrict__ p50,
+                              double* __restrict__ p95, double* __restrict__ p100, uint32_t* __restrict__ largest) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const unsigned long long nn = n;
   *p50 = val[perm[(unsigned)((50ull * nn + 99ull) / 100ull) - 1u]];
@@ -249,9 +253,8 @@ __global__ void metrics_pick(const uint32_t* __restrict__ perm, const double* __
 // rounded, every prefix is exact, hence equal to the left-to-right sum, and the last element is the answer.  Otherwise the
 // in-order fold below.
 constexpr int MT_TILE = 2048;
-__global__ void __launch_bounds__(1024) metrics_totals(const SumU4* __restrict__ scan, const double* __restrict__ a,
-                                                       const double* __restrict__ b, unsigned n, double* __restrict__ ta,
-                                                       double* __restrict__ tb) {
+COOK_KERNEL void metrics_totals(const SumU4* __restrict__ scan, const double* __restrict__ a, const double* __restrict__ b, unsigned n,
+                                double* __restrict__ ta, double* __restrict__ tb) {  // one block of 1024
   __shared__ unsigned s_bad;
   if (threadIdx.x == 0) s_bad = 0;
   __syncthreads();
@@ -286,10 +289,10 @@ __global__ void __launch_bounds__(1024) metrics_totals(const SumU4* __restrict__
   if (w < 2 && lane_id() == 0) *(w ? tb : ta) = acc;
 }
 // frequencies of users over the considerable / matched jobs (scheduler.clj:1216-1227), gpus per model over the jobs
-__global__ void __launch_bounds__(256) metrics_job_counts(MatchIn in, const int32_t* __restrict__ j2o, const uint32_t* __restrict__ j_user,
-                                                          unsigned n_users, uint32_t* __restrict__ user_considerable,
-                                                          uint32_t* __restrict__ user_matched, unsigned n_models,
-                                                          unsigned long long* __restrict__ job_gpus_by_model) {
+COOK_KERNEL void metrics_job_counts(const MatchIn* __restrict__ inp, const int32_t* __restrict__ j2o, const uint32_t* __restrict__ j_user,
+                                    unsigned n_users, uint32_t* __restrict__ user_considerable, uint32_t* __restrict__ user_matched,
+                                    unsigned n_models, unsigned long long* __restrict__ job_gpus_by_model) {
+  const MatchIn& in = *inp;
   const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= in.K) return;
   const unsigned jj = in.j_index ? in.j_index[k] : k;
@@ -308,10 +311,9 @@ __global__ void __launch_bounds__(256) metrics_job_counts(MatchIn in, const int3
   }
 }
 // offers-scheduled = leases Fenzo used (scheduler.clj:1372-1374); "gpus/<model>" totals of offers->resource-maps (tools.clj:1032-1058)
-__global__ void __launch_bounds__(256) metrics_offer_counts(const int32_t* __restrict__ acount, unsigned M, unsigned* __restrict__ scheduled,
-                                                            const uint32_t* __restrict__ o_gpu_model, const double* __restrict__ o_gpu_count,
-                                                            unsigned gpu_slots, unsigned n_models,
-                                                            unsigned long long* __restrict__ offer_gpus_by_model) {
+COOK_KERNEL void metrics_offer_counts(const int32_t* __restrict__ acount, unsigned M, unsigned* __restrict__ scheduled,
+                                      const uint32_t* __restrict__ o_gpu_model, const double* __restrict__ o_gpu_count, unsigned gpu_slots,
+                                      unsigned n_models, unsigned long long* __restrict__ offer_gpus_by_model) {
   const unsigned v = blockIdx.x * blockDim.x + threadIdx.x;
   const bool used = v < M && acount[v] > 0;
   const unsigned long long b = __ballot(used);

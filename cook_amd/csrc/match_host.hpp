@@ -333,6 +333,7 @@ static V2Buf match_v2_setup(cook_engine* e, const MatchIn& in, const MatchState&
     *hin = in;
     pinned_copy(e, din, hin, sizeof(MatchIn), hipMemcpyHostToDevice);
     vb.in_dev = din;
+    e->v_in_is_last = std::memcmp(&in, &e->last_in, sizeof(MatchIn)) == 0;  // (cook_match_metrics reads it in place)
   }
   if (M) KM<match_pack_offers, 256>(e, "match_pack_offers", div_up(M, 256), (const MatchIn*)vb.in_dev, oa, ob, vb.ow);
   KM<match_pack_jobs, 256>(e, "match_pack_jobs", div_up(K, 256), (const MatchIn*)vb.in_dev, jr, jcons);
@@ -473,6 +474,7 @@ void match_run_device(cook_engine* e, unsigned K, const uint32_t* j_index, bool 
   in.fitness = (unsigned)e->params.fitness;
   e->last_in = in;
   e->last_in_valid = true;
+  e->v_in_is_last = false;
   const MatchState st = match_state_setup(e, in);
   e->cf_inelig = 0;  // (stats word 38 speaks of THIS match: set below or by match_try_classfit where the class-ordered form was asked for and refused)
   const int algo = e->params.match_algo;

@@ -25,6 +25,7 @@ struct PoolBatch {
   std::vector<PoolFlow> flows;
   ucontext_t main_ctx;
   unsigned launches = 0, grouped = 0, singles = 0, syncs = 0;  // launches made, of them for more than one pool; operations issued alone
+  bool closing_sync = true;  // synchronise once more when every flow has finished, even if nothing was issued since the last synchronisation
 };
 static thread_local PoolBatch* tl_batch = nullptr;
 static thread_local PoolFlow* tl_flow = nullptr;  // the flow running on this thread (null: none, or the scheduler itself)
@@ -46,8 +47,9 @@ static void batch_drain_before_free() {
 // issues what the flows have recorded: operations without a key as they stand, the same kernel at the front of several flows as one launch
 // COOK_BATCH_TRACE=1: every operation a pool batch issues, to stderr (name x pools; "alone" = issued on its own)
 static const bool g_batch_trace = std::getenv("COOK_BATCH_TRACE") != nullptr;
-static void batch_flush(PoolBatch& b) {
+static unsigned batch_flush(PoolBatch& b) {  // -> operations issued
   const unsigned P = (unsigned)b.flows.size();
+  const unsigned before = b.launches + b.singles;
   const BatchOp* group[COOK_MULTI_MAX * 8];
   for (;;) {
     for (auto& f : b.flows)
@@ -82,6 +84,7 @@ static void batch_flush(PoolBatch& b) {
     if (n > 1) ++b.grouped;
   }
   for (auto& f : b.flows) f.ops.clear(), f.cur = 0;
+  return b.launches + b.singles - before;
 }
 
 static void flow_entry() {
@@ -158,9 +161,10 @@ static int batch_run(PoolBatch& b) {
         swapcontext(&b.main_ctx, &f.ctx);
         tl_flow = nullptr;
       }
-    batch_flush(b);
+    const unsigned issued = batch_flush(b);
     bool parked = false;
     for (auto& f : b.flows) parked = parked || f.state == 1;
+    if (!parked && !issued && !b.closing_sync) break;  // every flow ended at its last synchronisation: the stream is idle
     const auto t0 = std::chrono::steady_clock::now();
     if (g_batch_trace) std::fprintf(stderr, "batch: synchronise\n");
     COOK_HIP(hipStreamSynchronize(b.stream));
@@ -189,8 +193,9 @@ static const bool g_rank_batch = env_switch_on_unless_zero("COOK_RANK_BATCH");
 // several devices, COOK_SYNC_TRACE, a call from inside a flow), `body(i)` what engine i's flow does inside the pool batch.  Returns the
 // first engine's error that is not COOK_OK; every engine whose flow failed keeps its own message.  rank_part: the batch is the rank part of a
 // cycle — timed as the rank stage of every engine, counted in the lead's batch statistics, its kernel timings collected.
+// rc_out (optional, [n]): every engine's own code.
 template <class One, class Body>
-int run_pools_batched(cook_engine** engines, uint32_t n, One&& one, Body&& body, bool rank_part) {
+int run_pools_batched(cook_engine** engines, uint32_t n, One&& one, Body&& body, bool rank_part, int* rc_out = nullptr) {
   if (!engines_valid(engines, n, false)) return COOK_E_INVALID;
   cook_engine* lead = engines[0];
   bool same_device = true;
@@ -199,6 +204,7 @@ int run_pools_batched(cook_engine** engines, uint32_t n, One&& one, Body&& body,
     int first = COOK_OK;
     for (uint32_t i = 0; i < n; ++i) {
       const int rc = one(i);
+      if (rc_out) rc_out[i] = rc;
       if (rc != COOK_OK && first == COOK_OK) first = rc;
     }
     return first;
@@ -210,6 +216,7 @@ int run_pools_batched(cook_engine** engines, uint32_t n, One&& one, Body&& body,
     PoolBatch b;
     b.lead = lead;
     b.stream = lead->stream;
+    b.closing_sync = rank_part;
     b.flows.resize(n);
     for (uint32_t i = 0; i < n; ++i) {
       b.flows[i].e = engines[i];
@@ -220,7 +227,12 @@ int run_pools_batched(cook_engine** engines, uint32_t n, One&& one, Body&& body,
     flows_rc = batch_run(b);
     for (uint32_t i = 0; i < n; ++i)
       if (b.flows[i].rc != COOK_OK) flow_err[i] = {b.flows[i].rc, engines[i]->err};
-    if (!rank_part) return;
+    lead->any_batch_stats[0] = n, lead->any_batch_stats[1] = b.launches, lead->any_batch_stats[2] = b.grouped,
+    lead->any_batch_stats[3] = b.singles, lead->any_batch_stats[4] = b.syncs;
+    if (!rank_part) {
+      prof_collect(lead);
+      return;
+    }
     tr->stop();
     for (uint32_t i = 1; i < n; ++i) engines[i]->rank_ms = lead->rank_ms;  // one joint sequence of launches
     lead->batch_stats[0] = n, lead->batch_stats[1] = b.launches, lead->batch_stats[2] = b.grouped, lead->batch_stats[3] = b.singles,
@@ -229,5 +241,7 @@ int run_pools_batched(cook_engine** engines, uint32_t n, One&& one, Body&& body,
   });
   for (uint32_t i = 0; i < n; ++i)
     if (flow_err[i].first != COOK_OK) engines[i]->err = flow_err[i].second;  // every engine whose flow failed keeps its own message
+  if (rc_out)
+    for (uint32_t i = 0; i < n; ++i) rc_out[i] = rc != COOK_OK ? rc : flow_err[i].first;  // (the scheduler's own error: every engine of the batch failed)
   return rc != COOK_OK ? rc : flows_rc;
 }

@@ -477,18 +477,11 @@ class Engine:
 
     def match_metrics(self, n_users: int = 0, n_gpu_models: int = 0) -> dict:
         """handle-match-cycle-metrics' numbers (scheduler.clj:1210-1280) for the LAST match."""
-        m = A.CookCycleMetrics()
-        uc = np.zeros(max(1, n_users), np.uint32)
-        um = np.zeros(max(1, n_users), np.uint32)
-        jg = np.zeros(n_gpu_models + 1, np.int64)
-        og = np.zeros(n_gpu_models + 1, np.int64)
-        self._chk(self._lib.cook_match_metrics(self._h, C.byref(m), _p(uc, C.c_uint32) if n_users else None,
-                                               _p(um, C.c_uint32) if n_users else None, n_users, _p(jg, C.c_int64), _p(og, C.c_int64),
+        o = _MetricsOut(n_users, n_gpu_models)
+        self._chk(self._lib.cook_match_metrics(self._h, C.byref(o.m), _p(o.uc, C.c_uint32) if n_users else None,
+                                               _p(o.um, C.c_uint32) if n_users else None, n_users, _p(o.jg, C.c_int64), _p(o.og, C.c_int64),
                                                n_gpu_models))
-        return dict(considerable=m.considerable, matched=m.matched, unmatched=m.unmatched, offers=m.offers,
-                    offers_scheduled=m.offers_scheduled, head_matched=bool(m.head_matched), jobs=m.jobs.as_dict(),
-                    offers_stats=m.offer_stats.as_dict(), user_considerable=uc[:n_users].copy(), user_matched=um[:n_users].copy(),
-                    job_gpus_by_model=jg, offer_gpus_by_model=og)
+        return o.result()
 
     # ---- offer construction from node state --------------------------------------------------------------------
     def offers_stage(self, nodes: A.Nodes, pods: A.Pods, oparams: A.CookOfferParams):
@@ -579,6 +572,12 @@ class Engine:
                 "cf_spins", "cf_ticks_walk", "cf_ticks_phase1", "cf_rewinds", "cf_flips", "cf_hwid_decider", "cf_hwid_books")
         return {k: int(x) for k, x in zip(keys, out[:max(0, n)]) if not k.startswith("_")}
 
+    def batch_stats(self) -> dict:
+        """the last pool batch this engine led, whatever call made it (cook_batch_stats); all zeros before any"""
+        out = (C.c_uint32 * 5)()
+        self._chk(self._lib.cook_batch_stats(self._h, out))
+        return dict(zip(("pools", "launches", "grouped_launches", "singles", "syncs"), (int(x) for x in out)))
+
     def set_profiling(self, on: bool):
         self._lib.cook_set_profiling(self._h, int(bool(on)))
 
@@ -589,6 +588,30 @@ class Engine:
         launches = (C.c_uint32 * cap)()
         n = self._lib.cook_kernel_timings(self._h, names, ms, launches, cap)
         return {names[i].decode(): (ms[i], launches[i]) for i in range(max(0, n))}
+
+
+class _MetricsOut:
+    """the output buffers of one engine's cook_match_metrics"""
+
+    def __init__(self, n_users: int, n_gpu_models: int):
+        self.n_users, self.n_gpu_models = int(n_users), int(n_gpu_models)
+        self.m = A.CookCycleMetrics()
+        self.uc = np.zeros(max(1, self.n_users), np.uint32)
+        self.um = np.zeros(max(1, self.n_users), np.uint32)
+        self.jg = np.zeros(self.n_gpu_models + 1, np.int64)
+        self.og = np.zeros(self.n_gpu_models + 1, np.int64)
+
+    def req(self) -> A.CookMetricsReq:
+        return A.CookMetricsReq(C.pointer(self.m), _p(self.uc, C.c_uint32) if self.n_users else None,
+                                _p(self.um, C.c_uint32) if self.n_users else None, self.n_users, self.n_gpu_models, _p(self.jg, C.c_int64),
+                                _p(self.og, C.c_int64))
+
+    def result(self) -> dict:
+        m, n = self.m, self.n_users
+        return dict(considerable=m.considerable, matched=m.matched, unmatched=m.unmatched, offers=m.offers,
+                    offers_scheduled=m.offers_scheduled, head_matched=bool(m.head_matched), jobs=m.jobs.as_dict(),
+                    offers_stats=m.offer_stats.as_dict(), user_considerable=self.uc[:n].copy(), user_matched=self.um[:n].copy(),
+                    job_gpus_by_model=self.jg, offer_gpus_by_model=self.og)
 
 
 class PinnedArena:
@@ -834,3 +857,74 @@ def cycle_match_multi(engines: Sequence[Engine]):
     arr = (C.c_void_p * len(engines))(*[e._h for e in engines])
     lead = engines[0]
     lead._chk(lead._lib.cook_cycle_match_multi(arr, len(engines)))
+
+
+def _multi_results(engines, rc, codes, results, raise_errors):
+    """what the per-pool multi calls return: the engines' results, a CookError (the engine's own code and message) in the place of an engine
+    that failed; raise_errors: the first of them is raised instead"""
+    out = []
+    for e, c, r in zip(engines, codes, results):
+        out.append(r() if c == 0 else CookError(c, e._lib.cook_last_error(e._h).decode()))
+    if rc != 0 and all(c == 0 for c in codes):  # the whole call was refused: nothing ran
+        err = CookError(rc, "the call was refused: a NULL argument or entry, no engine, or an engine named twice")
+        if raise_errors:
+            raise err
+        return [err for _ in engines]
+    if raise_errors:
+        for r in out:
+            if isinstance(r, CookError):
+                raise r
+    return out
+
+
+def cycle_autoscale_multi(engines: Sequence[Engine], calls: Sequence[Optional[dict]], raise_errors: bool = True) -> list:
+    """cycle_autoscale of several engines (pools of one device) in ONE call (cook_cycle_autoscale_multi: the pools' flows in one pool batch,
+    every stream synchronisation shared).  calls: per engine the keywords of Engine.cycle_autoscale (None: the defaults).  -> per engine
+    (task indices, info dict), as Engine.cycle_autoscale.  An engine that fails does not spoil the others: raise_errors=False puts its
+    CookError in its place instead of raising it."""
+    n = len(engines)
+    if not n:
+        return []
+    calls = [dict(c or {}) for c in calls]
+    assert len(calls) == n
+    keep, ps, outs, caps = [], [], [], []
+    for e, kw in zip(engines, calls):
+        sk = np.ascontiguousarray(kw["offer_skipped"], dtype=np.uint8) if kw.get("offer_skipped") is not None else None
+        ex = np.ascontiguousarray(kw["exclude_tasks"] if kw.get("exclude_tasks") is not None else [], dtype=np.uint32)
+        max_jobs = int(kw.get("max_jobs", 1000))
+        ps.append(A.CookAutoscaleParams(max_jobs, len(ex), float(kw.get("scale_factor", 1.0)), _p(sk, C.c_uint8) if sk is not None else None,
+                                        _p(ex, C.c_uint32) if len(ex) else None))
+        cap = int(kw["cap"]) if kw.get("cap") is not None else max(max_jobs, getattr(e, "_rank_np", 0))  # >= max(max_jobs, K)
+        caps.append(cap)
+        outs.append(np.zeros(max(1, cap), dtype=np.uint32))
+        keep.append((sk, ex))
+    arr = (C.c_void_p * n)(*[e._h for e in engines])
+    pp = (C.c_void_p * n)(*[C.addressof(p) for p in ps])
+    tp = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    cp = (C.c_uint32 * n)(*caps)
+    info = (A.CookAutoscaleInfo * n)()
+    codes = (C.c_int * n)()
+    rc = engines[0]._lib.cook_cycle_autoscale_multi(arr, n, pp, tp, cp, info, codes)
+    res = _multi_results(engines, rc, list(codes), [lambda i=i: (outs[i][: info[i].n_out].copy(), info[i].as_dict()) for i in range(n)], raise_errors)
+    for i, r in enumerate(res):
+        if isinstance(r, CookError):
+            r.info = info[i].as_dict()  # (|Out| > cap: the info says how many)
+    return res
+
+
+def match_metrics_multi(engines: Sequence[Engine], n_users=0, n_gpu_models=0, raise_errors: bool = True) -> list:
+    """match_metrics of several engines (pools of one device) in ONE call (cook_match_metrics_multi: two stream synchronisations for all of
+    them, the same kernel of several pools in one launch).  n_users / n_gpu_models: one value for all, or one per engine (n_users 0: that
+    engine's per-user arrays are left out).  -> per engine the dict of Engine.match_metrics; raise_errors as in cycle_autoscale_multi."""
+    n = len(engines)
+    if not n:
+        return []
+    nus = [int(n_users)] * n if np.isscalar(n_users) else [int(x) for x in n_users]
+    nms = [int(n_gpu_models)] * n if np.isscalar(n_gpu_models) else [int(x) for x in n_gpu_models]
+    assert len(nus) == n and len(nms) == n
+    outs = [_MetricsOut(u, g) for u, g in zip(nus, nms)]
+    reqs = (A.CookMetricsReq * n)(*[o.req() for o in outs])
+    arr = (C.c_void_p * n)(*[e._h for e in engines])
+    codes = (C.c_int * n)()
+    rc = engines[0]._lib.cook_match_metrics_multi(arr, n, reqs, codes)
+    return _multi_results(engines, rc, list(codes), [o.result for o in outs], raise_errors)

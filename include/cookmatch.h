@@ -356,6 +356,19 @@ typedef struct cook_autoscale_info {
   double fraction_unmatched;
 } cook_autoscale_info;
 int cook_cycle_autoscale(cook_engine* e, const cook_autoscale_params* p, uint32_t* task_idx, uint32_t cap, cook_autoscale_info* info);
+/* cook_cycle_autoscale for every pool of a GPU in ONE call from one thread: the pools' flows in one pool batch (the mechanism of
+ * cook_cycle_run_rank_multi), so the pools share every stream synchronisation and launch the same kernel once.  Engine i's result
+ * is exactly what cook_cycle_autoscale(engines[i], params[i], task_idx[i], cap[i], &info[i]) gives: outputs, info, error code and message,
+ * state rule.  Returns the first engine's code that is not COOK_OK; rc[i], when given, is engine i's code; every engine keeps its own
+ * cook_last_error; an engine that fails (COOK_E_STATE, a bad exclude index, |Out| > cap with info still filled ...) does not spoil the
+ * others.  COOK_E_INVALID with nothing run: engines, params or cap NULL, n == 0, a NULL entry of engines or params, an engine twice.
+ * One after another, with the same results: one engine, engines of several devices, COOK_RANK_BATCH=0, a call from inside a flow. */
+int cook_cycle_autoscale_multi(cook_engine** engines, uint32_t n,
+                               const cook_autoscale_params* const* params, /* [n], every entry required            */
+                               uint32_t* const* task_idx,                  /* [n]; entry i may be NULL iff cap[i]==0 */
+                               const uint32_t* cap,                        /* [n]                                    */
+                               cook_autoscale_info* info,                  /* [n] or NULL                            */
+                               int* rc);                                   /* [n] or NULL: every engine's own code   */
 
 /* ---- SWEEP: the three task killers over the cluster's running set (scheduler.clj:1888-2016, group.clj:17-44) --------------------
  * Stateless, like cook_offers_build: the engine handle only picks the device and stream; no rank, considerable, match, offers or
@@ -655,6 +668,16 @@ typedef struct cook_cycle_metrics {
  * (:1404-1486) are host arithmetic on these numbers. */
 int cook_match_metrics(cook_engine* e, cook_cycle_metrics* out, uint32_t* user_considerable, uint32_t* user_matched, uint32_t n_users,
                        int64_t* job_gpus_by_model, int64_t* offer_gpus_by_model, uint32_t n_gpu_models);
+/* cook_match_metrics for every pool of a GPU in ONE call from one thread (one pool batch, as cook_cycle_autoscale_multi): the call makes the
+ * two stream synchronisations of one pool's call, and the same kernel of several pools is one launch.  Engine i's result, code and message
+ * are exactly those of cook_match_metrics with req[i]'s arguments; errors, rc and the one-after-another cases as cook_cycle_autoscale_multi
+ * (COOK_E_INVALID with nothing run: engines or req NULL, n == 0, a NULL engine, an engine twice). */
+typedef struct cook_metrics_req {   /* the arguments of cook_match_metrics for one engine */
+  cook_cycle_metrics* out;          /* required */
+  uint32_t* user_considerable; uint32_t* user_matched; uint32_t n_users;
+  uint32_t n_gpu_models; int64_t* job_gpus_by_model; int64_t* offer_gpus_by_model;
+} cook_metrics_req;
+int cook_match_metrics_multi(cook_engine** engines, uint32_t n, const cook_metrics_req* req /* [n] */, int* rc /* [n] or NULL */);
 
 /* ---- USER STATISTICS: the arithmetic of set-stats-counters! (monitor.clj:40-116, 177-207) from the last rank, on the device --------
  * Per user u and state s (0 running, 1 waiting, 2 starved, 3 waiting-under-quota): per_user[(u*4 + s)*3 + {0,1,2}] = {jobs, cpus, mem};
@@ -971,6 +994,11 @@ int cook_match_stats(cook_engine* e, uint32_t out[16]);
    [53..56] 100 MHz ticks: the launch, its prologue, the epochs' merges, the bookkeeper's batch pre-checks; [57..63] reserved (0) */
 #define COOK_MATCH_STATS_EX_N 64
 int cook_match_stats_ex(cook_engine* e, uint32_t* out, uint32_t cap);
+/* the last pool batch this engine led, whatever call made it (the rank part, queue cycles, pool usage, cook_cycle_autoscale_multi,
+   cook_match_metrics_multi): pools, launches made, of them for more than one pool, operations issued alone (copies, fills, kernels outside
+   the batched path), stream synchronisations.  All zeros before any; a call that ran its engines one after another leaves them as they were.
+   (cook_match_stats_ex [32..36] stay the rank part's.) */
+int cook_batch_stats(const cook_engine* lead, uint32_t out[5]);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop
