@@ -431,6 +431,69 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueueCarry(JNIEnv* env, jcla
   }
   return cook_cycle_run_queue_carry(H(h), &s, &cy, (uint32_t)num_considerable);
 }
+/* cycleRunQueueCarry with the release (cook_cycle_run_queue_release; defer != 0: cook_cycle_run_queue_release_multi for this one pool, the
+ * placement then runs in cycleMatchMulti).  finished: the n_finished tasks that ended since the last cycle, in the host's order, as an
+ * array of direct buffers {host u32, user u32, cpus f64, mem f64, gpus f64, ports i32, scalars f64 (n_fin_scalars columns of n_finished),
+ * gpu_model u32, disk_request f64, disk_type u32, group u32} (null elements: the column is absent), or null: no release.
+ * release_offers / release_usage / release_groups = 1 give their resources back to the staged offers (then offers must be null), take
+ * them out of the staged user state, remove them from the groups' running cotasks (then groups must be null), on the device. */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueueRelease(JNIEnv* env, jclass c, jlong h, jint num_considerable, jint remove_mode,
+                                                                 jint n_last_offers, jobject offer_skipped, jint m, jobject offer_dims,
+                                                                 jobjectArray offers, jint n_groups, jobjectArray groups, jint carry_offers,
+                                                                 jint carry_usage, jint n_users, jobject tokens_left, jint n_finished,
+                                                                 jint n_fin_scalars, jobjectArray finished, jint release_offers,
+                                                                 jint release_usage, jint release_groups, jint defer) {
+  int bad = 0;
+  cook_offers o = offers_of(env, m, dims_of(env, offer_dims, &bad), offers, &bad);
+  cook_groups g = groups_of(env, n_groups, groups, &bad);
+  cook_queue_step s;
+  cook_queue_carry cy;
+  cook_finished f;
+  const jint nf = n_finished > 0 ? n_finished : 0, ns = n_fin_scalars > 0 ? n_fin_scalars : 0;
+  (void)c;
+  s.offer_skipped = BUFN(const uint8_t, offer_skipped, n_last_offers > 0 ? n_last_offers : 0);
+  s.remove_mode = (uint32_t)remove_mode;
+  s.n_offer_skipped = (uint32_t)(n_last_offers > 0 ? n_last_offers : 0);
+  s.offers = offers ? &o : 0;
+  s.groups = groups ? &g : 0;
+  cy.offers = (uint32_t)carry_offers;
+  cy.usage = (uint32_t)carry_usage;
+  cy.tokens_left = BUFN(const int64_t, tokens_left, n_users > 0 ? n_users : 0);
+  f.n = (uint32_t)nf;
+  f.host = EL(const uint32_t, finished, 0, nf);
+  f.user = EL(const uint32_t, finished, 1, nf);
+  f.cpus = EL(const double, finished, 2, nf);
+  f.mem = EL(const double, finished, 3, nf);
+  f.gpus = EL(const double, finished, 4, nf);
+  f.ports = EL(const int32_t, finished, 5, nf);
+  f.scalars = EL(const double, finished, 6, (uint64_t)nf * (uint64_t)ns);
+  f.n_scalars = (uint32_t)ns;
+  f.gpu_model = EL(const uint32_t, finished, 7, nf);
+  f.disk_request = EL(const double, finished, 8, nf);
+  f.disk_type = EL(const uint32_t, finished, 9, nf);
+  f.group = EL(const uint32_t, finished, 10, nf);
+  f.offers = (uint32_t)release_offers;
+  f.usage = (uint32_t)release_usage;
+  f.groups = (uint32_t)release_groups;
+  if (bad) return COOK_E_INVALID;
+  if (defer) {
+    cook_engine* e = H(h);
+    const cook_queue_step* sp = &s;
+    const cook_queue_carry* cp = &cy;
+    const cook_finished* fp = finished ? &f : 0;
+    const uint32_t k = (uint32_t)num_considerable;
+    return cook_cycle_run_queue_release_multi(&e, 1, &sp, &cp, &fp, &k);
+  }
+  return cook_cycle_run_queue_release(H(h), &s, &cy, finished ? &f : 0, (uint32_t)num_considerable);
+}
+/* the counts of the last queue cycle's release (cook_cycle_release_info): info_out = direct buffer of one cook_release_info */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleReleaseInfo(JNIEnv* env, jclass c, jlong h, jobject info_out) {
+  int bad = 0;
+  cook_release_info* out = BUF(cook_release_info, info_out);
+  (void)c;
+  if (bad || !out) return COOK_E_INVALID;
+  return cook_cycle_release_info(H(h), out);
+}
 /* the running usage of n staged engines of one device in ONE call (cook_rank_pool_usage_multi): usage_out = direct buffer of n cook_usage */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_rankPoolUsageMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n, jobject usage_out) {
   cook_engine* es[64];

@@ -146,6 +146,60 @@ class QueueCarry:
         return CookQueueCarry(self.offers, self.usage, _ptr(self.tokens_left, _i64p))
 
 
+class CookFinished(C.Structure):  # cook_cycle_run_queue_release*
+    _fields_ = [("n", C.c_uint32), ("host", _u32p), ("user", _u32p), ("cpus", _f64p), ("mem", _f64p), ("gpus", _f64p), ("ports", _i32p),
+                ("scalars", _f64p), ("n_scalars", C.c_uint32), ("gpu_model", _u32p), ("disk_request", _f64p), ("disk_type", _u32p),
+                ("group", _u32p), ("offers", C.c_uint32), ("usage", C.c_uint32), ("groups", C.c_uint32)]
+
+
+class CookReleaseInfo(C.Structure):  # cook_cycle_release_info
+    _fields_ = [("with_row", C.c_uint32), ("without_row", C.c_uint32), ("counts_clamped", C.c_uint32), ("cotasks_removed", C.c_uint32),
+                ("cotasks_missing", C.c_uint32)]
+
+
+@dataclass
+class Finished:
+    """The tasks that ended since the last cycle, in the host's order (cook_finished): a queue cycle gives their resources back to the
+    staged offers (offers), takes them out of the staged user state (usage) and out of the groups' running cotasks (groups), on the
+    device.  scalars: [n, n_scalars], NaN = no request under that name; group: NONE_U32 = no group."""
+    host: np.ndarray
+    cpus: np.ndarray
+    mem: np.ndarray
+    user: Optional[np.ndarray] = None
+    gpus: Optional[np.ndarray] = None
+    ports: Optional[np.ndarray] = None
+    scalars: Optional[np.ndarray] = None
+    gpu_model: Optional[np.ndarray] = None
+    disk_request: Optional[np.ndarray] = None
+    disk_type: Optional[np.ndarray] = None
+    group: Optional[np.ndarray] = None
+    offers: int = 0
+    usage: int = 0
+    groups: int = 0
+
+    @property
+    def n(self) -> int:
+        return len(self.host)
+
+    def as_struct(self):
+        """-> (CookFinished, the arrays its pointers refer to)"""
+        n = self.n
+        a = dict(host=_arr(self.host, np.uint32), user=_arr(self.user, np.uint32), cpus=_arr(self.cpus, np.float64), mem=_arr(self.mem, np.float64),
+                 gpus=_arr(self.gpus, np.float64), ports=_arr(self.ports, np.int32), gpu_model=_arr(self.gpu_model, np.uint32),
+                 disk_request=_arr(self.disk_request, np.float64), disk_type=_arr(self.disk_type, np.uint32), group=_arr(self.group, np.uint32))
+        for k, v in a.items():
+            assert v is None or v.shape == (n,), (k, v.shape, n)
+        cols, ns = None, 0
+        if self.scalars is not None:
+            sc = np.asarray(self.scalars, np.float64).reshape(n, -1)
+            ns = sc.shape[1]
+            cols = np.ascontiguousarray(sc.T).reshape(-1)  # the ABI takes one contiguous column per name, as cook_jobs.scalars
+        st = CookFinished(n, _ptr(a["host"], _u32p), _ptr(a["user"], _u32p), _ptr(a["cpus"], _f64p), _ptr(a["mem"], _f64p), _ptr(a["gpus"], _f64p),
+                          _ptr(a["ports"], _i32p), _ptr(cols, _f64p), ns, _ptr(a["gpu_model"], _u32p), _ptr(a["disk_request"], _f64p),
+                          _ptr(a["disk_type"], _u32p), _ptr(a["group"], _u32p), int(self.offers), int(self.usage), int(self.groups))
+        return st, (a, cols)
+
+
 class CookRebalanceParams(C.Structure):
     _fields_ = [("safe_dru_threshold", C.c_double), ("min_dru_diff", C.c_double),
                 ("max_preemption", C.c_int32), ("reserved", C.c_int32)]

@@ -53,11 +53,12 @@ static const uint32_t* carry_segments(cook_engine* e, const uint64_t* key, unsig
 }
 
 // Inside queue_advance, behind q_mark_removed: k > 0 considered jobs of the last cycle, their job_to_offer in e->m_j2o, their rows
-// through e->j_index, `skipped` the step's offer_skipped on the device (or null).
-void carry_enqueue(cook_engine* e, const cook_queue_carry* c, const uint8_t* skipped, unsigned k) {
+// through e->j_index, `skipped` the step's offer_skipped on the device (or null).  -> the staged offers are a fresh set of columns
+// written by this call (what a release behind it may update in place).
+bool carry_enqueue(cook_engine* e, const cook_queue_carry* c, const uint8_t* skipped, unsigned k) {
   CarryBufs& b = bufs(e->cyb);
   b.pool_pending = false;
-  if (!c || !(c->offers || c->usage) || !k) return;
+  if (!c || !(c->offers || c->usage) || !k) return false;
   MatchIn& in = e->min;
   const unsigned M = e->M;
   const int32_t* j2o = e->m_j2o.ptr();
@@ -70,7 +71,7 @@ void carry_enqueue(cook_engine* e, const cook_queue_carry* c, const uint8_t* ski
   const unsigned U = usage ? e->cb->U : 0u;
   uint64_t* okey = offers ? b.okey.ensure(k) : nullptr;
   uint64_t* ukey = usage ? b.ukey.ensure(k) : nullptr;
-  if (!okey && !ukey) return;
+  if (!okey && !ukey) return false;
   KM<carry_keys, 256>(e, "carry_keys", div_up(k, 256), j2o, k, skipped, (const uint32_t*)j.j_index, (const uint32_t*)e->j_user.ptr(), M, U, okey, ukey);
   if (offers) {
     const uint32_t* perm = carry_segments(e, okey, k, M, b.o_permA, b.o_permB, b.o_start, b.o_end);
@@ -112,6 +113,7 @@ void carry_enqueue(cook_engine* e, const cook_queue_carry* c, const uint8_t* ski
       b.pool_pending = true;
     }
   }
+  return offers;
 }
 // the host's refill of the tokens (behind the spend on the stream; read until the advance's synchronisation)
 void carry_tokens(cook_engine* e, const cook_queue_carry* c) {

@@ -61,6 +61,7 @@ struct UnschedBufs;    // unscheduled_host.hpp
 struct UsageBufs;      // usage_host.hpp
 struct QueueBufs;      // queue_host.hpp
 struct CarryBufs;      // carry_host.hpp
+struct ReleaseBufs;    // release_host.hpp
 
 }  // namespace
 
@@ -201,6 +202,7 @@ struct cook_engine {
   std::vector<int32_t> h_g_min;
   std::unique_ptr<QueueBufs> qb;               // (allocated on first use)
   std::unique_ptr<CarryBufs> cyb;              // the carry of a queue cycle (allocated on first use)
+  std::unique_ptr<ReleaseBufs> rlb;            // the release of a queue cycle (allocated on first use)
 
   // ---- rebalancer state (allocated on first use) ----
   std::unique_ptr<RebalBufs> rb;
@@ -227,7 +229,7 @@ struct cook_engine {
   DArr<uint64_t> cf_attr8;
   DArr<uint32_t> cf_h2o, cf_pos[3], cf_scr[3], cf_gcount, cf_gmem;
   DArr<CfJob> cf_jobs;
-  uint32_t cf_max_host = 0xFFFFFFFFu;   // greatest host id of the staged offers; 0xFFFFFFFF: not known (offers built on the device)
+  uint32_t cf_max_host = 0xFFFFFFFFu;   // greatest host id of the staged offers (match_stage_offers, cook_cycle_update's offers); 0xFFFFFFFF: not known (offers built on the device)
   uint32_t cf_group_run_total = 0;      // running cotasks over all staged groups
   unsigned last_form = 0;               // how the last match was placed: 0 window rounds, 1 serial sweep, 3 class-ordered best fit
   unsigned spread_serial_calls = 0;     // matches that match_algo 0 / 2 / 3 would have placed in window rounds and the sweep placed: a spreader (cook_match_stats_ex [39])
@@ -300,6 +302,7 @@ static std::atomic<int> g_engines_on_device[64];
 #include "user_stats_host.hpp"
 #include "autoscale_host.hpp"
 #include "carry_host.hpp"      // a queue cycle's carry: needs the staged user state (considerable_host.hpp)
+#include "release_host.hpp"    // a queue cycle's release: the carry's segments and column sets
 #include "queue_host.hpp"
 #include "sweep_host.hpp"
 #include "unscheduled_host.hpp"
@@ -603,6 +606,35 @@ int cook_cycle_run_queue_carry_multi(cook_engine** engines, uint32_t n, const co
         cycle_match(e, K, /*defer=*/true);
       },
       /*rank_part=*/true);
+}
+// ... and the release (release_host.hpp): finished tasks' resources back into the staged offers, user state and groups, behind the carry
+int cook_cycle_run_queue_release(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
+                                 uint32_t num_considerable) {
+  return cycle_run_one(e, [&] { return cycle_queue_part(e, step, num_considerable, carry, finished); }, /*defer=*/false);
+}
+int cook_cycle_run_queue_release_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
+                                       const cook_finished* const* finished, const uint32_t* num_considerable) {
+  if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
+  auto step = [&](uint32_t i) { return steps ? steps[i] : nullptr; };
+  auto carry = [&](uint32_t i) { return carries ? carries[i] : nullptr; };
+  auto fin = [&](uint32_t i) { return finished ? finished[i] : nullptr; };
+  return run_pools_batched(
+      engines, n,
+      [&](uint32_t i) {
+        return cycle_run_one(engines[i], [&] { return cycle_queue_part(engines[i], step(i), num_considerable[i], carry(i), fin(i)); }, /*defer=*/true);
+      },
+      [&](uint32_t i) {
+        cook_engine* e = engines[i];
+        const unsigned K = cycle_queue_part(e, step(i), num_considerable[i], carry(i), fin(i));
+        cycle_match(e, K, /*defer=*/true);
+      },
+      /*rank_part=*/true);
+}
+int cook_cycle_release_info(cook_engine* e, cook_release_info* out) {
+  return guarded(e, [&] {
+    if (!out) e->fail(COOK_E_INVALID, "cook_cycle_release_info: null out");
+    *out = e->rlb ? e->rlb->info : cook_release_info{};
+  });
 }
 int cook_rank_pool_usage_multi(cook_engine** engines, uint32_t n, cook_usage* out) {
   if (!engines || n == 0 || !out) return COOK_E_INVALID;

@@ -4,6 +4,8 @@
 // and groups, which the stream orders behind the kernels that still read the old offers) and reads two words back — the number of
 // jobs removed and of cotasks folded in — in ONE synchronisation; the new queue length is the only value the host needs before it
 // sizes the considerable filters' launches.  A carry (carry_host.hpp) is enqueued in the same place, over the same old rows.
+// A release (release_host.hpp) is enqueued behind the carry and the fold, also when there is nothing to advance over; its counters ride
+// in the same synchronisation.
 #pragma once
 #include "queue_kernels.hpp"
 
@@ -11,7 +13,7 @@ struct QueueBufs {
   DArr<int> removed;
   DArr<SumI> scan, gscan;
   DArr<uint32_t> ranked_tmp, g_off[2], g_host[2], g_attr[2];
-  DArr<unsigned> add_cnt, cursor, counters;  // counters: [0] jobs removed, [1] cotasks folded in
+  DArr<unsigned> add_cnt, cursor, counters;  // counters: [0] jobs removed, [1] cotasks folded in, then the release's (REL_CNT_*)
   DArr<uint8_t> skipped;
   unsigned cur = 0;  // which of g_*[2] holds the groups' current cotask table (when e->q_groups_own)
 };
@@ -26,11 +28,12 @@ void queue_reset_groups(cook_engine* e) {
 }
 
 // everything that can refuse a step, before anything changes
-void queue_check_step(cook_engine* e, const cook_queue_step* s, const cook_queue_carry* c = nullptr) {
+void queue_check_step(cook_engine* e, const cook_queue_step* s, const cook_queue_carry* c = nullptr, const cook_finished* f = nullptr) {
   if (!e->cycle_staged || !e->q_valid || !e->rank_done || !e->match_ran())
     e->fail(COOK_E_STATE, "cook_cycle_run_queue needs a completed cycle (cook_cycle_run, cook_cycle_run_rank* + cook_cycle_match_multi or a queue "
                           "cycle) with no cook_cycle_stage / cook_cycle_update / cook_rank* / cook_considerable / cook_match_stage since");
   carry_check(e, s, c);
+  release_check(e, s, f);
   if (!s) return;
   if (s->remove_mode > 1u) e->fail(COOK_E_INVALID, "cook_queue_step.remove_mode: 0 = the kept matches, 1 = every considered job");
   if (s->offer_skipped && s->n_offer_skipped != e->M)
@@ -57,18 +60,19 @@ void queue_check_step(cook_engine* e, const cook_queue_step* s, const cook_queue
 }
 
 // steps 1-3 of a queue cycle (cookmatch.h): the last cycle's jobs leave the queue, their cotasks join the groups, fresh offers
-void queue_advance(cook_engine* e, const cook_queue_step* s, const cook_queue_carry* c = nullptr) {
-  queue_check_step(e, s, c);
+void queue_advance(cook_engine* e, const cook_queue_step* s, const cook_queue_carry* c = nullptr, const cook_finished* f = nullptr) {
+  queue_check_step(e, s, c, f);
   const auto t_call = std::chrono::steady_clock::now();
   e->q_valid = false;  // from here on the queue is being edited: a call that fails below leaves no standing queue (cycle_take_part sets it again)
   QueueBufs& b = bufs(e->qb);
   MatchIn& in = e->min;
   const unsigned n = e->n_ranked, k = e->cycle_considered, G = e->G, M_old = e->M;
   const bool fold = G && k && in.j_group && !(s && s->groups);
-  unsigned* cnt = b.counters.ensure(2);
-  const bool advance = k && n;
+  unsigned* cnt = b.counters.ensure(REL_CNT_WORDS);
+  const bool advance = k && n, release = release_active(f);
+  bool carried = false;
+  if (advance || release) memset_async(e, cnt, 0, REL_CNT_WORDS * 4);
   if (advance) {
-    memset_async(e, cnt, 0, 8);
     int* removed = b.removed.ensure(n);
     memset_async(e, removed, 0, (size_t)n * 4);
     unsigned* add_cnt = b.add_cnt.ensure(std::max(1u, G));
@@ -79,7 +83,7 @@ void queue_advance(cook_engine* e, const cook_queue_step* s, const cook_queue_ca
     const uint32_t* j_index = e->j_index.ptr();
     KM<q_mark_removed, 256>(e, "q_mark_removed", div_up(k, 256), e->q_last_pos, j2o, k, n, skipped, (unsigned)(s && s->remove_mode == 1u), j_index,
         in.j_group, G, (unsigned)fold, removed, add_cnt, cnt);
-    if (c) carry_enqueue(e, c, skipped, k);  // (the carried offer columns are the staged ones from here: the fold below reads hosts and attributes, which stay)
+    if (c) carried = carry_enqueue(e, c, skipped, k);  // (the carried offer columns are the staged ones from here: the fold below reads hosts and attributes, which stay)
     // ---- the queue: stable compaction, back into the resident buffer ----------------------------------------------------------------
     b.scan.ensure(n);
     uint32_t* tmp = b.ranked_tmp.ensure(n);
@@ -109,6 +113,9 @@ void queue_advance(cook_engine* e, const cook_queue_step* s, const cook_queue_ca
     }
     pinned_copy(e, e->h_scratch, cnt, 8, hipMemcpyDeviceToHost);
   }
+  // ---- the release: behind the carry and the fold, whether or not the last cycle considered anything ------------------------------------
+  if (f || e->rlb) release_enqueue(e, f, cnt, carried, (advance && fold) ? k : 0u);
+  if (release) pinned_copy(e, e->h_scratch + REL_H_CNT, cnt, REL_CNT_WORDS * 4, hipMemcpyDeviceToHost);
   // ---- the step's groups and offers (behind the kernels above on the stream: the fold read the OLD offers) ------------------------------
   if (s && s->groups && G) {
     const cook_groups* g = s->groups;
@@ -128,13 +135,18 @@ void queue_advance(cook_engine* e, const cook_queue_step* s, const cook_queue_ca
   }
   if (s && s->offers) match_stage_offers(e, s->offers, false);
   carry_tokens(e, c);
-  if (advance || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
+  if (advance || release || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
   if (c) carry_finish(e);
   if (advance) {
     unsigned h[2] = {0, 0};
     std::memcpy(h, e->h_scratch, 8);
     e->n_ranked = n - h[0];
     if (fold) e->cf_group_run_total += h[1];
+  }
+  if (release) {
+    unsigned h[REL_CNT_WORDS];
+    std::memcpy(h, e->h_scratch + REL_H_CNT, sizeof(h));
+    release_finish(e, h);
   }
   e->q_advance_us = (uint32_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count();
 }

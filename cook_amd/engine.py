@@ -313,6 +313,23 @@ class Engine:
         self._chk(self._lib.cook_cycle_run_queue_carry(self._h, C.byref(st), C.byref(cs) if cs is not None else None, int(num_considerable)))
         del keep
 
+    def cycle_run_queue_release(self, num_considerable: int, carry: Optional[A.QueueCarry] = None, finished: Optional[A.Finished] = None, **step):
+        """cycle_run_queue_carry with the release (cook_cycle_run_queue_release): behind the carry and the groups' fold the resources of
+        the `finished` tasks go back to the staged offers (finished.offers), out of the staged user state (finished.usage) and out of the
+        groups' running cotasks (finished.groups), on the device, in list order.  finished None: exactly cycle_run_queue_carry."""
+        st, keep = self._queue_step(**step)
+        cs = carry.as_struct() if carry is not None else None
+        fs, fkeep = finished.as_struct() if finished is not None else (None, None)
+        self._chk(self._lib.cook_cycle_run_queue_release(self._h, C.byref(st), C.byref(cs) if cs is not None else None,
+                                                         C.byref(fs) if fs is not None else None, int(num_considerable)))
+        del keep, fkeep
+
+    def release_info(self) -> dict:
+        """The counts of the last queue cycle's release (cook_cycle_release_info); all 0 when it had none."""
+        out = A.CookReleaseInfo()
+        self._chk(self._lib.cook_cycle_release_info(self._h, C.byref(out)))
+        return {k: int(getattr(out, k)) for k, _ in A.CookReleaseInfo._fields_}
+
     def cycle_fetch(self, out=None):
         """-> (ranked task indices, job_to_offer by rank position, head matched).  `out` = (u32 buffer, i32 buffer) to fetch into
         (e.g. page-locked arrays of a PinnedArena, each with room for every pending task): views of them are returned."""
@@ -847,6 +864,32 @@ def cycle_run_queue_carry_multi(engines: Sequence[Engine], num_considerable, ste
     ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
     cptrs = (C.c_void_p * n)(*[C.addressof(c) if c is not None else None for c in cs])
     _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_carry_multi(arr, n, ptrs, cptrs, ks))
+
+
+def cycle_run_queue_release_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None,
+                                  carries: Optional[Sequence[Optional[A.QueueCarry]]] = None,
+                                  finished: Optional[Sequence[Optional[A.Finished]]] = None):
+    """cycle_run_queue_carry_multi with one list of finished tasks per engine (cook_cycle_run_queue_release_multi; None: no release for
+    that pool); cycle_match_multi places them.  A pool whose step, carry or list is refused stays as it was and raises after the
+    others have gone on."""
+    if not engines:
+        return
+    n = len(engines)
+    arr = (C.c_void_p * n)(*[e._h for e in engines])
+    ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
+    assert len(ks) == n
+    ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
+    steps = list(steps) if steps is not None else [None] * n
+    carries = list(carries) if carries is not None else [None] * n
+    finished = list(finished) if finished is not None else [None] * n
+    assert len(steps) == n and len(carries) == n and len(finished) == n
+    built = [e._queue_step(**(s or {})) for e, s in zip(engines, steps)]
+    cs = [c.as_struct() if c is not None else None for c in carries]
+    fs = [f.as_struct() if f is not None else (None, None) for f in finished]
+    ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
+    cptrs = (C.c_void_p * n)(*[C.addressof(c) if c is not None else None for c in cs])
+    fptrs = (C.c_void_p * n)(*[C.addressof(f) if f is not None else None for f, _ in fs])
+    _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_release_multi(arr, n, ptrs, cptrs, fptrs, ks))
 
 
 def cycle_match_multi(engines: Sequence[Engine]):

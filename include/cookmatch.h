@@ -571,7 +571,8 @@ int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_que
  *     tokens_left is honoured whatever the two flags say.  Quotas, enforce_rate_limit and the eligible mask stay as staged.
  * Refused before anything changes: offers = 1 together with step->offers, a flag above 1, tokens_left while the staged state has no
  * limiter (COOK_E_INVALID); usage = 1 or tokens_left without a staged user state (COOK_E_STATE).
- * Not carried, the host's to tell: finished tasks and new hosts (step->offers / cook_cycle_update), the time-based token refill
+ * Not carried, the host's to tell: finished tasks (cook_cycle_run_queue_release below takes their list) and new hosts (step->offers /
+ * cook_cycle_update), the time-based token refill
  * (tokens_left).  carry NULL, or both flags 0 and no tokens: exactly cook_cycle_run_queue / _multi. */
 typedef struct cook_queue_carry {
   uint32_t offers;            /* 1: carry the kept placements into the staged offers (then step->offers must be NULL) */
@@ -582,6 +583,67 @@ int cook_cycle_run_queue_carry(cook_engine* e, const cook_queue_step* step, cons
 /* as cook_cycle_run_queue_multi (then cook_cycle_match_multi); steps / carries NULL or an entry NULL: defaults */
 int cook_cycle_run_queue_carry_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps,
                                      const cook_queue_carry* const* carries, const uint32_t* num_considerable);
+
+/* ---- THE RELEASE: a queue cycle that gives the resources of FINISHED tasks back, the inverse of the carry -----------------------------
+ * In the reference this is nobody's arithmetic either: Fenzo unassigns finished tasks before scheduleOnce (scheduler.clj:665-669), so
+ * the host's lease and running totals get the resources back; generate-user-usage-map (:711-727) no longer counts the task; the group
+ * constraints no longer see the instance as a running cotask (constraints.clj:553-566).  A queue cycle takes the short list of the tasks
+ * that ended since the last cycle and, on the device, returns their resources to the staged offers, takes them out of the staged user
+ * state and of the pool usage, and removes them from the groups' running-cotask lists, with no synchronisation of its own.
+ * Position in the advance: behind the carry and behind the groups' fold (a task placed last cycle may have finished already), in
+ * front of the step's considerable filters; it also runs when the last cycle considered nothing or the queue is empty.
+ * Order rule (oracle-defined, like the carry's): every fp64 sum runs over the entries of its segment in LIST order, left to right,
+ * from 0.0, x = x + r one entry after another, no re-association.
+ *  offers = 1.  The row of an entry is the staged offer whose host equals the entry's host; an entry whose host has no row changes no
+ *     offer and is counted in without_row.  For a row, with R_c, R_m, R_n, R_ports, R_s[s] the sums over its entries (count, positive
+ *     port counts, non-NaN named scalars): cpus += R_c, mem += R_m, run_cpus -= R_c, run_mem -= R_m, run_count = max(0, run_count - R_n),
+ *     num_tasks = max(0, num_tasks - R_n), ports += R_ports, scalars[s] += R_s[s]; a row where either count was clamped adds one to
+ *     counts_clamped.  For a k8s row, entry after entry in list order: gpus > 0 with a model adds the gpus to the gpu_count slot of that
+ *     model, disk_request >= 0 with a type adds it to the disk_space slot of that type; no such slot: nothing changes.  run_cpus /
+ *     run_mem / run_count / num_tasks / ports that were staged as NULL (all 0) come into existence first, as in the carry; a named
+ *     scalar or a slot table the offers have no column for stays absent.  Neither the caller's arrays nor the rows of cook_offers_run
+ *     are written, and the columns the last match read stay as they were (cook_match_explain): behind a carry of the same advance the
+ *     release updates the carry's fresh copy in place, without one it writes a fresh copy of its own.
+ *  usage = 1.  Per user, over its entries in list order: usage_count[u] -= count, usage_cpus[u] / usage_mem[u] / usage_gpus[u] -= the
+ *     left-to-right sums.  With pool_usage_given the pool usage shrinks by the same four quantities summed over ALL entries in list
+ *     order.  Tokens, quotas and the eligible mask are untouched.
+ *  groups = 1.  On the table as it stands after this advance's fold: for every entry with a group g, in list order, the first row of
+ *     g's list (in the list's order) whose run_host equals the entry's host and that no earlier entry took leaves the list; an entry
+ *     that finds none is counted in cotasks_missing.  The survivors keep their order.
+ * Refused before anything changes.  COOK_E_INVALID: a flag above 1; offers = 1 together with step->offers; groups = 1 together with
+ * step->groups; offers = 1 while two staged offers are on one host; host / cpus / mem missing (user missing with usage = 1);
+ * n_scalars > COOK_MAX_SCALARS; cpus, mem, gpus or a scalar negative or infinite, cpus / mem / gpus / disk_request NaN; a user >= the
+ * staged users; a group >= the staged groups that is not COOK_NONE_U32.  COOK_E_STATE: usage = 1 without a user state staged by
+ * cook_cycle_set_considerable.  A refused step leaves the queue, the offers, the usage and the groups as they were.
+ * finished NULL, n = 0 or all three flags 0: exactly cook_cycle_run_queue_carry / _carry_multi.  The arrays are read until the call
+ * returns.  cook_user_stats / cook_unscheduled / cook_usage_breakdown keep describing the last RANK.  Taking finished rows out of the
+ * rank's task table stays with cook_cycle_update and the next rank; new hosts stay with step->offers.  (Additive: no existing
+ * layout changes.) */
+typedef struct cook_finished {      /* tasks that ended since the last cycle, in the host's order (the order rule above) */
+  uint32_t n;
+  const uint32_t* host;             /* [n] host id, as cook_offers.host / cook_groups.run_host */
+  const uint32_t* user;             /* [n]; required with usage = 1 */
+  const double *cpus, *mem;         /* [n] required */
+  const double* gpus;               /* [n] or NULL (all 0) */
+  const int32_t* ports;             /* [n] or NULL; only positive counts are returned */
+  const double* scalars; uint32_t n_scalars;   /* n_scalars columns of n doubles as cook_jobs.scalars, NaN = no request under that name */
+  const uint32_t* gpu_model; const double* disk_request; const uint32_t* disk_type;  /* as cook_jobs; NULL = none */
+  const uint32_t* group;            /* [n] or NULL; COOK_NONE_U32 = no group */
+  uint32_t offers, usage, groups;   /* 0 / 1 each: what to release into */
+} cook_finished;
+typedef struct cook_release_info {
+  uint32_t with_row, without_row;            /* entries whose host has / has no row in the staged offers (offers = 1) */
+  uint32_t counts_clamped;                   /* offers whose run_count or num_tasks would have gone below 0 */
+  uint32_t cotasks_removed, cotasks_missing; /* groups = 1 */
+} cook_release_info;
+int cook_cycle_run_queue_release(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
+                                 uint32_t num_considerable);
+/* as cook_cycle_run_queue_carry_multi (then cook_cycle_match_multi); finished NULL or an entry NULL: no release for that pool */
+int cook_cycle_run_queue_release_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps,
+                                       const cook_queue_carry* const* carries, const cook_finished* const* finished,
+                                       const uint32_t* num_considerable);
+/* the counts of the last queue cycle's release; all 0 when it had none */
+int cook_cycle_release_info(cook_engine* e, cook_release_info* out);
 
 /* ---- REBALANCE: replaces init-state + the rebalance loop's decisions ---------------------------------------
  * (rebalancer.clj:222-266, 320-407, 270-309, 434-467; dru.clj:128-144).

@@ -2,7 +2,8 @@
 """Seeded random sweep of the engine against the oracle (TEST TOOL): small random configurations of rank / cycle / match / explain /
 cycle update and of the rebalancer, both match_algo values, eval split caps, ports / named scalars, k8s gpu maps with several entries;
 `--carry N`: queue cycles with and without the carry (cook_cycle_run_queue / cook_cycle_run_queue_carry) against tests/carry_oracle.py,
-from random draws of their own (the other legs' draws do not depend on N).
+from random draws of their own (the other legs' draws do not depend on N); `--release N`: the same kind of queue cycles with random lists
+of finished tasks beside the carry's draws (cook_cycle_run_queue_release) against tests/release_oracle.py, again from draws of their own.
 `--emu` runs the SIMT-emulator build on the CPU, otherwise libcookmatch.so on the GPU.  Prints one line; exit 1 on the first
 difference (with the configuration that produced it)."""
 import argparse
@@ -23,6 +24,8 @@ def main():
     ap.add_argument("--multi", type=int, default=0, help="multi-pool configurations (2-8 random pools through ONE cook_cycle_match_multi: served walkers with "
                                                           "1-3 serve streams, or lockstep launches; pools that disagree on good-enough / K)")
     ap.add_argument("--carry", type=int, default=0, help="queue-cycle configurations: random pools, user states, skipped offers, remove modes, carry flags, token refills")
+    ap.add_argument("--release", type=int, default=0, help="queue-cycle configurations as --carry, with random lists of finished tasks: placements of the cycles so far "
+                                                            "(some twice), hosts without a row, random release flags")
     ap.add_argument("--emu", action="store_true")
     ap.add_argument("--scale", type=float, default=1.0, help="size factor of the configurations")
     ap.add_argument("--algo", type=int, default=-1, help="force cook_params.match_algo (default: drawn per configuration)")
@@ -122,8 +125,8 @@ def main():
         except AssertionError as ex:
             print("FAIL rebalance", it, kw, str(ex)[:300])
             sys.exit(1)
-    crng = np.random.default_rng([args.seed, 0xCA22])  # its own stream: the legs above draw what they drew before this leg existed
-    for it in range(args.carry):
+
+    def draw_queue_case(crng):
         from tests import autoscale_cases as AS
         from tests import carry_cases as K
         from tests import carry_oracle as O
@@ -154,10 +157,53 @@ def main():
                 cy.tokens_left = crng.integers(0, 40, st.n).astype(np.int64)
             if cy.offers is not None:
                 m_last = cy.offers.n
+        return kw, p, pool, cycles, k, with_state
+
+    crng = np.random.default_rng([args.seed, 0xCA22])  # its own stream: the legs above draw what they drew before this leg existed
+    for it in range(args.carry):
+        kw, p, pool, cycles, k, with_state = draw_queue_case(crng)
+        from tests import carry_cases as K
+        from tests import carry_oracle as O
+        from tests import queue_cases as S
         try:
             S.compare(K.run_engine(make_engine, p, pool, cycles), O.oracle(p, pool, cycles), cycles)
         except AssertionError as ex:
             print("FAIL carry", it, kw, p.match_algo, p.good_enough_fitness, k, str(ex)[:300])
+            sys.exit(1)
+    rrng = np.random.default_rng([args.seed, 0x4E1EA5E])  # its own stream again
+    for it in range(args.release):
+        from tests import release_cases as X
+        from tests import release_oracle as R
+        kw, p, pool, cycles, k, with_state = draw_queue_case(rrng)
+        grouped = pool.groups is not None and pool.pending_jobs.group is not None
+
+        def ends(cy):
+            frac, twice, lost = rrng.uniform(0.05, 0.9), rrng.random() < 0.3, rrng.random() < 0.4
+            flags = dict(offers=int(cy.offers is None and rrng.random() < 0.8), usage=int(with_state and rrng.random() < 0.8),
+                         groups=int(grouped and rrng.random() < 0.8))
+            seed = int(rrng.integers(1, 1 << 30))
+
+            def draw(history):
+                g = np.random.default_rng(seed)
+                picks = [q for q in R.placed_rows(history) if g.random() < frac]
+                if twice:
+                    picks = picks + picks[::3]
+                picks = [picks[x] for x in g.permutation(len(picks))]
+                fin = R.finished_of(history, picks, **flags)
+                if fin is not None and lost:  # some entries on hosts that have no row (one id far above every staged one)
+                    where = g.random(fin.n) < 0.2
+                    fin.host[where] = g.choice([1 << 20, 3, 77777], size=int(where.sum())).astype(np.uint32)
+                if fin is not None and fin.offers and len(set(history[-1].offers.host.tolist())) < history[-1].offers.n:
+                    fin.offers = 0  # (two staged offers on one host: the engine refuses offers = 1)
+                return fin
+            return draw
+        for cy in cycles[1:]:
+            cy.finished = ends(cy) if rrng.random() < 0.85 else None
+        try:
+            want = R.oracle(p, pool, cycles)
+            X.compare(X.run_engine(make_engine, p, pool, cycles), want, cycles)
+        except AssertionError as ex:
+            print("FAIL release", it, kw, p.match_algo, p.good_enough_fitness, k, str(ex)[:300])
             sys.exit(1)
     guard = ""
     if args.guard:
@@ -170,7 +216,7 @@ def main():
             print(f"FAIL guard: {hits} writes outside a device buffer (COOK_GUARD lines on stderr)")
             sys.exit(1)
         guard = ", COOK_GUARD=1: no write outside a device buffer"
-    print(f"fuzz ok: {args.match} match / cycle configurations, {args.multi} multi-pool configurations, {args.rebalance} rebalancer configurations, {args.carry} queue-cycle configurations, seed {args.seed}, "
+    print(f"fuzz ok: {args.match} match / cycle configurations, {args.multi} multi-pool configurations, {args.rebalance} rebalancer configurations, {args.carry} queue-cycle configurations, {args.release} with releases, seed {args.seed}, "
           f"{'emulator' if args.emu else 'gpu'}{guard}")
 
 
