@@ -1,14 +1,55 @@
-// carry_host.hpp — host orchestration of the carry (cook_cycle_run_queue_carry*, cookmatch.h).  Included by engine.hip
-// inside its anonymous namespace, behind match_host.hpp (MatchIn's staging), considerable_host.hpp (ConsBufs) and rank_host.hpp
+// carry_host.hpp — host orchestration of the carry (cook_cycle_run_queue_carry*, cookmatch.h), and in front of it what
+// the carry, the release and the advance share: QueueArgs, the read-back slots, groups_install, SegSort.  Included by engine.hip inside
+// its anonymous namespace, behind match_host.hpp (MatchIn's staging), considerable_host.hpp (ConsBufs) and rank_host.hpp
 // (radix_sort_masked); queue_host.hpp calls carry_check from queue_check_step and carry_enqueue / carry_finish from queue_advance.
 // Everything is enqueued on the advance's stream over the OLD offers and the OLD considered rows; the only thing the host reads back,
 // the pool's four sums, rides in the advance's one synchronisation.
 #pragma once
 #include "carry_kernels.hpp"
 
+// what a queue cycle's entry point was given (carry, finished: null = none)
+struct QueueArgs {
+  const cook_queue_step* step;
+  const cook_queue_carry* carry;
+  const cook_finished* finished;
+};
+
+// where a queue cycle's advance lands its read-backs in h_scratch, in 64-bit words: the advance's two counters (1 word), the carry's
+// pool (4 doubles), the release's counters (REL_CNT_WORDS of 4 bytes) and its pool (4 doubles)
+constexpr unsigned Q_H_ADVANCE = 0, Q_H_CARRY_POOL = 1, REL_H_CNT = 8, REL_H_POOL = 12;  // (release_host.hpp asserts that they do not overlap)
+
+// a queue cycle's table of the groups' cotasks takes the place of the one in use; the staged one is kept for the next rank
+void groups_install(cook_engine* e, const uint32_t* off, const uint32_t* host, const uint32_t* attr) {
+  MatchIn& in = e->min;
+  if (!e->q_groups_own) {
+    e->q_sg_off = in.g_run_off, e->q_sg_host = in.g_run_host, e->q_sg_attr = in.g_run_attr, e->q_sg_total = e->cf_group_run_total;
+    e->q_groups_own = true;
+  }
+  in.g_run_off = off, in.g_run_host = host, in.g_run_attr = attr;
+}
+
+static unsigned long long carry_key_mask(unsigned max_key) {
+  unsigned long long m = 0;
+  for (unsigned long long x = max_key; x; x >>= 1) m = (m << 1) | 1ull;
+  return m;
+}
+// the positions [0, k) of a key column, stably sorted by key (-> the permutation), and the segments [start[x], end[x]) of the keys below n_seg
+struct SegSort {
+  DArr<uint32_t> permA, permB, start, end;
+  const uint32_t* carry_segments(cook_engine* e, const uint64_t* key, unsigned k, unsigned n_seg) {
+    permA.ensure(k), permB.ensure(k);
+    start.ensure(n_seg), end.ensure(n_seg);
+    memset_async(e, start.ptr(), 0, (size_t)n_seg * 4);
+    memset_async(e, end.ptr(), 0, (size_t)n_seg * 4);
+    KM<iota_u32, 256>(e, "iota", div_up(k, 256), permA.ptr(), k);
+    const uint32_t* perm = radix_sort_masked(e, key, carry_key_mask(n_seg), permA.ptr(), permA.ptr(), permB.ptr(), k);
+    KM<carry_seg_bounds, 256>(e, "carry_seg_bounds", div_up(k, 256), perm, key, k, n_seg, start.ptr(), end.ptr());
+    return perm;
+  }
+};
 struct CarryBufs {
   DArr<uint64_t> okey, ukey;
-  DArr<uint32_t> o_permA, o_permB, u_permA, u_permB, o_start, o_end, u_start, u_end;
+  SegSort o, u;
   DArr<double> pool;  // {count, cpus, mem, gpus} of all kept jobs
   // the engine's own copy of the offer columns a carry changes; two sets: a carry reads the staged columns (which may be the other set)
   // and writes a fresh one, so the last match's inputs (cook_match_explain) stay as they were
@@ -21,7 +62,9 @@ struct CarryBufs {
 };
 
 // what can refuse a carry, before anything changes (queue_check_step)
-void carry_check(cook_engine* e, const cook_queue_step* s, const cook_queue_carry* c) {
+void carry_check(cook_engine* e, const QueueArgs& q) {
+  const cook_queue_step* s = q.step;
+  const cook_queue_carry* c = q.carry;
   if (!c) return;
   if (c->offers > 1u || c->usage > 1u) e->fail(COOK_E_INVALID, "cook_queue_carry: offers / usage are 0 or 1");
   if (c->offers && s && s->offers)
@@ -34,22 +77,31 @@ void carry_check(cook_engine* e, const cook_queue_step* s, const cook_queue_carr
   if (c->usage && !e->has_j_user) e->fail(COOK_E_INVALID, "cook_queue_carry: usage = 1 needs pending_jobs->user");
 }
 
-static unsigned long long carry_key_mask(unsigned max_key) {
-  unsigned long long m = 0;
-  for (unsigned long long x = max_key; x; x >>= 1) m = (m << 1) | 1ull;
-  return m;
+// a fold of the offers: `ci` the staged offer columns, `co` the set w of the engine's own
+static void carry_offer_cols(const MatchIn& in, unsigned M, CarryBufs::Cols& w, CarryOfferIn& ci, CarryOfferCols& co) {
+  const unsigned gs = in.gpu_slots ? in.gpu_slots : 1u, ds = in.disk_slots ? in.disk_slots : 1u;
+  ci = CarryOfferIn{}, co = CarryOfferCols{};
+  ci.cpus = in.o_cpus, ci.mem = in.o_mem, ci.run_cpus = in.o_run_cpus, ci.run_mem = in.o_run_mem;
+  ci.gpu_count = in.o_gpu_count, ci.disk_space = in.o_disk_space;
+  ci.run_count = in.o_run_count, ci.num_tasks = in.o_num_tasks, ci.ports = in.o_ports;
+  ci.k8s = in.o_k8s, ci.gpu_model = in.o_gpu_model, ci.disk_type = in.o_disk_type;
+  ci.gpu_slots = gs, ci.disk_slots = ds;
+  co.cpus = w.cpus.ensure(M), co.mem = w.mem.ensure(M), co.run_cpus = w.run_cpus.ensure(M), co.run_mem = w.run_mem.ensure(M);
+  co.run_count = w.run_count.ensure(M), co.num_tasks = w.num_tasks.ensure(M), co.ports = w.ports.ensure(M);
+  for (unsigned s = 0; s < 3u; ++s) {
+    ci.scal[s] = in.o_scal[s];
+    co.scal[s] = in.o_scal[s] ? w.scal[s].ensure(M) : nullptr;
+  }
+  co.gpu_count = in.o_gpu_count ? w.gpu_count.ensure((size_t)M * gs) : nullptr;
+  co.disk_space = in.o_disk_space ? w.disk_space.ensure((size_t)M * ds) : nullptr;
 }
-// considered positions, stably sorted by key; the segments [start[x], end[x]) of the keys below n_seg
-static const uint32_t* carry_segments(cook_engine* e, const uint64_t* key, unsigned k, unsigned n_seg, DArr<uint32_t>& pa, DArr<uint32_t>& pb,
-                                      DArr<uint32_t>& start, DArr<uint32_t>& end) {
-  pa.ensure(k), pb.ensure(k);
-  start.ensure(n_seg), end.ensure(n_seg);
-  memset_async(e, start.ptr(), 0, (size_t)n_seg * 4);
-  memset_async(e, end.ptr(), 0, (size_t)n_seg * 4);
-  KM<iota_u32, 256>(e, "iota", div_up(k, 256), pa.ptr(), k);
-  const uint32_t* perm = radix_sort_masked(e, key, carry_key_mask(n_seg), pa.ptr(), pa.ptr(), pb.ptr(), k);
-  KM<carry_seg_bounds, 256>(e, "carry_seg_bounds", div_up(k, 256), perm, key, k, n_seg, start.ptr(), end.ptr());
-  return perm;
+// the written columns are the staged offers from here on (hosts, attributes and limits are the same rows: host_dup and the greatest
+// host id stay valid; every match packs its offers afresh, so nothing else is cached per offer table)
+static void carry_stage_cols(MatchIn& in, const CarryOfferCols& co) {
+  in.o_cpus = co.cpus, in.o_mem = co.mem, in.o_run_cpus = co.run_cpus, in.o_run_mem = co.run_mem;
+  in.o_run_count = co.run_count, in.o_num_tasks = co.num_tasks, in.o_ports = co.ports;
+  for (unsigned s = 0; s < 3u; ++s) in.o_scal[s] = co.scal[s];
+  in.o_gpu_count = co.gpu_count, in.o_disk_space = co.disk_space;
 }
 
 // Inside queue_advance, behind q_mark_removed: k > 0 considered jobs of the last cycle, their job_to_offer in e->m_j2o, their rows
@@ -74,42 +126,24 @@ bool carry_enqueue(cook_engine* e, const cook_queue_carry* c, const uint8_t* ski
   if (!okey && !ukey) return false;
   KM<carry_keys, 256>(e, "carry_keys", div_up(k, 256), j2o, k, skipped, (const uint32_t*)j.j_index, (const uint32_t*)e->j_user.ptr(), M, U, okey, ukey);
   if (offers) {
-    const uint32_t* perm = carry_segments(e, okey, k, M, b.o_permA, b.o_permB, b.o_start, b.o_end);
-    CarryBufs::Cols& w = b.cols[b.cur ^ 1u];
-    const unsigned gs = in.gpu_slots ? in.gpu_slots : 1u, ds = in.disk_slots ? in.disk_slots : 1u;
-    CarryOfferIn ci{};
-    ci.cpus = in.o_cpus, ci.mem = in.o_mem, ci.run_cpus = in.o_run_cpus, ci.run_mem = in.o_run_mem;
-    ci.gpu_count = in.o_gpu_count, ci.disk_space = in.o_disk_space;
-    ci.run_count = in.o_run_count, ci.num_tasks = in.o_num_tasks, ci.ports = in.o_ports;
-    ci.k8s = in.o_k8s, ci.gpu_model = in.o_gpu_model, ci.disk_type = in.o_disk_type;
-    ci.gpu_slots = gs, ci.disk_slots = ds;
-    CarryOfferCols co{};
-    co.cpus = w.cpus.ensure(M), co.mem = w.mem.ensure(M), co.run_cpus = w.run_cpus.ensure(M), co.run_mem = w.run_mem.ensure(M);
-    co.run_count = w.run_count.ensure(M), co.num_tasks = w.num_tasks.ensure(M), co.ports = w.ports.ensure(M);
-    for (unsigned s = 0; s < 3u; ++s) {
-      ci.scal[s] = in.o_scal[s];
-      co.scal[s] = in.o_scal[s] ? w.scal[s].ensure(M) : nullptr;
-    }
-    co.gpu_count = in.o_gpu_count ? w.gpu_count.ensure((size_t)M * gs) : nullptr;
-    co.disk_space = in.o_disk_space ? w.disk_space.ensure((size_t)M * ds) : nullptr;
-    KM<carry_fold_offers, CARRY_OT>(e, "carry_fold_offers", M, perm, (const uint32_t*)b.o_start.ptr(), (const uint32_t*)b.o_end.ptr(), M, j, ci, co);
-    // the carried columns are the staged offers from here on (hosts, attributes and limits are the same rows: host_dup and the
-    // greatest host id stay valid; every match packs its offers afresh, so nothing else is cached per offer table)
+    const uint32_t* perm = b.o.carry_segments(e, okey, k, M);
+    CarryOfferIn ci;
+    CarryOfferCols co;
+    carry_offer_cols(in, M, b.cols[b.cur ^ 1u], ci, co);
+    KM<fold_offers<false>, FOLD_OT>(e, "carry_fold_offers", M, perm, (const uint32_t*)b.o.start.ptr(), (const uint32_t*)b.o.end.ptr(), M, 1u, j, ci, co,
+        (unsigned*)nullptr);
     b.cur ^= 1u;
-    in.o_cpus = co.cpus, in.o_mem = co.mem, in.o_run_cpus = co.run_cpus, in.o_run_mem = co.run_mem;
-    in.o_run_count = co.run_count, in.o_num_tasks = co.num_tasks, in.o_ports = co.ports;
-    for (unsigned s = 0; s < 3u; ++s) in.o_scal[s] = co.scal[s];
-    in.o_gpu_count = co.gpu_count, in.o_disk_space = co.disk_space;
+    carry_stage_cols(in, co);
   }
   if (usage) {
     ConsBufs& cb = *e->cb;
-    const uint32_t* perm = carry_segments(e, ukey, k, U, b.u_permA, b.u_permB, b.u_start, b.u_end);
+    const uint32_t* perm = b.u.carry_segments(e, ukey, k, U);
     int64_t* spend = (cb.has_tokens && !c->tokens_left) ? cb.tokens.ptr() : nullptr;
-    KM<carry_fold_users, CARRY_UT>(e, "carry_fold_users", U, perm, (const uint32_t*)b.u_start.ptr(), (const uint32_t*)b.u_end.ptr(), U, j, cb.ucount.ptr(),
-        cb.ucpus.ptr(), cb.umem.ptr(), cb.ugpus.ptr(), spend);
+    KM<fold_users<false, RowsSorted>, FOLD_UT>(e, "carry_fold_users", U, RowsSorted{perm, j}, (const uint32_t*)b.u.start.ptr(),
+        (const uint32_t*)b.u.end.ptr(), U, cb.ucount.ptr(), cb.ucpus.ptr(), cb.umem.ptr(), cb.ugpus.ptr(), spend);
     if (cb.pool_usage_given) {
-      KM<carry_fold_pool, CARRY_UT>(e, "carry_fold_pool", 1, j2o, k, skipped, j, b.pool.ensure(4));
-      pinned_copy(e, e->h_scratch + 1, b.pool.ptr(), 32, hipMemcpyDeviceToHost);
+      KM<fold_pool<false, RowsKept>, FOLD_UT>(e, "carry_fold_pool", 1, RowsKept{j2o, skipped, j}, k, b.pool.ensure(4));
+      pinned_copy(e, e->h_scratch + Q_H_CARRY_POOL, b.pool.ptr(), 32, hipMemcpyDeviceToHost);
       b.pool_pending = true;
     }
   }
@@ -126,7 +160,7 @@ void carry_finish(cook_engine* e) {
   if (!e->cyb || !e->cyb->pool_pending) return;
   e->cyb->pool_pending = false;
   double h[4];
-  std::memcpy(h, e->h_scratch + 1, 32);
+  std::memcpy(h, e->h_scratch + Q_H_CARRY_POOL, 32);
   cook_usage& p = e->cb->pool_usage;
   p.count = p.count + h[0], p.cpus = p.cpus + h[1], p.mem = p.mem + h[2], p.gpus = p.gpus + h[3];
 }

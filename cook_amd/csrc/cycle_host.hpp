@@ -51,14 +51,13 @@ static unsigned cycle_rank_part(cook_engine* e, uint32_t num_considerable) {
   return cycle_take_part(e, num_considerable);
 }
 // a queue cycle's part in front of the placement: advance -> cycle_take_part, no rank
-static unsigned cycle_queue_part(cook_engine* e, const cook_queue_step* step, uint32_t num_considerable, const cook_queue_carry* carry = nullptr,
-                                 const cook_finished* finished = nullptr) {
+static unsigned cycle_queue_part(cook_engine* e, const QueueArgs& q, uint32_t num_considerable) {
   if (recording()) {
-    queue_advance(e, step, carry, finished);
+    queue_advance(e, q);
     return cycle_take_part(e, num_considerable);
   }
   StageTimer tr(e, 0, &e->rank_ms);
-  queue_advance(e, step, carry, finished);
+  queue_advance(e, q);
   const unsigned K = cycle_take_part(e, num_considerable);
   tr.stop();
   return K;

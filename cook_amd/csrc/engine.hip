@@ -568,67 +568,42 @@ int cook_cycle_run_rank_multi(cook_engine** engines, uint32_t n, const uint32_t*
       /*rank_part=*/true);
 }
 // ---- queue cycles: match cycles on the standing ranked queue, without a re-rank (cookmatch.h) -----------------------------------
+// (with the carry, carry_host.hpp: the kept placements into the staged offers and the staged user state, inside the advance; with the
+// release, release_host.hpp: finished tasks' resources back into the staged offers, user state and groups, behind the carry)
 int cook_cycle_run_queue(cook_engine* e, const cook_queue_step* step, uint32_t num_considerable) {
-  return cycle_run_one(e, [&] { return cycle_queue_part(e, step, num_considerable); }, /*defer=*/false);
+  return cook_cycle_run_queue_release(e, step, nullptr, nullptr, num_considerable);
 }
 int cook_cycle_run_queue_rank(cook_engine* e, const cook_queue_step* step, uint32_t num_considerable) {
-  return cycle_run_one(e, [&] { return cycle_queue_part(e, step, num_considerable); }, /*defer=*/true);
+  return cycle_run_one(e, [&] { return cycle_queue_part(e, QueueArgs{step, nullptr, nullptr}, num_considerable); }, /*defer=*/true);
 }
-// ... for every pool of a GPU: one flow per pool in a pool batch, as cook_cycle_run_rank_multi
-int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const uint32_t* num_considerable) {
+int cook_cycle_run_queue_carry(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, uint32_t num_considerable) {
+  return cook_cycle_run_queue_release(e, step, carry, nullptr, num_considerable);
+}
+int cook_cycle_run_queue_release(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
+                                 uint32_t num_considerable) {
+  return cycle_run_one(e, [&] { return cycle_queue_part(e, QueueArgs{step, carry, finished}, num_considerable); }, /*defer=*/false);
+}
+// ... for every pool of a GPU: one flow per pool in a pool batch, as cook_cycle_run_rank_multi (steps, carries, finished: null = none)
+static int queue_run_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
+                           const cook_finished* const* finished, const uint32_t* num_considerable) {
   if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
+  auto args = [&](uint32_t i) { return QueueArgs{steps ? steps[i] : nullptr, carries ? carries[i] : nullptr, finished ? finished[i] : nullptr}; };
   return run_pools_batched(
-      engines, n, [&](uint32_t i) { return cook_cycle_run_queue_rank(engines[i], steps ? steps[i] : nullptr, num_considerable[i]); },
-      [&](uint32_t i) {
-        cook_engine* e = engines[i];
-        const unsigned K = cycle_queue_part(e, steps ? steps[i] : nullptr, num_considerable[i]);
-        cycle_match(e, K, /*defer=*/true);
-      },
+      engines, n,
+      [&](uint32_t i) { return cycle_run_one(engines[i], [&] { return cycle_queue_part(engines[i], args(i), num_considerable[i]); }, /*defer=*/true); },
+      [&](uint32_t i) { cycle_match(engines[i], cycle_queue_part(engines[i], args(i), num_considerable[i]), /*defer=*/true); },
       /*rank_part=*/true);
 }
-// ... with the carry (carry_host.hpp): the kept placements into the staged offers and the staged user state, inside the advance
-int cook_cycle_run_queue_carry(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, uint32_t num_considerable) {
-  return cycle_run_one(e, [&] { return cycle_queue_part(e, step, num_considerable, carry); }, /*defer=*/false);
+int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const uint32_t* num_considerable) {
+  return queue_run_multi(engines, n, steps, nullptr, nullptr, num_considerable);
 }
 int cook_cycle_run_queue_carry_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
                                      const uint32_t* num_considerable) {
-  if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
-  auto step = [&](uint32_t i) { return steps ? steps[i] : nullptr; };
-  auto carry = [&](uint32_t i) { return carries ? carries[i] : nullptr; };
-  return run_pools_batched(
-      engines, n,
-      [&](uint32_t i) {
-        return cycle_run_one(engines[i], [&] { return cycle_queue_part(engines[i], step(i), num_considerable[i], carry(i)); }, /*defer=*/true);
-      },
-      [&](uint32_t i) {
-        cook_engine* e = engines[i];
-        const unsigned K = cycle_queue_part(e, step(i), num_considerable[i], carry(i));
-        cycle_match(e, K, /*defer=*/true);
-      },
-      /*rank_part=*/true);
-}
-// ... and the release (release_host.hpp): finished tasks' resources back into the staged offers, user state and groups, behind the carry
-int cook_cycle_run_queue_release(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
-                                 uint32_t num_considerable) {
-  return cycle_run_one(e, [&] { return cycle_queue_part(e, step, num_considerable, carry, finished); }, /*defer=*/false);
+  return queue_run_multi(engines, n, steps, carries, nullptr, num_considerable);
 }
 int cook_cycle_run_queue_release_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
                                        const cook_finished* const* finished, const uint32_t* num_considerable) {
-  if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
-  auto step = [&](uint32_t i) { return steps ? steps[i] : nullptr; };
-  auto carry = [&](uint32_t i) { return carries ? carries[i] : nullptr; };
-  auto fin = [&](uint32_t i) { return finished ? finished[i] : nullptr; };
-  return run_pools_batched(
-      engines, n,
-      [&](uint32_t i) {
-        return cycle_run_one(engines[i], [&] { return cycle_queue_part(engines[i], step(i), num_considerable[i], carry(i), fin(i)); }, /*defer=*/true);
-      },
-      [&](uint32_t i) {
-        cook_engine* e = engines[i];
-        const unsigned K = cycle_queue_part(e, step(i), num_considerable[i], carry(i), fin(i));
-        cycle_match(e, K, /*defer=*/true);
-      },
-      /*rank_part=*/true);
+  return queue_run_multi(engines, n, steps, carries, finished, num_considerable);
 }
 int cook_cycle_release_info(cook_engine* e, cook_release_info* out) {
   return guarded(e, [&] {

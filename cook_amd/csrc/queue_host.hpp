@@ -28,12 +28,13 @@ void queue_reset_groups(cook_engine* e) {
 }
 
 // everything that can refuse a step, before anything changes
-void queue_check_step(cook_engine* e, const cook_queue_step* s, const cook_queue_carry* c = nullptr, const cook_finished* f = nullptr) {
+void queue_check_step(cook_engine* e, const QueueArgs& q) {
+  const cook_queue_step* s = q.step;
   if (!e->cycle_staged || !e->q_valid || !e->rank_done || !e->match_ran())
     e->fail(COOK_E_STATE, "cook_cycle_run_queue needs a completed cycle (cook_cycle_run, cook_cycle_run_rank* + cook_cycle_match_multi or a queue "
                           "cycle) with no cook_cycle_stage / cook_cycle_update / cook_rank* / cook_considerable / cook_match_stage since");
-  carry_check(e, s, c);
-  release_check(e, s, f);
+  carry_check(e, q);
+  release_check(e, q);
   if (!s) return;
   if (s->remove_mode > 1u) e->fail(COOK_E_INVALID, "cook_queue_step.remove_mode: 0 = the kept matches, 1 = every considered job");
   if (s->offer_skipped && s->n_offer_skipped != e->M)
@@ -60,8 +61,11 @@ void queue_check_step(cook_engine* e, const cook_queue_step* s, const cook_queue
 }
 
 // steps 1-3 of a queue cycle (cookmatch.h): the last cycle's jobs leave the queue, their cotasks join the groups, fresh offers
-void queue_advance(cook_engine* e, const cook_queue_step* s, const cook_queue_carry* c = nullptr, const cook_finished* f = nullptr) {
-  queue_check_step(e, s, c, f);
+void queue_advance(cook_engine* e, const QueueArgs& q) {
+  queue_check_step(e, q);
+  const cook_queue_step* s = q.step;
+  const cook_queue_carry* c = q.carry;
+  const cook_finished* f = q.finished;
   const auto t_call = std::chrono::steady_clock::now();
   e->q_valid = false;  // from here on the queue is being edited: a call that fails below leaves no standing queue (cycle_take_part sets it again)
   QueueBufs& b = bufs(e->qb);
@@ -104,14 +108,10 @@ void queue_advance(cook_engine* e, const cook_queue_step* s, const cook_queue_ca
         KM<q_fold_copy_old, 256>(e, "q_fold_copy_old", div_up(n_old, 256), in.g_run_off, in.g_run_host, in.g_run_attr, G, n_old, (const uint32_t*)n_off, n_host, n_attr);
       KM<q_fold_append, 256>(e, "q_fold_append", div_up(k, 256), j2o, k, skipped, j_index, in.j_group, G, in.g_run_off, (const uint32_t*)n_off, cursor,
           in.o_host, in.o_attr, in.n_attr, in.g_attr_key, n_host, n_attr);
-      if (!e->q_groups_own) {
-        e->q_sg_off = in.g_run_off, e->q_sg_host = in.g_run_host, e->q_sg_attr = in.g_run_attr, e->q_sg_total = e->cf_group_run_total;
-        e->q_groups_own = true;
-      }
       b.cur = nx;
-      in.g_run_off = n_off, in.g_run_host = n_host, in.g_run_attr = n_attr;
+      groups_install(e, n_off, n_host, n_attr);
     }
-    pinned_copy(e, e->h_scratch, cnt, 8, hipMemcpyDeviceToHost);
+    pinned_copy(e, e->h_scratch + Q_H_ADVANCE, cnt, 8, hipMemcpyDeviceToHost);
   }
   // ---- the release: behind the carry and the fold, whether or not the last cycle considered anything ------------------------------------
   if (f || e->rlb) release_enqueue(e, f, cnt, carried, (advance && fold) ? k : 0u);
@@ -120,16 +120,12 @@ void queue_advance(cook_engine* e, const cook_queue_step* s, const cook_queue_ca
   if (s && s->groups && G) {
     const cook_groups* g = s->groups;
     const unsigned nx = b.cur ^ (e->q_groups_own ? 1u : 0u);
-    if (!e->q_groups_own) {
-      e->q_sg_off = in.g_run_off, e->q_sg_host = in.g_run_host, e->q_sg_attr = in.g_run_attr, e->q_sg_total = e->cf_group_run_total;
-      e->q_groups_own = true;
-    }
     const unsigned nr = g->run_off[G];
-    in.g_run_off = h2d_opt(e, b.g_off[nx], g->run_off, G + 1);
+    const uint32_t* n_off = h2d_opt(e, b.g_off[nx], g->run_off, G + 1);
     b.g_host[nx].ensure(std::max(1u, nr)), b.g_attr[nx].ensure(std::max(1u, nr));
     if (nr) copy_async(e, b.g_host[nx].ptr(), g->run_host, (size_t)nr * 4, hipMemcpyHostToDevice);
     if (nr) copy_async(e, b.g_attr[nx].ptr(), g->run_attr, (size_t)nr * 4, hipMemcpyHostToDevice);
-    in.g_run_host = b.g_host[nx].ptr(), in.g_run_attr = b.g_attr[nx].ptr();
+    groups_install(e, n_off, b.g_host[nx].ptr(), b.g_attr[nx].ptr());
     b.cur = nx;
     e->cf_group_run_total = nr;
   }
@@ -139,7 +135,7 @@ void queue_advance(cook_engine* e, const cook_queue_step* s, const cook_queue_ca
   if (c) carry_finish(e);
   if (advance) {
     unsigned h[2] = {0, 0};
-    std::memcpy(h, e->h_scratch, 8);
+    std::memcpy(h, e->h_scratch + Q_H_ADVANCE, 8);
     e->n_ranked = n - h[0];
     if (fold) e->cf_group_run_total += h[1];
   }

@@ -1,5 +1,5 @@
 // release_host.hpp — host orchestration of the release (cook_cycle_run_queue_release*, cookmatch.h).  Included by
-// engine.hip inside its anonymous namespace, behind carry_host.hpp (carry_segments, CarryBufs' column sets); queue_host.hpp calls
+// engine.hip inside its anonymous namespace, behind carry_host.hpp (SegSort, CarryBufs' column sets); queue_host.hpp calls
 // release_check from queue_check_step and release_enqueue / release_finish from queue_advance.  Everything is enqueued on the advance's
 // stream behind the carry and the groups' fold; what the host reads back — three counters behind the advance's two, and the pool's four
 // sums — rides in the advance's one synchronisation.
@@ -15,7 +15,7 @@ struct ReleaseBufs {
   DArr<int32_t> ports;
   DArr<uint32_t> h2row;  // host id -> row of the staged offers
   DArr<uint64_t> okey, ukey, gkey;
-  DArr<uint32_t> o_permA, o_permB, u_permA, u_permB, g_permA, g_permB, o_start, o_end, u_start, u_end, g_start, g_end;
+  SegSort o, u, g;
   DArr<double> pool;  // {count, cpus, mem, gpus} of all entries
   // the groups' table behind a release, two of them: a release reads the table in use (staged, folded, or the other one of these) and
   // writes the one the last match cannot have read
@@ -30,13 +30,16 @@ struct ReleaseBufs {
   unsigned n_group_entries = 0;
 };
 
-// where the release's read-backs land in h_scratch (64-bit words; the advance's two counters are word 0, the carry's pool words 1..4)
-constexpr unsigned REL_H_CNT = 8, REL_H_POOL = 12;
+// the read-back slots of carry_host.hpp, now that every size is known
+static_assert(Q_H_ADVANCE + 1 <= Q_H_CARRY_POOL && Q_H_CARRY_POOL + 4 <= REL_H_CNT && REL_H_CNT + (REL_CNT_WORDS + 1) / 2 <= REL_H_POOL && REL_H_POOL + 4 <= 64,
+              "the queue advance's read-backs overlap in h_scratch");
 
 static bool release_active(const cook_finished* f) { return f && f->n && (f->offers || f->usage || f->groups); }
 
 // what can refuse a release, before anything changes (queue_check_step)
-void release_check(cook_engine* e, const cook_queue_step* s, const cook_finished* f) {
+void release_check(cook_engine* e, const QueueArgs& q) {
+  const cook_queue_step* s = q.step;
+  const cook_finished* f = q.finished;
   if (!f) return;
   if (f->offers > 1u || f->usage > 1u || f->groups > 1u) e->fail(COOK_E_INVALID, "cook_finished: offers / usage / groups are 0 or 1");
   if (!release_active(f)) return;
@@ -106,6 +109,7 @@ void release_enqueue(cook_engine* e, const cook_finished* f, unsigned* cnt, bool
     for (unsigned s = 0; s < 3u; ++s)
       l.scal[s] = (f->scalars && s < f->n_scalars) ? h2d_opt(e, b.scal[s], f->scalars + (size_t)s * n, n) : nullptr;
   }
+  const CarryJobs rows = l.rows();
   // ---- keys ---------------------------------------------------------------------------------------------------------------------------
   const uint32_t* h2row = nullptr;
   unsigned n_hosts = 0;
@@ -122,52 +126,35 @@ void release_enqueue(cook_engine* e, const cook_finished* f, unsigned* cnt, bool
   KM<release_keys, 256>(e, "release_keys", div_up(n, 256), l, n, h2row, n_hosts, in.o_host, offers ? M : 0u, U, groups ? G : 0u, okey, ukey, gkey, cnt);
   // ---- offers -------------------------------------------------------------------------------------------------------------------------
   if (offers) {
-    const uint32_t* perm = carry_segments(e, okey, n, M, b.o_permA, b.o_permB, b.o_start, b.o_end);
+    const uint32_t* perm = b.o.carry_segments(e, okey, n, M);
     CarryBufs& cy = bufs(e->cyb);
     // behind a carry of this advance: its fresh set, in place (one wave owns one row); else a fresh set of its own, every row written
-    CarryBufs::Cols& w = cy.cols[carried ? cy.cur : (cy.cur ^ 1u)];
-    const unsigned gs = in.gpu_slots ? in.gpu_slots : 1u, ds = in.disk_slots ? in.disk_slots : 1u;
-    CarryOfferIn ci{};
-    ci.cpus = in.o_cpus, ci.mem = in.o_mem, ci.run_cpus = in.o_run_cpus, ci.run_mem = in.o_run_mem;
-    ci.gpu_count = in.o_gpu_count, ci.disk_space = in.o_disk_space;
-    ci.run_count = in.o_run_count, ci.num_tasks = in.o_num_tasks, ci.ports = in.o_ports;
-    ci.k8s = in.o_k8s, ci.gpu_model = in.o_gpu_model, ci.disk_type = in.o_disk_type;
-    ci.gpu_slots = gs, ci.disk_slots = ds;
-    CarryOfferCols co{};
-    co.cpus = w.cpus.ensure(M), co.mem = w.mem.ensure(M), co.run_cpus = w.run_cpus.ensure(M), co.run_mem = w.run_mem.ensure(M);
-    co.run_count = w.run_count.ensure(M), co.num_tasks = w.num_tasks.ensure(M), co.ports = w.ports.ensure(M);
-    for (unsigned s = 0; s < 3u; ++s) {
-      ci.scal[s] = in.o_scal[s];
-      co.scal[s] = in.o_scal[s] ? w.scal[s].ensure(M) : nullptr;
-    }
-    co.gpu_count = in.o_gpu_count ? w.gpu_count.ensure((size_t)M * gs) : nullptr;
-    co.disk_space = in.o_disk_space ? w.disk_space.ensure((size_t)M * ds) : nullptr;
-    KM<release_fold_offers, RELEASE_OT>(e, "release_fold_offers", M, perm, (const uint32_t*)b.o_start.ptr(), (const uint32_t*)b.o_end.ptr(), M,
-        carried ? 0u : 1u, l, ci, co, cnt);
+    CarryOfferIn ci;
+    CarryOfferCols co;
+    carry_offer_cols(in, M, cy.cols[carried ? cy.cur : (cy.cur ^ 1u)], ci, co);
+    KM<fold_offers<true>, FOLD_OT>(e, "release_fold_offers", M, perm, (const uint32_t*)b.o.start.ptr(), (const uint32_t*)b.o.end.ptr(), M,
+        carried ? 0u : 1u, rows, ci, co, cnt + REL_CNT_CLAMPED);
     if (!carried) cy.cur ^= 1u;
-    in.o_cpus = co.cpus, in.o_mem = co.mem, in.o_run_cpus = co.run_cpus, in.o_run_mem = co.run_mem;
-    in.o_run_count = co.run_count, in.o_num_tasks = co.num_tasks, in.o_ports = co.ports;
-    for (unsigned s = 0; s < 3u; ++s) in.o_scal[s] = co.scal[s];
-    in.o_gpu_count = co.gpu_count, in.o_disk_space = co.disk_space;
+    carry_stage_cols(in, co);
   }
   // ---- the users and the pool ----------------------------------------------------------------------------------------------------------
   if (usage) {
     ConsBufs& cb = *e->cb;
-    const uint32_t* perm = carry_segments(e, ukey, n, U, b.u_permA, b.u_permB, b.u_start, b.u_end);
-    KM<release_fold_users, RELEASE_UT>(e, "release_fold_users", U, perm, (const uint32_t*)b.u_start.ptr(), (const uint32_t*)b.u_end.ptr(), U, l,
-        cb.ucount.ptr(), cb.ucpus.ptr(), cb.umem.ptr(), cb.ugpus.ptr());
+    const uint32_t* perm = b.u.carry_segments(e, ukey, n, U);
+    KM<fold_users<true, RowsSorted>, FOLD_UT>(e, "release_fold_users", U, RowsSorted{perm, rows}, (const uint32_t*)b.u.start.ptr(),
+        (const uint32_t*)b.u.end.ptr(), U, cb.ucount.ptr(), cb.ucpus.ptr(), cb.umem.ptr(), cb.ugpus.ptr(), (int64_t*)nullptr);
     if (cb.pool_usage_given) {
-      KM<release_fold_pool, RELEASE_UT>(e, "release_fold_pool", 1, n, l, b.pool.ensure(4));
+      KM<fold_pool<true, RowsSorted>, FOLD_UT>(e, "release_fold_pool", 1, RowsSorted{nullptr, rows}, n, b.pool.ensure(4));
       pinned_copy(e, e->h_scratch + REL_H_POOL, b.pool.ptr(), 32, hipMemcpyDeviceToHost);
       b.pool_pending = true;
     }
   }
   // ---- the groups: mark, scan, compact into a table the last match did not read ----------------------------------------------------------
   if (groups) {
-    const uint32_t* perm = carry_segments(e, gkey, n, G, b.g_permA, b.g_permB, b.g_start, b.g_end);
+    const uint32_t* perm = b.g.carry_segments(e, gkey, n, G);
     uint8_t* claimed = b.claimed.ensure(rows_max);
     memset_async(e, claimed, 0, rows_max);
-    KM<release_group_mark, COOK_WAVE>(e, "release_group_mark", G, perm, (const uint32_t*)b.g_start.ptr(), (const uint32_t*)b.g_end.ptr(), G, l.host,
+    KM<release_group_mark, COOK_WAVE>(e, "release_group_mark", G, perm, (const uint32_t*)b.g.start.ptr(), (const uint32_t*)b.g.end.ptr(), G, l.host,
         in.g_run_off, in.g_run_host, rows_max, claimed, cnt);
     const unsigned nx = b.tcur ^ 1u;  // (the table in use, and the one the last match read, may be t_*[tcur]; never t_*[tcur ^ 1])
     uint32_t* n_off = b.t_off[nx].ensure(G + 1);
@@ -179,12 +166,8 @@ void release_enqueue(cook_engine* e, const cook_finished* f, unsigned* cnt, bool
     KM<release_group_offsets, 256>(e, "release_group_offsets", div_up(G + 1, 256), (const SumI*)incl, in.g_run_off, G, n_off);
     KM<release_group_compact, 256>(e, "release_group_compact", div_up(rows_max, 256), (const uint8_t*)claimed, (const SumI*)incl, n_rows, rows_max,
         in.g_run_host, in.g_run_attr, n_host, n_attr);
-    if (!e->q_groups_own) {
-      e->q_sg_off = in.g_run_off, e->q_sg_host = in.g_run_host, e->q_sg_attr = in.g_run_attr, e->q_sg_total = e->cf_group_run_total;
-      e->q_groups_own = true;
-    }
     b.tcur = nx;
-    in.g_run_off = n_off, in.g_run_host = n_host, in.g_run_attr = n_attr;
+    groups_install(e, n_off, n_host, n_attr);
   }
 }
 

@@ -229,6 +229,105 @@ def check_base(make_engine, *, fractional=False, scale=1.0, algo=2, expect_form=
     return check(make_engine, params, pool, cycles, want, expect_form=expect_form)
 
 
+# ---- 2b: the folds' chunk boundaries ----------------------------------------------------------------------------------------------------
+SEG_OFFERS, SEG_USERS = (64, 65, 129, 768), (256, 257, 513)
+
+
+SEG_EXTRA = 18  # jobs behind the 1026
+
+
+def segment_pool(left=(700.0, 701.0, 702.0, 703.0), user_mem=0.3):
+    """1026 jobs of 1 cpu and a non-dyadic mem (0.1 .. 0.9) that three users own 256, 257 and 513 of, and four hosts of 64, 65, 129 and
+    768 cpus with mem that never limits: whatever order the matcher places in, K = 1026 fills every host exactly.  Behind them in rank
+    order (the dru of a user's n-th 1-cpu job is n): eleven more jobs of the largest user — one of 1 cpu; per host, greatest `left`
+    first, a pair of NO cpus whose mem is left[host] and the next double above it; two more of 1 cpu —, two jobs of 1000 cpus of each
+    of the other two users (user 1's first asks for user_mem, its second for no mem: only the count can reject it), and three jobs of a fourth user whose share is tiny."""
+    n = sum(SEG_USERS)
+    user = np.array([u for i in range(SEG_USERS[2]) for u in range(3) if i < SEG_USERS[u]] + [2] * 11 + [0, 0, 1, 1] + [3] * 3, np.uint32)
+    assert np.array_equal(np.bincount(user[:n]), SEG_USERS) and len(user) == n + SEG_EXTRA
+    N = len(user)
+    cpus, mem = np.ones(N), 0.1 * (1 + np.arange(N) % 9)
+    cpus[n + 1:n + 9] = 0.0
+    mem[n + 1:n + 9] = [x for v in np.argsort(left)[::-1] for x in (left[v], np.nextafter(left[v], np.inf))]
+    cpus[n + 11:n + 15], mem[n + 13:n + 15] = 1000.0, (user_mem, 0.0)
+    tasks = A.Tasks(cpus=cpus, mem=mem, user=user, priority=np.full(N, 50, np.int32), start_ms=np.zeros(N, np.int64),
+                    task_id=(10_000 + np.arange(N)).astype(np.int64), job_id=(100 + np.arange(N)).astype(np.int64), pending=np.ones(N, np.uint8))
+    users = A.Users(div_cpus=np.array([1.0, 1.0, 1.0, 1e-6]), div_mem=np.full(4, A.DMAX))
+    oc = np.array(SEG_OFFERS, np.float64)
+    offers = A.Offers(cpus=oc, mem=oc.copy(), host=np.arange(4, dtype=np.uint32), k8s=np.zeros(4, np.uint8), run_cpus=np.ones(4), run_mem=np.ones(4),
+                      run_count=np.ones(4, np.int32))
+    return SimpleNamespace(tasks=tasks, users=users, pending_jobs=A.Jobs(cpus=cpus.copy(), mem=mem.copy(), user=user.copy()), offers=offers, groups=None)
+
+
+def segment_state(quota_mem_1=A.DMAX):
+    """nobody is limited in the first cycle; behind its carry users 0 and 1 have room for ONE more job each, the largest user for nine,
+    the pool for twelve; user 1's mem quota is quota_mem_1"""
+    ucount = np.array([3.0, 5.0, 7.0, 2.0])
+    qcount = np.full(4, 2.0 ** 31 - 1)
+    qcount[:3] = ucount[:3] + np.array(SEG_USERS) + np.array([1.0, 1.0, 9.0])
+    qmem = np.full(4, A.DMAX)
+    qmem[1] = quota_mem_1
+    pu = A.usage(17.0, 17.0 * 3.0 + 0.1, 17.0 * 0.7, 0.0)
+    return A.UserState(quota_count=qcount, quota_cpus=np.full(4, A.DMAX), quota_mem=qmem, quota_gpus=np.full(4, A.DMAX),
+                       usage_count=ucount, usage_cpus=ucount * 3.0 + 0.1, usage_mem=ucount * 0.7, usage_gpus=np.zeros(4),
+                       pool_quota=A.quota(count=pu.count + sum(SEG_USERS) + 12.0), pool_usage=pu)
+
+
+def oracle_stale_user(params, pool, cycles, col, u, put=lambda old, new: old):
+    """the oracle's cycles with ONE user's entry of a usage column not carried (put: what it holds instead, from the stale and the
+    carried value)"""
+    real = O.carry_usage
+
+    def patched(st, jobs, hit, spend):
+        new = real(st, jobs, hit, spend)
+        getattr(new, col)[u] = put(getattr(st, col)[u], getattr(new, col)[u])
+        return new
+    O.carry_usage = patched
+    try:
+        return O.oracle(params, pool, cycles)
+    finally:
+        O.carry_usage = real
+
+
+def check_segment_lengths(make_engine):
+    """ONE advance whose kept placements fill offers with exactly 64, 65 and 129 jobs (a wave's chunk, one more, two chunks and one) and
+    belong to users with exactly 256, 257 and 513 of them (a workgroup's chunk, one more, two chunks and one); the pool's fold runs over
+    all 1026.  The next cycle reads every one of those sums: no cpus are left anywhere; EVERY host's mem is left to the last bit (a job
+    that asks for exactly the remainder fits there and nowhere else, one that asks for the next double fits nowhere); each of the three
+    users' counts admits exactly the jobs it should (one more or one fewer kept job moves the line); user 1's carried mem admits a job
+    at equality with its quota (the next double above the carried sum does not; a smaller sum is not seen: a user's filter rejects
+    everything behind a rejected job, so one user cannot show both sides); the pool's count stops the last user."""
+    params = P1()
+    n = sum(SEG_USERS)
+    eligible = np.ones(n + SEG_EXTRA, np.uint8)
+    cycles = lambda state: [O.cycle(n, state=state, eligible=eligible), O.cycle(n, carry_offers=True, carry_usage=True)]
+    # the carried sums, from the oracle (the jobs behind the 1026 are not seen by the first cycle, whatever they ask for)
+    first = O.oracle(params, segment_pool(), cycles(segment_state()))[1]
+    left, a1 = first.offers.mem, float(first.state.usage_mem[1])
+    assert len(set(left.tolist())) == 4
+    m1 = next(m for m in (0.3, 0.7, 1.1, 1.3, 1.7, 1.9, 2.3) if np.nextafter(a1, np.inf) + m > a1 + m)
+    pool, cyc = segment_pool(left, m1), cycles(segment_state(quota_mem_1=a1 + m1))
+    want = O.oracle(params, pool, cyc)
+    w0, w1 = want
+    assert len(w0.pos) == n and (w0.j2o >= 0).all(), "a placement of the first cycle is not kept"
+    assert np.array_equal(np.sort(np.bincount(w0.j2o)), np.sort(SEG_OFFERS)) and {64, 65, 129} <= set(np.bincount(w0.j2o).tolist())
+    assert {256, 257, 513} <= set(np.bincount(w0.jobs.user).tolist())
+    assert int((np.diff(w0.jobs.user.astype(np.int64)) != 0).sum()) > 500, "the users' jobs are not interleaved in the queue"
+    assert np.array_equal(w1.offers.cpus, np.zeros(4)) and np.array_equal(w1.offers.mem, left) and w1.state.usage_mem[1] == a1
+    # the second cycle: the largest user's 1-cpu job and eight probes pass the filters, its last two do not; ONE job of each of the two
+    # other users does; one job of the last user does.  Only the probes that ask for exactly what a host has left are placed, each there
+    by_left = np.argsort(left)[::-1]
+    assert np.array_equal(w1.jobs.user, [2] * 9 + [0, 1, 3]), w1.jobs.user
+    assert np.array_equal(w1.j2o, [-1] + [x for v in by_left for x in (v, -1)] + [-1, -1, -1]), w1.j2o
+    assert w1.jobs.mem[10] == m1
+    assert_matters(params, pool, cyc, want, offer_cols=("cpus", "mem"), state_cols=("usage_count", "pool_usage"))
+    for u in range(3):
+        assert differs(want, oracle_stale_user(params, pool, cyc, "usage_count", u)), f"the carry of user {u}'s count changes no result"
+    one_up = lambda old, new: np.nextafter(new, np.inf)
+    assert differs(want, oracle_stale_user(params, pool, cyc, "usage_mem", 1, one_up)), "user 1's carried mem is not read to the last bit"
+    return check(make_engine, params, pool, cyc, want)
+
+
 # ---- 3: every column ------------------------------------------------------------------------------------------------------------------
 def check_columns(make_engine, *, null_cols=False, seed=232, k=120, n_cycles=4, n_pending=500):
     params = P1()

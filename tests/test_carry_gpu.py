@@ -28,6 +28,10 @@ def test_carry_non_dyadic(make_engine):
     K.check_base(make_engine, fractional=True)
 
 
+def test_carry_segment_lengths(make_engine):
+    K.check_segment_lengths(make_engine)
+
+
 @pytest.mark.parametrize("null_cols", [False, True])
 def test_carry_every_column(make_engine, null_cols):
     K.check_columns(make_engine, null_cols=null_cols)
