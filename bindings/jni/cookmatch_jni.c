@@ -494,6 +494,120 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleReleaseInfo(JNIEnv* env, jclass
   if (bad || !out) return COOK_E_INVALID;
   return cook_cycle_release_info(H(h), out);
 }
+/* cycleRunQueueRelease with the host churn (cook_cycle_run_queue_hosts; defer != 0: cook_cycle_run_queue_hosts_multi for this one pool, the
+ * placement then runs in cycleMatchMulti); the step carries no offers (a churn edits the STAGED ones).  leave_host: n_leave host ids
+ * whose rows leave the staged offers, or null.  join: the m_join rows that join, marshalled as the offers of cycleStage (join_dims as
+ * offer_dims), or null; join_before: m_join host ids of the OLD rows in front of which they go (COOK_NONE_U32: behind the last row), or
+ * null: all at the end. */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueueHosts(JNIEnv* env, jclass c, jlong h, jint num_considerable, jint remove_mode,
+                                                               jint n_last_offers, jobject offer_skipped, jint n_groups, jobjectArray groups,
+                                                               jint carry_offers, jint carry_usage, jint n_users, jobject tokens_left,
+                                                               jint n_finished, jint n_fin_scalars, jobjectArray finished, jint release_offers,
+                                                               jint release_usage, jint release_groups, jint n_leave, jobject leave_host,
+                                                               jint m_join, jobject join_dims, jobjectArray join, jobject join_before,
+                                                               jint defer) {
+  int bad = 0;
+  const jint mj = m_join > 0 ? m_join : 0, nl = n_leave > 0 ? n_leave : 0;
+  cook_offers o = offers_of(env, mj, dims_of(env, join_dims, &bad), join, &bad);
+  cook_groups g = groups_of(env, n_groups, groups, &bad);
+  cook_queue_step s;
+  cook_queue_carry cy;
+  cook_finished f;
+  cook_host_churn hc;
+  const jint nf = n_finished > 0 ? n_finished : 0, ns = n_fin_scalars > 0 ? n_fin_scalars : 0;
+  (void)c;
+  s.offer_skipped = BUFN(const uint8_t, offer_skipped, n_last_offers > 0 ? n_last_offers : 0);
+  s.remove_mode = (uint32_t)remove_mode;
+  s.n_offer_skipped = (uint32_t)(n_last_offers > 0 ? n_last_offers : 0);
+  s.offers = 0;
+  s.groups = groups ? &g : 0;
+  cy.offers = (uint32_t)carry_offers;
+  cy.usage = (uint32_t)carry_usage;
+  cy.tokens_left = BUFN(const int64_t, tokens_left, n_users > 0 ? n_users : 0);
+  f.n = (uint32_t)nf;
+  f.host = EL(const uint32_t, finished, 0, nf);
+  f.user = EL(const uint32_t, finished, 1, nf);
+  f.cpus = EL(const double, finished, 2, nf);
+  f.mem = EL(const double, finished, 3, nf);
+  f.gpus = EL(const double, finished, 4, nf);
+  f.ports = EL(const int32_t, finished, 5, nf);
+  f.scalars = EL(const double, finished, 6, (uint64_t)nf * (uint64_t)ns);
+  f.n_scalars = (uint32_t)ns;
+  f.gpu_model = EL(const uint32_t, finished, 7, nf);
+  f.disk_request = EL(const double, finished, 8, nf);
+  f.disk_type = EL(const uint32_t, finished, 9, nf);
+  f.group = EL(const uint32_t, finished, 10, nf);
+  f.offers = (uint32_t)release_offers;
+  f.usage = (uint32_t)release_usage;
+  f.groups = (uint32_t)release_groups;
+  hc.n_leave = leave_host ? (uint32_t)nl : 0u;
+  hc.leave_host = BUFN(const uint32_t, leave_host, nl);
+  hc.join = join ? &o : 0;
+  hc.join_before = BUFN(const uint32_t, join_before, mj);
+  if (bad) return COOK_E_INVALID;
+  if (defer) {
+    cook_engine* e = H(h);
+    const cook_queue_step* sp = &s;
+    const cook_queue_carry* cp = &cy;
+    const cook_finished* fp = finished ? &f : 0;
+    const cook_host_churn* hp = &hc;
+    const uint32_t k = (uint32_t)num_considerable;
+    return cook_cycle_run_queue_hosts_multi(&e, 1, &sp, &cp, &fp, &hp, &k);
+  }
+  return cook_cycle_run_queue_hosts(H(h), &s, &cy, finished ? &f : 0, &hc, (uint32_t)num_considerable);
+}
+/* the counts of the last queue cycle's host churn (cook_cycle_churn_info): info_out = direct buffer of one cook_churn_info */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleChurnInfo(JNIEnv* env, jclass c, jlong h, jobject info_out) {
+  int bad = 0;
+  cook_churn_info* out = BUF(cook_churn_info, info_out);
+  (void)c;
+  if (bad || !out) return COOK_E_INVALID;
+  return cook_cycle_churn_info(H(h), out);
+}
+/* The staged offer table as the next match will read it (cook_cycle_fetch_offers).  dims_out: direct buffer of 5 jint that receives
+ * {n, gpu_slots, disk_slots, n_attr_keys, n_scalars}; columns: an array of 18 direct buffers in the field order of cook_offer_rows
+ * {cpus, mem, host, k8s, gpu_model, gpu_count, disk_type, disk_space, attr, max_tasks, num_tasks, location, host_start_s, run_cpus,
+ * run_mem, run_count, ports, scalars} (null elements: skipped), each with room for cap rows at the widest shape the header allows
+ * (COOK_MAX_RES_SLOTS map entries, COOK_MAX_SCALARS scalars, max_attr_keys attribute keys); columns == null with cap = 0 asks for the
+ * dims alone (COOK_E_INVALID when there are rows). */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleFetchOffers(JNIEnv* env, jclass c, jlong h, jint cap, jint max_attr_keys, jobject dims_out,
+                                                             jobjectArray columns) {
+  int bad = 0, rc;
+  const uint64_t n = cap > 0 ? (uint64_t)cap : 0u, na = max_attr_keys > 0 ? (uint64_t)max_attr_keys : 0u;
+  jint* dims = BUFN(jint, dims_out, 5);
+  cook_offer_rows r;
+  (void)c;
+  r.cap = (uint32_t)n;
+  r.n = r.gpu_slots = r.disk_slots = r.n_attr_keys = r.n_scalars = 0u;
+  r.cpus = EL(double, columns, 0, n);
+  r.mem = EL(double, columns, 1, n);
+  r.host = EL(uint32_t, columns, 2, n);
+  r.k8s = EL(uint8_t, columns, 3, n);
+  r.gpu_model = EL(uint32_t, columns, 4, n * COOK_MAX_RES_SLOTS);
+  r.gpu_count = EL(double, columns, 5, n * COOK_MAX_RES_SLOTS);
+  r.disk_type = EL(uint32_t, columns, 6, n * COOK_MAX_RES_SLOTS);
+  r.disk_space = EL(double, columns, 7, n * COOK_MAX_RES_SLOTS);
+  r.attr = EL(uint32_t, columns, 8, n * na);
+  r.max_tasks = EL(int32_t, columns, 9, n);
+  r.num_tasks = EL(int32_t, columns, 10, n);
+  r.location = EL(uint32_t, columns, 11, n);
+  r.host_start_s = EL(int64_t, columns, 12, n);
+  r.run_cpus = EL(double, columns, 13, n);
+  r.run_mem = EL(double, columns, 14, n);
+  r.run_count = EL(int32_t, columns, 15, n);
+  r.ports = EL(int32_t, columns, 16, n);
+  r.scalars = EL(double, columns, 17, n * COOK_MAX_SCALARS);
+  if (bad || !dims) return COOK_E_INVALID;
+  if (r.attr) { /* the staged attribute keys must fit the caller's buffer: ask for the widths first (cap 0 writes no column) */
+    cook_offer_rows probe = {0};
+    rc = cook_cycle_fetch_offers(H(h), &probe);
+    if (rc != COOK_OK && probe.n == 0u) return rc;
+    if ((uint64_t)probe.n_attr_keys > na) return COOK_E_INVALID;
+  }
+  rc = cook_cycle_fetch_offers(H(h), &r);
+  dims[0] = (jint)r.n, dims[1] = (jint)r.gpu_slots, dims[2] = (jint)r.disk_slots, dims[3] = (jint)r.n_attr_keys, dims[4] = (jint)r.n_scalars;
+  return rc;
+}
 /* the running usage of n staged engines of one device in ONE call (cook_rank_pool_usage_multi): usage_out = direct buffer of n cook_usage */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_rankPoolUsageMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n, jobject usage_out) {
   cook_engine* es[64];

@@ -200,6 +200,81 @@ class Finished:
         return st, (a, cols)
 
 
+class CookHostChurn(C.Structure):  # cook_cycle_run_queue_hosts*
+    _fields_ = [("n_leave", C.c_uint32), ("leave_host", _u32p), ("join", C.POINTER(CookOffers)), ("join_before", _u32p)]
+
+
+class CookChurnInfo(C.Structure):  # cook_cycle_churn_info
+    _fields_ = [("left", C.c_uint32), ("leave_missing", C.c_uint32), ("joined", C.c_uint32), ("n_offers", C.c_uint32)]
+
+
+ChurnInfo = CookChurnInfo
+
+
+class CookOfferRows(C.Structure):  # cook_cycle_fetch_offers
+    _fields_ = [("cap", C.c_uint32), ("n", C.c_uint32), ("gpu_slots", C.c_uint32), ("disk_slots", C.c_uint32), ("n_attr_keys", C.c_uint32),
+                ("n_scalars", C.c_uint32),
+                ("cpus", _f64p), ("mem", _f64p), ("host", _u32p), ("k8s", _u8p), ("gpu_model", _u32p), ("gpu_count", _f64p),
+                ("disk_type", _u32p), ("disk_space", _f64p), ("attr", _u32p), ("max_tasks", _i32p), ("num_tasks", _i32p),
+                ("location", _u32p), ("host_start_s", _i64p), ("run_cpus", _f64p), ("run_mem", _f64p), ("run_count", _i32p),
+                ("ports", _i32p), ("scalars", _f64p)]
+
+
+class HostChurn:
+    """The hosts that leave and the rows that join the staged offers in a queue cycle (cook_host_churn).  leave: host ids; join: an
+    Offers with the joining rows; before: per joining row the host id of the OLD row it goes in front of (NONE_U32: behind the last
+    row; None: all at the end)."""
+
+    def __init__(self, leave=None, join: Optional["Offers"] = None, before=None):
+        self.leave = _arr(leave if leave is not None else [], np.uint32)
+        self.join = join
+        self.before = _arr(before, np.uint32)
+        assert self.before is None or (join is not None and self.before.shape == (join.n,)), "before: one anchor per joining row"
+
+    def as_struct(self):
+        """-> (CookHostChurn, the objects its pointers refer to)"""
+        js = self.join.as_struct() if self.join is not None else None
+        st = CookHostChurn(len(self.leave), _ptr(self.leave, _u32p) if len(self.leave) else _u32p(), C.pointer(js) if js is not None else None,
+                           _ptr(self.before, _u32p))
+        return st, (js, self.leave, self.before, self.join)
+
+
+class OfferRows:
+    """Caller-allocated columns for cook_cycle_fetch_offers (cook_offer_rows): room for `cap` rows at the given widths; `skip` names
+    columns that are passed as NULL.  After the call, offers() returns the fetched table as an Offers with every column."""
+    COLS = (("cpus", np.float64, 1), ("mem", np.float64, 1), ("host", np.uint32, 1), ("k8s", np.uint8, 1), ("gpu_model", np.uint32, "g"),
+            ("gpu_count", np.float64, "g"), ("disk_type", np.uint32, "d"), ("disk_space", np.float64, "d"), ("attr", np.uint32, "a"),
+            ("max_tasks", np.int32, 1), ("num_tasks", np.int32, 1), ("location", np.uint32, 1), ("host_start_s", np.int64, 1),
+            ("run_cpus", np.float64, 1), ("run_mem", np.float64, 1), ("run_count", np.int32, 1), ("ports", np.int32, 1), ("scalars", np.float64, "s"))
+
+    def __init__(self, cap: int, n_attr_keys: int = 0, skip=()):
+        self.cap, self.n_attr_keys = int(cap), max(1, int(n_attr_keys))
+        w = {"g": MAX_RES_SLOTS, "d": MAX_RES_SLOTS, "a": max(1, int(n_attr_keys)), "s": MAX_SCALARS, 1: 1}
+        self.arrays = {name: None if name in skip else np.zeros(max(1, self.cap * w[k]), dt) for name, dt, k in self.COLS}
+        self.struct = CookOfferRows(self.cap, 0, 0, 0, 0, 0, *[_ptr(self.arrays[name], _PT[dt]) for name, dt, _ in self.COLS])
+
+    @property
+    def n(self) -> int:
+        return int(self.struct.n)
+
+    def column(self, name):
+        """the fetched column: [n], [n, width] for the maps and the attributes, [n, n_scalars] for the scalars; None where skipped or
+        of width 0"""
+        st, a = self.struct, self.arrays[name]
+        n = int(st.n)
+        k = {c: kk for c, _, kk in self.COLS}[name]
+        w = {"g": st.gpu_slots, "d": st.disk_slots, "a": st.n_attr_keys, "s": st.n_scalars, 1: 1}[k]
+        if a is None or w == 0:
+            return None
+        if k == "s":
+            return a[:n * w].reshape(w, n).T.copy()
+        out = a[:n * w].copy()
+        return out if k == 1 else out.reshape(n, w)
+
+    def offers(self) -> "Offers":
+        return Offers(**{name: self.column(name) for name, _, _ in self.COLS})
+
+
 class CookRebalanceParams(C.Structure):
     _fields_ = [("safe_dru_threshold", C.c_double), ("min_dru_diff", C.c_double),
                 ("max_preemption", C.c_int32), ("reserved", C.c_int32)]
@@ -219,6 +294,7 @@ class CookPreemption(C.Structure):
 
 MAX_SCALARS, MAX_RES_SLOTS = 3, 4  # COOK_MAX_SCALARS, COOK_MAX_RES_SLOTS
 _DT = {_f64p: np.float64, _u32p: np.uint32, _i32p: np.int32, _i64p: np.int64, _u8p: np.uint8}
+_PT = {v: k for k, v in _DT.items()}
 
 
 def _ptr(arr: Optional[np.ndarray], ptype):

@@ -1,0 +1,258 @@
+// churn_host.hpp — host orchestration of the host churn (cook_cycle_run_queue_hosts*, cook_cycle_fetch_offers, cookmatch.h; DESIGN.md
+// §21).  Included by engine.hip inside its anonymous namespace, behind release_host.hpp (its host-indexed table, SegSort, the counters'
+// read-back); queue_host.hpp calls churn_check from queue_check_step and churn_enqueue / churn_finish from queue_advance.  Everything
+// is enqueued on the advance's stream behind the carry, the groups' fold and the release, which still index the OLD rows; the one
+// counter the host reads back rides in the advance's one synchronisation.  The host knows the new row count before the first launch
+// from its mirror of the staged host ids (cook_engine::o_hosts), so no launch waits for a read-back.
+#pragma once
+#include "churn_kernels.hpp"
+
+struct ChurnBufs {
+  struct Cols {
+    DArr<double> cpus, mem, run_cpus, run_mem, scal[3], gpu_count, disk_space;
+    DArr<uint32_t> host, gpu_model, disk_type, attr, location;
+    DArr<uint8_t> k8s;
+    DArr<int32_t> max_tasks, num_tasks, run_count, ports;
+    DArr<int64_t> host_start;
+  };
+  DArr<uint32_t> leave, before;  // the lists on the device
+  Cols join;                     // ... and the joining rows' columns
+  // the churn's own full column sets, written in turns: a churn reads the staged table (which may be the other set, or partly the
+  // carry's) and writes the set the last match cannot have read
+  Cols set[2];
+  unsigned cur = 0;
+  DArr<uint32_t> h2row, src;
+  DArr<uint8_t> keep;
+  DArr<uint64_t> akey;
+  SegSort a;
+  DArr<SumI> scan;
+  ChurnGather h_args{};  // (read by the upload until the advance's synchronisation)
+  DArr<ChurnGather> d_args;
+  cook_churn_info info{};  // of the last queue cycle
+  bool pending = false;    // this advance reads the churn's counter back
+  // what churn_check worked out from the mirror, for the churn_enqueue of the same step
+  unsigned plan_left = 0, plan_new = 0;
+};
+
+// this step carries into or releases into the staged offers: run_cpus / run_mem / run_count / num_tasks / ports exist from here on
+static bool carry_release_offers(const QueueArgs& q) {
+  return (q.carry && q.carry->offers) || (release_active(q.finished) && q.finished->offers);
+}
+static bool churn_active(const cook_host_churn* h) { return h && (h->n_leave || (h->join && h->join->n)); }
+
+// named scalar columns the staged offers have
+static unsigned churn_staged_scalars(const MatchIn& in) {
+  unsigned n = 0;
+  while (n < (unsigned)COOK_MAX_SCALARS && in.o_scal[n]) ++n;
+  return n;
+}
+
+// what can refuse a churn, before anything changes (queue_check_step)
+void churn_check(cook_engine* e, const QueueArgs& q) {
+  const cook_host_churn* h = q.hosts;
+  if (!churn_active(h)) return;
+  const cook_queue_step* s = q.step;
+  const MatchIn& in = e->min;
+  if (s && s->offers) e->fail(COOK_E_INVALID, "cook_host_churn edits the STAGED offers; step->offers replaces them (one or the other)");
+  if (in.host_dup) e->fail(COOK_E_INVALID, "cook_host_churn: two staged offers are on one host");
+  if (!e->o_hosts_known)
+    e->fail(COOK_E_STATE, "cook_host_churn: the staged offers were built on the device (cook_cycle_stage_built_offers): build them again from the nodes");
+  if (h->n_leave && !h->leave_host) e->fail(COOK_E_INVALID, "cook_host_churn: n_leave without leave_host");
+  const cook_offers* j = h->join;
+  const unsigned nj = j ? j->n : 0u, M_old = e->M;
+  const std::vector<uint32_t>& staged = e->o_hosts;  // ascending
+  if (staged.size() != M_old) e->fail(COOK_E_STATE, "cook_host_churn: the engine's record of the staged hosts is out of step with the staged offers");
+  auto is_staged = [&](uint32_t x) { return std::binary_search(staged.begin(), staged.end(), x); };
+  std::vector<uint32_t> lv(h->leave_host, h->leave_host + h->n_leave);
+  std::sort(lv.begin(), lv.end());
+  if (std::adjacent_find(lv.begin(), lv.end()) != lv.end()) e->fail(COOK_E_INVALID, "cook_host_churn: a host twice in leave_host");
+  unsigned left = 0;
+  for (uint32_t x : lv) left += is_staged(x) ? 1u : 0u;
+  if (nj) {
+    if (!j->cpus || !j->mem || !j->host) e->fail(COOK_E_INVALID, "cook_host_churn: join needs cpus, mem and host");
+    if (j->gpu_model && !j->gpu_count) e->fail(COOK_E_INVALID, "cook_host_churn: join has gpu_model without gpu_count");
+    if (j->disk_type && !j->disk_space) e->fail(COOK_E_INVALID, "cook_host_churn: join has disk_type without disk_space");
+    // (the five columns a carry or a release brings into existence count as present from the first such step on this table on, this
+    //  very advance included, whether or not it had anything to carry or to release: absent, they read as 0 for every row, and the
+    //  gather writes them out when the joining rows bring values)
+    const bool made = e->o_run_cols_made || carry_release_offers(q);
+    const bool lacks = (j->k8s && !in.o_k8s) || (j->gpu_model && !in.o_gpu_model) || (j->gpu_count && !in.o_gpu_count) ||
+                       (j->disk_type && !in.o_disk_type) || (j->disk_space && !in.o_disk_space) || (j->attr && !(in.o_attr && in.n_attr)) ||
+                       (j->max_tasks && !in.o_max_tasks) || (j->num_tasks && !in.o_num_tasks && !made) || (j->location && !in.o_location) ||
+                       (j->host_start_s && !in.o_host_start) || (j->run_cpus && !in.o_run_cpus && !made) || (j->run_mem && !in.o_run_mem && !made) ||
+                       (j->run_count && !in.o_run_count && !made) || (j->ports && !in.o_ports && !made) || (j->scalars && !in.o_scal[0]);
+    if (lacks) e->fail(COOK_E_INVALID, "cook_host_churn: join carries a column the staged offers lack");
+    auto slots = [](uint32_t x) { return x ? x : 1u; };
+    if ((j->gpu_model || j->gpu_count) && slots(j->gpu_slots) != in.gpu_slots) e->fail(COOK_E_INVALID, "cook_host_churn: join->gpu_slots differs from the staged offers'");
+    if ((j->disk_type || j->disk_space) && slots(j->disk_slots) != in.disk_slots) e->fail(COOK_E_INVALID, "cook_host_churn: join->disk_slots differs from the staged offers'");
+    if (j->attr && j->n_attr_keys != in.n_attr) e->fail(COOK_E_INVALID, "cook_host_churn: join->n_attr_keys differs from the staged offers'");
+    if (j->scalars && j->n_scalars != churn_staged_scalars(in)) e->fail(COOK_E_INVALID, "cook_host_churn: join->n_scalars differs from the staged offers'");
+    std::vector<uint32_t> jh(j->host, j->host + nj);
+    std::sort(jh.begin(), jh.end());
+    if (std::adjacent_find(jh.begin(), jh.end()) != jh.end()) e->fail(COOK_E_INVALID, "cook_host_churn: a host twice in join");
+    for (uint32_t x : jh)
+      if (is_staged(x) && !std::binary_search(lv.begin(), lv.end(), x))
+        e->fail(COOK_E_INVALID, "cook_host_churn: a joining host is already staged and does not leave in this call");
+    if (h->join_before)
+      for (unsigned i = 0; i < nj; ++i)
+        if (h->join_before[i] != COOK_NONE_U32 && !is_staged(h->join_before[i]))
+          e->fail(COOK_E_INVALID, "cook_host_churn: join_before names a host that has no row in the staged offers");
+  }
+  const unsigned M_new = M_old - left + nj;
+  match_check_offer_count(e, M_new);
+  ChurnBufs& b = bufs(e->chb);
+  b.plan_left = left, b.plan_new = M_new;
+}
+
+// the columns of a table as the gather reads them
+static ChurnColsT<false> churn_cols_of(const MatchIn& in) {
+  ChurnColsT<false> c{};
+  c.cpus = in.o_cpus, c.mem = in.o_mem, c.host = in.o_host, c.k8s = in.o_k8s;
+  c.gpu_model = in.o_gpu_model, c.gpu_count = in.o_gpu_count, c.disk_type = in.o_disk_type, c.disk_space = in.o_disk_space;
+  c.attr = in.n_attr ? in.o_attr : nullptr;
+  c.max_tasks = in.o_max_tasks, c.num_tasks = in.o_num_tasks, c.location = in.o_location, c.host_start = in.o_host_start;
+  c.run_cpus = in.o_run_cpus, c.run_mem = in.o_run_mem, c.run_count = in.o_run_count, c.ports = in.o_ports;
+  for (unsigned s = 0; s < 3u; ++s) c.scal[s] = in.o_scal[s];
+  return c;
+}
+// the written set is the staged table from here on
+static void churn_stage_cols(MatchIn& in, const ChurnColsT<true>& c, unsigned M) {
+  in.M = M;
+  in.o_cpus = c.cpus, in.o_mem = c.mem, in.o_host = c.host, in.o_k8s = c.k8s;
+  in.o_gpu_model = c.gpu_model, in.o_gpu_count = c.gpu_count, in.o_disk_type = c.disk_type, in.o_disk_space = c.disk_space;
+  in.o_attr = c.attr;
+  in.o_max_tasks = c.max_tasks, in.o_num_tasks = c.num_tasks, in.o_location = c.location, in.o_host_start = c.host_start;
+  in.o_run_cpus = c.run_cpus, in.o_run_mem = c.run_mem, in.o_run_count = c.run_count, in.o_ports = c.ports;
+  for (unsigned s = 0; s < 3u; ++s) in.o_scal[s] = c.scal[s];
+}
+
+// Inside queue_advance, behind the release (so: over the table the NEXT match would have read), also when the last cycle considered
+// nothing.  cnt: QueueBufs::counters, zero on the stream.
+void churn_enqueue(cook_engine* e, const cook_host_churn* h, unsigned* cnt) {
+  ChurnBufs& b = bufs(e->chb);
+  b.info = cook_churn_info{0u, 0u, 0u, e->M};
+  b.pending = false;
+  if (!churn_active(h)) return;
+  MatchIn& in = e->min;
+  const cook_offers* j = h->join;
+  const unsigned M_old = e->M, n_leave = h->n_leave, nj = j ? j->n : 0u, M_new = b.plan_new;
+  const unsigned gs = in.gpu_slots ? in.gpu_slots : 1u, ds = in.disk_slots ? in.disk_slots : 1u, na = in.n_attr;
+  // ---- the lists (read until the advance's synchronisation) ----------------------------------------------------------------------------
+  const uint32_t* leave = h2d_opt(e, b.leave, h->leave_host, n_leave);
+  const uint32_t* before = nj ? h2d_opt(e, b.before, h->join_before, nj) : nullptr;
+  ChurnColsT<false> jc{};
+  if (nj) {
+    ChurnBufs::Cols& w = b.join;
+    jc.cpus = h2d_opt(e, w.cpus, j->cpus, nj), jc.mem = h2d_opt(e, w.mem, j->mem, nj), jc.host = h2d_opt(e, w.host, j->host, nj);
+    jc.k8s = h2d_opt(e, w.k8s, j->k8s, nj);
+    jc.gpu_model = h2d_opt(e, w.gpu_model, j->gpu_model, (size_t)nj * gs), jc.gpu_count = h2d_opt(e, w.gpu_count, j->gpu_count, (size_t)nj * gs);
+    jc.disk_type = h2d_opt(e, w.disk_type, j->disk_type, (size_t)nj * ds), jc.disk_space = h2d_opt(e, w.disk_space, j->disk_space, (size_t)nj * ds);
+    jc.attr = na ? h2d_opt(e, w.attr, j->attr, (size_t)nj * na) : nullptr;
+    jc.max_tasks = h2d_opt(e, w.max_tasks, j->max_tasks, nj), jc.num_tasks = h2d_opt(e, w.num_tasks, j->num_tasks, nj);
+    jc.location = h2d_opt(e, w.location, j->location, nj), jc.host_start = h2d_opt(e, w.host_start, j->host_start_s, nj);
+    jc.run_cpus = h2d_opt(e, w.run_cpus, j->run_cpus, nj), jc.run_mem = h2d_opt(e, w.run_mem, j->run_mem, nj);
+    jc.run_count = h2d_opt(e, w.run_count, j->run_count, nj), jc.ports = h2d_opt(e, w.ports, j->ports, nj);
+    for (unsigned s = 0; s < 3u; ++s)
+      jc.scal[s] = (j->scalars && s < j->n_scalars) ? h2d_opt(e, w.scal[s], j->scalars + (size_t)s * nj, nj) : nullptr;
+  }
+  // ---- rows of the leaving hosts and of the anchors --------------------------------------------------------------------------------------
+  const uint32_t* h2row = nullptr;
+  unsigned n_hosts = 0;
+  if (M_old && e->cf_max_host != 0xFFFFFFFFu && (size_t)e->cf_max_host <= 8u * (size_t)M_old + 65536u) {  // (else churn_row_of looks through o_host)
+    n_hosts = e->cf_max_host + 1u;
+    if (e->rlb && e->rlb->h2row_hosts == n_hosts) {  // the release of this advance has built it, over the same rows
+      h2row = e->rlb->h2row.ptr();
+    } else {
+      uint32_t* t = b.h2row.ensure(n_hosts);
+      memset_async(e, t, 0xFF, (size_t)n_hosts * 4);
+      KM<release_host_rows, 256>(e, "release_host_rows", div_up(M_old, 256), in.o_host, M_old, n_hosts, t);
+      h2row = t;
+    }
+  }
+  uint8_t* keep = b.keep.ensure(M_old);
+  memset_async(e, keep, 1, M_old);
+  uint64_t* akey = b.akey.ensure(nj);
+  KM<churn_mark, 256>(e, "churn_mark", div_up(std::max(n_leave, nj), 256), leave, n_leave, before, nj, h2row, n_hosts, in.o_host, M_old, keep, akey, cnt);
+  // ---- the joins by anchor in list order, ONE scan, the source map -----------------------------------------------------------------------
+  const uint32_t* perm = nj ? b.a.carry_segments(e, akey, nj, M_old + 1u) : nullptr;
+  const LoadChurnRows rows{keep, nj ? (const uint32_t*)b.a.start.ptr() : nullptr, nj ? (const uint32_t*)b.a.end.ptr() : nullptr, M_old};
+  SumI* incl = b.scan.ensure(M_old + 1u);
+  seg_scan<SumI>(e, "churn_scan", rows, (const uint8_t*)nullptr, M_old + 1u, incl, e->tmpI);
+  uint32_t* src = b.src.ensure(M_new);
+  memset_async(e, src, 0xFF, (size_t)M_new * 4);
+  KM<churn_source, 256>(e, "churn_source", div_up(std::max(M_old, nj), 256), rows, (const SumI*)incl, perm, (const uint64_t*)akey, nj, M_new, src);
+  // ---- ONE gather of every column into the set the staged table is not -------------------------------------------------------------------
+  ChurnGather& g = b.h_args;
+  g = ChurnGather{};
+  g.old = churn_cols_of(in), g.join = jc;
+  g.M_old = M_old, g.n_join = nj, g.M_new = M_new, g.gpu_slots = gs, g.disk_slots = ds, g.n_attr = na;
+  ChurnBufs::Cols& w = b.set[b.cur ^ 1u];
+  auto col = [&](auto& darr, const void* staged, size_t width) { return staged ? darr.ensure((size_t)M_new * width) : nullptr; };
+  const void* always = &g;  // cpus, mem and host are columns of every table
+  g.out.cpus = col(w.cpus, always, 1), g.out.mem = col(w.mem, always, 1), g.out.host = col(w.host, always, 1);
+  g.out.k8s = col(w.k8s, g.old.k8s, 1);
+  g.out.gpu_model = col(w.gpu_model, g.old.gpu_model, gs), g.out.gpu_count = col(w.gpu_count, g.old.gpu_count, gs);
+  g.out.disk_type = col(w.disk_type, g.old.disk_type, ds), g.out.disk_space = col(w.disk_space, g.old.disk_space, ds);
+  g.out.attr = col(w.attr, g.old.attr, na);
+  auto either = [](const void* a, const void* b) { return a ? a : b; };  // (the five columns a carry makes: also when only the joining rows have values)
+  g.out.max_tasks = col(w.max_tasks, g.old.max_tasks, 1), g.out.num_tasks = col(w.num_tasks, either(g.old.num_tasks, jc.num_tasks), 1);
+  g.out.location = col(w.location, g.old.location, 1), g.out.host_start = col(w.host_start, g.old.host_start, 1);
+  g.out.run_cpus = col(w.run_cpus, either(g.old.run_cpus, jc.run_cpus), 1), g.out.run_mem = col(w.run_mem, either(g.old.run_mem, jc.run_mem), 1);
+  g.out.run_count = col(w.run_count, either(g.old.run_count, jc.run_count), 1), g.out.ports = col(w.ports, either(g.old.ports, jc.ports), 1);
+  for (unsigned s = 0; s < 3u; ++s) g.out.scal[s] = col(w.scal[s], g.old.scal[s], 1);
+  const ChurnGather* d_args = h2d_opt(e, b.d_args, (const ChurnGather*)&g, 1);
+  KM<churn_gather, 256>(e, "churn_gather", div_up(M_new, 256), d_args, (const uint32_t*)src);
+  b.cur ^= 1u;
+  churn_stage_cols(in, g.out, M_new);
+  e->M = M_new;
+  // ---- the mirror: host_dup stays 0, and the greatest host id stays exact (the class-ordered walk's and the release's tables) --------------
+  std::vector<uint32_t>& staged = e->o_hosts;
+  for (unsigned t = 0; t < n_leave; ++t) {
+    auto it = std::lower_bound(staged.begin(), staged.end(), h->leave_host[t]);
+    if (it != staged.end() && *it == h->leave_host[t]) staged.erase(it);
+  }
+  for (unsigned i = 0; i < nj; ++i) staged.insert(std::lower_bound(staged.begin(), staged.end(), j->host[i]), j->host[i]);
+  e->cf_max_host = staged.empty() ? 0xFFFFFFFFu : staged.back();
+  b.info = cook_churn_info{b.plan_left, 0u, nj, M_new};
+  b.pending = true;
+}
+
+// behind the advance's synchronisation; h: the advance's counters
+void churn_finish(cook_engine* e, const unsigned* h) {
+  if (!e->chb || !e->chb->pending) return;
+  e->chb->pending = false;
+  e->chb->info.leave_missing = h[CHURN_CNT_MISSING];
+}
+
+// cook_cycle_fetch_offers: the staged offer table as the next match will read it, in one synchronisation
+void churn_fetch_offers(cook_engine* e, cook_offer_rows* out) {
+  if (!out) e->fail(COOK_E_INVALID, "cook_cycle_fetch_offers: null out");
+  if (!e->match_staged) e->fail(COOK_E_STATE, "cook_cycle_fetch_offers before offers were staged");
+  const MatchIn& in = e->min;
+  const unsigned n = e->M, gs = in.gpu_slots ? in.gpu_slots : 1u, ds = in.disk_slots ? in.disk_slots : 1u, na = in.o_attr ? in.n_attr : 0u;
+  const unsigned ns = churn_staged_scalars(in);
+  out->n = n, out->gpu_slots = gs, out->disk_slots = ds, out->n_attr_keys = na, out->n_scalars = ns;
+  if (out->cap < n) e->fail(COOK_E_INVALID, "cook_cycle_fetch_offers: cap is smaller than the staged offers' row count (see n)");
+  bool copied = false;
+  auto col = [&](auto* dst, const auto* staged, size_t width, auto none) {
+    if (!dst || !n || !width) return;
+    if (staged) {
+      copy_async(e, dst, staged, (size_t)n * width * sizeof(*dst), hipMemcpyDeviceToHost);
+      copied = true;
+    } else {
+      std::fill(dst, dst + (size_t)n * width, none);
+    }
+  };
+  col(out->cpus, in.o_cpus, 1, 0.0), col(out->mem, in.o_mem, 1, 0.0), col(out->host, in.o_host, 1, (uint32_t)0u);
+  col(out->k8s, in.o_k8s, 1, (uint8_t)0u);
+  col(out->gpu_model, in.o_gpu_model, gs, (uint32_t)0u), col(out->gpu_count, in.o_gpu_count, gs, 0.0);
+  col(out->disk_type, in.o_disk_type, ds, (uint32_t)0u), col(out->disk_space, in.o_disk_space, ds, 0.0);
+  col(out->attr, in.o_attr, na, (uint32_t)0u);
+  col(out->max_tasks, in.o_max_tasks, 1, (int32_t)-1), col(out->num_tasks, in.o_num_tasks, 1, (int32_t)0);
+  col(out->location, in.o_location, 1, (uint32_t)0u), col(out->host_start_s, in.o_host_start, 1, (int64_t)-1);
+  col(out->run_cpus, in.o_run_cpus, 1, 0.0), col(out->run_mem, in.o_run_mem, 1, 0.0), col(out->run_count, in.o_run_count, 1, (int32_t)0);
+  col(out->ports, in.o_ports, 1, (int32_t)0);
+  if (out->scalars)
+    for (unsigned s = 0; s < ns; ++s) col(out->scalars + (size_t)s * n, in.o_scal[s], 1, 0.0);
+  if (copied) sync(e);
+}

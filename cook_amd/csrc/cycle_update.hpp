@@ -269,11 +269,15 @@ void offers_block_commit(cook_engine* e, UpdateBufs& ub, const cook_offers* o, O
   in.o_run_count = (const int32_t*)at(off[k++]);
   in.host_dup = 0;
   e->cf_max_host = 0xFFFFFFFFu;
+  e->o_hosts.clear();
+  e->o_run_cols_made = false;
+  e->o_hosts_known = true;
   if (M) {  // two offers on one host?
     std::vector<uint32_t> hs(o->host, o->host + M);
     std::sort(hs.begin(), hs.end());
     in.host_dup = std::adjacent_find(hs.begin(), hs.end()) != hs.end() ? 1u : 0u;
     e->cf_max_host = hs.back();  // (the class-ordered walk's and the release's host tables are sized by it)
+    e->o_hosts = std::move(hs);  // (the mirror a host churn is checked against)
   }
 }
 

@@ -62,6 +62,7 @@ struct UsageBufs;      // usage_host.hpp
 struct QueueBufs;      // queue_host.hpp
 struct CarryBufs;      // carry_host.hpp
 struct ReleaseBufs;    // release_host.hpp
+struct ChurnBufs;      // churn_host.hpp
 
 }  // namespace
 
@@ -203,6 +204,12 @@ struct cook_engine {
   std::unique_ptr<QueueBufs> qb;               // (allocated on first use)
   std::unique_ptr<CarryBufs> cyb;              // the carry of a queue cycle (allocated on first use)
   std::unique_ptr<ReleaseBufs> rlb;            // the release of a queue cycle (allocated on first use)
+  std::unique_ptr<ChurnBufs> chb;              // the host churn of a queue cycle (allocated on first use)
+  // the host's mirror of the staged offers' host ids, ascending (match_stage_offers, cook_cycle_update's offers; a host churn edits it per
+  // list entry): what a churn is checked against and sized by before its first launch.  Not known: offers built on the device
+  std::vector<uint32_t> o_hosts;
+  bool o_hosts_known = false;
+  bool o_run_cols_made = false;  // a carry or a release into this offer table has been asked for: its run_* / num_tasks / ports count as present (churn_host.hpp)
 
   // ---- rebalancer state (allocated on first use) ----
   std::unique_ptr<RebalBufs> rb;
@@ -303,6 +310,7 @@ static std::atomic<int> g_engines_on_device[64];
 #include "autoscale_host.hpp"
 #include "carry_host.hpp"      // a queue cycle's carry: needs the staged user state (considerable_host.hpp)
 #include "release_host.hpp"    // a queue cycle's release: the carry's segments and column sets
+#include "churn_host.hpp"      // a queue cycle's host churn: the release's host-indexed table, the carry's segments
 #include "queue_host.hpp"
 #include "sweep_host.hpp"
 #include "unscheduled_host.hpp"
@@ -581,13 +589,20 @@ int cook_cycle_run_queue_carry(cook_engine* e, const cook_queue_step* step, cons
 }
 int cook_cycle_run_queue_release(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
                                  uint32_t num_considerable) {
-  return cycle_run_one(e, [&] { return cycle_queue_part(e, QueueArgs{step, carry, finished}, num_considerable); }, /*defer=*/false);
+  return cook_cycle_run_queue_hosts(e, step, carry, finished, nullptr, num_considerable);
+}
+// (with the host churn, churn_host.hpp: hosts that leave or join, applied to the staged offers behind the release)
+int cook_cycle_run_queue_hosts(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
+                               const cook_host_churn* hosts, uint32_t num_considerable) {
+  return cycle_run_one(e, [&] { return cycle_queue_part(e, QueueArgs{step, carry, finished, hosts}, num_considerable); }, /*defer=*/false);
 }
 // ... for every pool of a GPU: one flow per pool in a pool batch, as cook_cycle_run_rank_multi (steps, carries, finished: null = none)
 static int queue_run_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
-                           const cook_finished* const* finished, const uint32_t* num_considerable) {
+                           const cook_finished* const* finished, const cook_host_churn* const* hosts, const uint32_t* num_considerable) {
   if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
-  auto args = [&](uint32_t i) { return QueueArgs{steps ? steps[i] : nullptr, carries ? carries[i] : nullptr, finished ? finished[i] : nullptr}; };
+  auto args = [&](uint32_t i) {
+    return QueueArgs{steps ? steps[i] : nullptr, carries ? carries[i] : nullptr, finished ? finished[i] : nullptr, hosts ? hosts[i] : nullptr};
+  };
   return run_pools_batched(
       engines, n,
       [&](uint32_t i) { return cycle_run_one(engines[i], [&] { return cycle_queue_part(engines[i], args(i), num_considerable[i]); }, /*defer=*/true); },
@@ -595,15 +610,28 @@ static int queue_run_multi(cook_engine** engines, uint32_t n, const cook_queue_s
       /*rank_part=*/true);
 }
 int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const uint32_t* num_considerable) {
-  return queue_run_multi(engines, n, steps, nullptr, nullptr, num_considerable);
+  return queue_run_multi(engines, n, steps, nullptr, nullptr, nullptr, num_considerable);
 }
 int cook_cycle_run_queue_carry_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
                                      const uint32_t* num_considerable) {
-  return queue_run_multi(engines, n, steps, carries, nullptr, num_considerable);
+  return queue_run_multi(engines, n, steps, carries, nullptr, nullptr, num_considerable);
 }
 int cook_cycle_run_queue_release_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
                                        const cook_finished* const* finished, const uint32_t* num_considerable) {
-  return queue_run_multi(engines, n, steps, carries, finished, num_considerable);
+  return queue_run_multi(engines, n, steps, carries, finished, nullptr, num_considerable);
+}
+int cook_cycle_run_queue_hosts_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
+                                     const cook_finished* const* finished, const cook_host_churn* const* hosts, const uint32_t* num_considerable) {
+  return queue_run_multi(engines, n, steps, carries, finished, hosts, num_considerable);
+}
+int cook_cycle_churn_info(cook_engine* e, cook_churn_info* out) {
+  return guarded(e, [&] {
+    if (!out) e->fail(COOK_E_INVALID, "cook_cycle_churn_info: null out");
+    *out = e->chb ? e->chb->info : cook_churn_info{0u, 0u, 0u, e->M};
+  });
+}
+int cook_cycle_fetch_offers(cook_engine* e, cook_offer_rows* out) {
+  return guarded(e, [&] { churn_fetch_offers(e, out); });
 }
 int cook_cycle_release_info(cook_engine* e, cook_release_info* out) {
   return guarded(e, [&] {

@@ -61,11 +61,15 @@ void match_stage_offers(cook_engine* e, const cook_offers* o, bool offers_dev) {
   // two offers on one host?  (offers built on the device are one per node: never)
   in.host_dup = 0;
   e->cf_max_host = 0xFFFFFFFFu;
+  e->o_hosts.clear();
+  e->o_run_cols_made = false;
+  e->o_hosts_known = !offers_dev;
   if (!offers_dev && M) {
     std::vector<uint32_t> hs(o->host, o->host + M);
     std::sort(hs.begin(), hs.end());
     in.host_dup = std::adjacent_find(hs.begin(), hs.end()) != hs.end() ? 1u : 0u;
     e->cf_max_host = hs.back();
+    e->o_hosts = std::move(hs);  // (the mirror a host churn is checked against)
   }
 }
 void match_stage_offers(cook_engine* e, const cook_offers* o) {

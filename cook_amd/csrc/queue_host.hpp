@@ -5,7 +5,7 @@
 // jobs removed and of cotasks folded in — in ONE synchronisation; the new queue length is the only value the host needs before it
 // sizes the considerable filters' launches.  A carry (carry_host.hpp) is enqueued in the same place, over the same old rows.
 // A release (release_host.hpp) is enqueued behind the carry and the fold, also when there is nothing to advance over; its counters ride
-// in the same synchronisation.
+// in the same synchronisation.  A host churn (churn_host.hpp) is enqueued behind the release; its counter rides there too.
 #pragma once
 #include "queue_kernels.hpp"
 
@@ -35,6 +35,7 @@ void queue_check_step(cook_engine* e, const QueueArgs& q) {
                           "cycle) with no cook_cycle_stage / cook_cycle_update / cook_rank* / cook_considerable / cook_match_stage since");
   carry_check(e, q);
   release_check(e, q);
+  churn_check(e, q);
   if (!s) return;
   if (s->remove_mode > 1u) e->fail(COOK_E_INVALID, "cook_queue_step.remove_mode: 0 = the kept matches, 1 = every considered job");
   if (s->offer_skipped && s->n_offer_skipped != e->M)
@@ -73,9 +74,9 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   const unsigned n = e->n_ranked, k = e->cycle_considered, G = e->G, M_old = e->M;
   const bool fold = G && k && in.j_group && !(s && s->groups);
   unsigned* cnt = b.counters.ensure(REL_CNT_WORDS);
-  const bool advance = k && n, release = release_active(f);
+  const bool advance = k && n, release = release_active(f), churn = churn_active(q.hosts);
   bool carried = false;
-  if (advance || release) memset_async(e, cnt, 0, REL_CNT_WORDS * 4);
+  if (advance || release || churn) memset_async(e, cnt, 0, REL_CNT_WORDS * 4);
   if (advance) {
     int* removed = b.removed.ensure(n);
     memset_async(e, removed, 0, (size_t)n * 4);
@@ -115,7 +116,10 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   }
   // ---- the release: behind the carry and the fold, whether or not the last cycle considered anything ------------------------------------
   if (f || e->rlb) release_enqueue(e, f, cnt, carried, (advance && fold) ? k : 0u);
-  if (release) pinned_copy(e, e->h_scratch + REL_H_CNT, cnt, REL_CNT_WORDS * 4, hipMemcpyDeviceToHost);
+  if (carry_release_offers(q)) e->o_run_cols_made = true;
+  // ---- the host churn: behind the release (all of the above index the OLD rows), in front of the considerable filters ------------------
+  if (q.hosts || e->chb) churn_enqueue(e, q.hosts, cnt);
+  if (release || churn) pinned_copy(e, e->h_scratch + REL_H_CNT, cnt, REL_CNT_WORDS * 4, hipMemcpyDeviceToHost);
   // ---- the step's groups and offers (behind the kernels above on the stream: the fold read the OLD offers) ------------------------------
   if (s && s->groups && G) {
     const cook_groups* g = s->groups;
@@ -130,8 +134,9 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
     e->cf_group_run_total = nr;
   }
   if (s && s->offers) match_stage_offers(e, s->offers, false);
+  if (e->chb) e->chb->info.n_offers = e->M;  // (the rows behind the advance, whoever set them)
   carry_tokens(e, c);
-  if (advance || release || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
+  if (advance || release || churn || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
   if (c) carry_finish(e);
   if (advance) {
     unsigned h[2] = {0, 0};
@@ -139,10 +144,11 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
     e->n_ranked = n - h[0];
     if (fold) e->cf_group_run_total += h[1];
   }
-  if (release) {
+  if (release || churn) {
     unsigned h[REL_CNT_WORDS];
     std::memcpy(h, e->h_scratch + REL_H_CNT, sizeof(h));
     release_finish(e, h);
+    churn_finish(e, h);
   }
   e->q_advance_us = (uint32_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count();
 }

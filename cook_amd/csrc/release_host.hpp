@@ -14,6 +14,7 @@ struct ReleaseBufs {
   DArr<double> cpus, mem, gpus, disk_req, scal[3];
   DArr<int32_t> ports;
   DArr<uint32_t> h2row;  // host id -> row of the staged offers
+  unsigned h2row_hosts = 0;  // entries of h2row as THIS advance's release built it (0: it did not; a churn behind it builds its own)
   DArr<uint64_t> okey, ukey, gkey;
   SegSort o, u, g;
   DArr<double> pool;  // {count, cpus, mem, gpus} of all entries
@@ -78,6 +79,7 @@ void release_enqueue(cook_engine* e, const cook_finished* f, unsigned* cnt, bool
   b.info = cook_release_info{};
   b.pending = b.pool_pending = false;
   b.n_row_entries = b.n_group_entries = 0;
+  b.h2row_hosts = 0;
   if (!release_active(f)) return;
   MatchIn& in = e->min;
   const unsigned n = f->n, M = e->M, G = e->G;
@@ -119,6 +121,7 @@ void release_enqueue(cook_engine* e, const cook_finished* f, unsigned* cnt, bool
     memset_async(e, t, 0xFF, (size_t)n_hosts * 4);
     KM<release_host_rows, 256>(e, "release_host_rows", div_up(M, 256), in.o_host, M, n_hosts, t);
     h2row = t;
+    b.h2row_hosts = n_hosts;
   }
   uint64_t* okey = offers ? b.okey.ensure(n) : nullptr;
   uint64_t* ukey = usage ? b.ukey.ensure(n) : nullptr;

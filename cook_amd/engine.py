@@ -324,6 +324,41 @@ class Engine:
                                                          C.byref(fs) if fs is not None else None, int(num_considerable)))
         del keep, fkeep
 
+    def cycle_run_queue_hosts(self, num_considerable: int, carry: Optional[A.QueueCarry] = None, finished: Optional[A.Finished] = None,
+                              hosts: Optional[A.HostChurn] = None, **step):
+        """cycle_run_queue_release with the host churn (cook_cycle_run_queue_hosts): behind the carry, the groups' fold and the release
+        the rows of the hosts in hosts.leave go out of the staged offers and the rows of hosts.join come in, each in front of its
+        anchor, on the device; the surviving rows keep their order.  hosts None: exactly cycle_run_queue_release."""
+        st, keep = self._queue_step(**step)
+        cs = carry.as_struct() if carry is not None else None
+        fs, fkeep = finished.as_struct() if finished is not None else (None, None)
+        hs, hkeep = hosts.as_struct() if hosts is not None else (None, None)
+        self._chk(self._lib.cook_cycle_run_queue_hosts(self._h, C.byref(st), C.byref(cs) if cs is not None else None,
+                                                       C.byref(fs) if fs is not None else None, C.byref(hs) if hs is not None else None,
+                                                       int(num_considerable)))
+        del keep, fkeep, hkeep
+
+    def churn_info(self) -> dict:
+        """The counts of the last queue cycle's host churn (cook_cycle_churn_info); all 0 (n_offers: the staged rows) when it had none."""
+        out = A.CookChurnInfo()
+        self._chk(self._lib.cook_cycle_churn_info(self._h, C.byref(out)))
+        return {k: int(getattr(out, k)) for k, _ in A.CookChurnInfo._fields_}
+
+    def fetch_offers(self, rows: Optional[A.OfferRows] = None) -> A.OfferRows:
+        """The staged offer table as the next match will read it, behind any carry, release and churn (cook_cycle_fetch_offers).
+        rows: the caller's columns (their cap too small: CookError); None: sized by the staged table.  -> the OfferRows; .offers() is
+        the table as an Offers."""
+        probe = A.CookOfferRows()  # cap 0, every column skipped: the call reports n and the widths (and refuses cap < n: no synchronisation)
+        rc = self._lib.cook_cycle_fetch_offers(self._h, C.byref(probe))
+        if rc != 0 and probe.n == 0:
+            self._chk(rc)
+        if rows is None:
+            rows = A.OfferRows(probe.n, n_attr_keys=probe.n_attr_keys)
+        elif rows.n_attr_keys < probe.n_attr_keys:
+            raise ValueError(f"fetch_offers: the rows have room for {rows.n_attr_keys} attribute keys, the staged offers have {probe.n_attr_keys}")
+        self._chk(self._lib.cook_cycle_fetch_offers(self._h, C.byref(rows.struct)))
+        return rows
+
     def release_info(self) -> dict:
         """The counts of the last queue cycle's release (cook_cycle_release_info); all 0 when it had none."""
         out = A.CookReleaseInfo()
@@ -890,6 +925,36 @@ def cycle_run_queue_release_multi(engines: Sequence[Engine], num_considerable, s
     cptrs = (C.c_void_p * n)(*[C.addressof(c) if c is not None else None for c in cs])
     fptrs = (C.c_void_p * n)(*[C.addressof(f) if f is not None else None for f, _ in fs])
     _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_release_multi(arr, n, ptrs, cptrs, fptrs, ks))
+
+
+def cycle_run_queue_hosts_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None,
+                                carries: Optional[Sequence[Optional[A.QueueCarry]]] = None,
+                                finished: Optional[Sequence[Optional[A.Finished]]] = None,
+                                hosts: Optional[Sequence[Optional[A.HostChurn]]] = None):
+    """cycle_run_queue_release_multi with one host churn per engine (cook_cycle_run_queue_hosts_multi; None: no churn for that pool);
+    cycle_match_multi places them.  A pool whose step, carry, list or churn is refused stays as it was and raises after the others
+    have gone on."""
+    if not engines:
+        return
+    n = len(engines)
+    arr = (C.c_void_p * n)(*[e._h for e in engines])
+    ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
+    assert len(ks) == n
+    ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
+    steps = list(steps) if steps is not None else [None] * n
+    carries = list(carries) if carries is not None else [None] * n
+    finished = list(finished) if finished is not None else [None] * n
+    hosts = list(hosts) if hosts is not None else [None] * n
+    assert len(steps) == n and len(carries) == n and len(finished) == n and len(hosts) == n
+    built = [e._queue_step(**(s or {})) for e, s in zip(engines, steps)]
+    cs = [c.as_struct() if c is not None else None for c in carries]
+    fs = [f.as_struct() if f is not None else (None, None) for f in finished]
+    hs = [h.as_struct() if h is not None else (None, None) for h in hosts]
+    ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
+    cptrs = (C.c_void_p * n)(*[C.addressof(c) if c is not None else None for c in cs])
+    fptrs = (C.c_void_p * n)(*[C.addressof(f) if f is not None else None for f, _ in fs])
+    hptrs = (C.c_void_p * n)(*[C.addressof(h) if h is not None else None for h, _ in hs])
+    _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_hosts_multi(arr, n, ptrs, cptrs, fptrs, hptrs, ks))
 
 
 def cycle_match_multi(engines: Sequence[Engine]):

@@ -571,9 +571,8 @@ int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_que
  *     tokens_left is honoured whatever the two flags say.  Quotas, enforce_rate_limit and the eligible mask stay as staged.
  * Refused before anything changes: offers = 1 together with step->offers, a flag above 1, tokens_left while the staged state has no
  * limiter (COOK_E_INVALID); usage = 1 or tokens_left without a staged user state (COOK_E_STATE).
- * Not carried, the host's to tell: finished tasks (cook_cycle_run_queue_release below takes their list) and new hosts (step->offers /
- * cook_cycle_update), the time-based token refill
- * (tokens_left).  carry NULL, or both flags 0 and no tokens: exactly cook_cycle_run_queue / _multi. */
+ * Not carried: finished tasks (cook_cycle_run_queue_release below takes their list), hosts that join or leave
+ * (cook_cycle_run_queue_hosts below takes their lists); the host's to tell: the time-based token refill (tokens_left).  carry NULL, or both flags 0 and no tokens: exactly cook_cycle_run_queue / _multi. */
 typedef struct cook_queue_carry {
   uint32_t offers;            /* 1: carry the kept placements into the staged offers (then step->offers must be NULL) */
   uint32_t usage;             /* 1: carry them into the staged user state (needs cook_cycle_set_considerable staged)   */
@@ -617,8 +616,8 @@ int cook_cycle_run_queue_carry_multi(cook_engine** engines, uint32_t n, const co
  * cook_cycle_set_considerable.  A refused step leaves the queue, the offers, the usage and the groups as they were.
  * finished NULL, n = 0 or all three flags 0: exactly cook_cycle_run_queue_carry / _carry_multi.  The arrays are read until the call
  * returns.  cook_user_stats / cook_unscheduled / cook_usage_breakdown keep describing the last RANK.  Taking finished rows out of the
- * rank's task table stays with cook_cycle_update and the next rank; new hosts stay with step->offers.  (Additive: no existing
- * layout changes.) */
+ * rank's task table stays with cook_cycle_update and the next rank; hosts that join or leave go through cook_cycle_run_queue_hosts
+ * below.  (Additive: no existing layout changes.) */
 typedef struct cook_finished {      /* tasks that ended since the last cycle, in the host's order (the order rule above) */
   uint32_t n;
   const uint32_t* host;             /* [n] host id, as cook_offers.host / cook_groups.run_host */
@@ -644,6 +643,91 @@ int cook_cycle_run_queue_release_multi(cook_engine** engines, uint32_t n, const 
                                        const uint32_t* num_considerable);
 /* the counts of the last queue cycle's release; all 0 when it had none */
 int cook_cycle_release_info(cook_engine* e, cook_release_info* out);
+
+/* ---- THE HOST CHURN: a queue cycle that takes the rows of hosts that LEAVE out of the staged offers and puts rows that JOIN in -------
+ * In the reference nobody does this arithmetic: generate-offers (kubernetes/compute_cluster.clj:68-190) lists the nodes that exist and
+ * are schedulable now, Mesos rescinds offers and sends new ones, Fenzo expires a lost host's lease and meets a new lease on the next
+ * scheduleOnce (scheduler.clj:665-678).  A queue cycle takes a short list of hosts that leave and of rows that join and edits the
+ * staged offer table on the device inside the advance: a stable compaction plus an ordered insertion over every offer column, with no
+ * synchronisation of its own (its counters ride in the advance's one read-back) and no upload of the table.
+ * Position in the advance: behind the carry, the groups' fold and the release, which all still work on the OLD rows (the last cycle's
+ * job_to_offer and offer_skipped index them, and a task may finish on a host that leaves in the same call); in front of the step's
+ * considerable filters; it also runs when the last cycle considered nothing or the queue is empty.
+ * Order rule (oracle-defined and a contract: the lowest offer index wins ties in the placement).  OLD = the table as it stands behind the
+ * release.  The rows whose host is in leave_host go; the surviving rows keep their relative order.  Join row i is placed directly in
+ * front of the position of the OLD row whose host is join_before[i], whether or not that row leaves; rows with the same anchor keep
+ * list order; COOK_NONE_U32 = behind the last OLD row (join_before NULL: all of them).  A host that both leaves and joins with itself
+ * as the anchor is therefore replaced in place.  The new row indices are what job_to_offer, cook_match_explain, cook_match_metrics,
+ * cook_cycle_autoscale and the next step's offer_skipped / n_offer_skipped refer to from this cycle on; a host can reproduce them from
+ * this rule without a fetch.
+ * Columns: every column of the staged table moves with its row (the resources, run_*, num_tasks, max_tasks, ports, the named scalars,
+ * k8s, the [n][slots] gpu / disk maps, the [n][n_attr_keys] attributes, host, location, host_start_s).  A joining row's values are the
+ * list's, unchanged (the host states run_* and num_tasks of a host that returns).  A column the staged table has and join lacks gets,
+ * for the joining rows, the value a NULL column means for every row: 0, and -1 (absent) for max_tasks and host_start_s.  The five
+ * columns a carry or a release brings into existence (run_cpus, run_mem, run_count, num_tasks, ports) count as present from the first
+ * step on these offers that asked for offers = 1 in either, this very step included.  The churned
+ * table IS the staged table from then on, through later cycles and ranks until replaced, exactly as the carried one is.  The caller's
+ * arrays, the engine's originally staged arrays and the rows of cook_offers_run are never written, and the columns the last match read
+ * stay as they were.
+ * Refused before anything changes.  COOK_E_INVALID: join carries a column the staged table lacks, or another n_attr_keys / gpu_slots /
+ * disk_slots / n_scalars (0 slots means 1); join lacks cpus, mem or host (or has gpu_model without gpu_count, disk_type without
+ * disk_space); n_leave without leave_host; a host twice in leave_host or twice in join; a joining host that is already staged and does
+ * not leave in this call; join_before names a host that is not an OLD row; the staged offers have two rows on one host; step->offers
+ * together with a churn; a new row count that a stage would refuse.  COOK_E_STATE: the staged offers were built on the device
+ * (cook_cycle_stage_built_offers): build them again from the nodes.  A refused step leaves the queue, the offers, the usage and the
+ * groups as they were.  Not an error: a leave_host that has no row is counted in leave_missing.  hosts NULL, or both lists empty:
+ * exactly cook_cycle_run_queue_release / _release_multi.  The arrays are read until the call returns.  The groups' running cotasks
+ * are keyed by host id, not by row: a cotask on a host that leaves and returns still counts.  (Additive: no existing layout changes.) */
+typedef struct cook_host_churn {
+  uint32_t n_leave;
+  const uint32_t* leave_host;   /* [n_leave] host ids whose rows leave the staged offers */
+  const cook_offers* join;      /* rows that join (join->n of them), layout of cook_offers; NULL = none */
+  const uint32_t* join_before;  /* [join->n] host id of the OLD row in front of which the row goes; COOK_NONE_U32 = behind the last row; NULL = all at the end */
+} cook_host_churn;
+typedef struct cook_churn_info {
+  uint32_t left, leave_missing; /* leave_host entries that had / had no row */
+  uint32_t joined;              /* rows that joined */
+  uint32_t n_offers;            /* rows of the staged offers behind the advance */
+} cook_churn_info;
+int cook_cycle_run_queue_hosts(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
+                               const cook_host_churn* hosts, uint32_t num_considerable);
+/* as cook_cycle_run_queue_release_multi (then cook_cycle_match_multi); hosts NULL or an entry NULL: no churn for that pool */
+int cook_cycle_run_queue_hosts_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps,
+                                     const cook_queue_carry* const* carries, const cook_finished* const* finished,
+                                     const cook_host_churn* const* hosts, const uint32_t* num_considerable);
+/* the counts of the last queue cycle's churn; all 0 (n_offers = the staged row count) when it had none */
+int cook_cycle_churn_info(cook_engine* e, cook_churn_info* out);
+
+/* The staged offer table as the next match will read it, behind any carry, release and churn: one caller-allocated array per column of
+ * cook_offers, each with room for cap rows of its width; NULL = skip that column.  The call sets n and the widths: gpu_model / gpu_count
+ * are [n][gpu_slots], disk_type / disk_space [n][disk_slots], attr [n][n_attr_keys] (row-major, as staged; a width of 0: nothing is
+ * written), scalars n_scalars columns of n doubles one behind the other (as cook_offers.scalars).  cap < n: COOK_E_INVALID with n and
+ * the widths set and no column written.  A column the staged table does not have is filled with what NULL means for it (0; -1 for
+ * max_tasks and host_start_s).  Changes no state, invalidates nothing, costs one synchronisation; COOK_E_STATE before offers were staged. */
+typedef struct cook_offer_rows {
+  uint32_t cap;                 /* in: rows every non-NULL array has room for */
+  uint32_t n;                   /* out: rows of the staged offers */
+  uint32_t gpu_slots, disk_slots, n_attr_keys, n_scalars; /* out: the staged widths */
+  double* cpus;
+  double* mem;
+  uint32_t* host;
+  uint8_t* k8s;
+  uint32_t* gpu_model;
+  double* gpu_count;
+  uint32_t* disk_type;
+  double* disk_space;
+  uint32_t* attr;
+  int32_t* max_tasks;
+  int32_t* num_tasks;
+  uint32_t* location;
+  int64_t* host_start_s;
+  double* run_cpus;
+  double* run_mem;
+  int32_t* run_count;
+  int32_t* ports;
+  double* scalars;
+} cook_offer_rows;
+int cook_cycle_fetch_offers(cook_engine* e, cook_offer_rows* out);
 
 /* ---- REBALANCE: replaces init-state + the rebalance loop's decisions ---------------------------------------
  * (rebalancer.clj:222-266, 320-407, 270-309, 434-467; dru.clj:128-144).

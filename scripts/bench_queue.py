@@ -21,7 +21,12 @@ cycle with carry + release and no upload; leg two's host supplies the same offer
 cook_cycle_set_considerable and step->groups (its arithmetic — tests/carry_oracle.py and tests/release_oracle.py — is NOT timed).  Both
 legs must place every job identically in every cycle, or the run fails.  The row also has the device time of the release's kernels
 beside the carry's for the same cycles, from a profiled episode of its own.
-    python scripts/bench_queue.py [--steps 50] [--warmup 5] [--k-all] [--carry | --carry-only] [--release | --release-only] [--out results/queue.json]"""
+The host churn (cook_cycle_run_queue_hosts*), --churn: the release's two legs with, per queue cycle, CHURN_FRAC of the
+staged hosts leaving and as many rows joining (hosts that return, new hosts; anchored at random old rows or at the end).  Leg one is a
+queue cycle with carry + release + churn and no table upload; leg two's host supplies the same table through step->offers (its
+arithmetic — the oracles of tests/ — is NOT timed).  Both legs must place every job identically in every cycle, or the run fails.
+    python scripts/bench_queue.py [--steps 50] [--warmup 5] [--k-all] [--carry | --carry-only] [--release | --release-only] [--churn | --churn-only]
+                                  [--out results/queue.json]"""
 import argparse
 import copy
 import json
@@ -37,10 +42,11 @@ sys.path.insert(0, ROOT)
 
 from cook_amd import _abi as A  # noqa: E402
 from cook_amd import workload  # noqa: E402
-from cook_amd.engine import (Engine, cycle_match_multi, cycle_run_queue_carry_multi, cycle_run_queue_multi, cycle_run_queue_release_multi,  # noqa: E402
-                             cycle_run_rank_multi)
+from cook_amd.engine import (Engine, cycle_match_multi, cycle_run_queue_carry_multi, cycle_run_queue_hosts_multi, cycle_run_queue_multi,  # noqa: E402
+                             cycle_run_queue_release_multi, cycle_run_rank_multi)
 from tests import autoscale_cases as AS  # noqa: E402
 from tests import carry_oracle as CO  # noqa: E402
+from tests import churn_oracle as HO  # noqa: E402
 from tests import queue_cases as S  # noqa: E402
 from tests import release_oracle as RO  # noqa: E402
 
@@ -50,6 +56,8 @@ CARRY = ("carry_keys", "carry_seg_bounds", "carry_fold_offers", "carry_fold_user
 RELEASE = ("release_host_rows", "release_keys", "release_fold_offers", "release_fold_users", "release_fold_pool", "release_group_mark",
            "release_group_scan", "release_group_offsets", "release_group_compact")
 RELEASE_FRAC = 0.3  # of the episode's placements that have not ended yet, per queue cycle
+CHURN = ("churn_mark", "churn_scan", "churn_source", "churn_gather")
+CHURN_FRAC = 0.01  # of the staged hosts leave per queue cycle, and as many rows join
 ADVANCE = ("q_mark_removed", "q_queue_scan", "q_compact_ranked", "q_group_scan", "q_fold_offsets", "q_fold_copy_old", "q_fold_append")
 
 
@@ -352,12 +360,157 @@ def run_release(name, pools, k, steps, warmup):
             "advance_syncs": 1, "identical_placements": True, "released_per_cycle": released, "groups": grouped}
 
 
+def run_churn(name, pools, k, steps, warmup):
+    """the two legs of the host churn (carry + release + churn against a host that supplies the table, the user state and the groups);
+    -> one result row"""
+    params = A.default_params()
+    n = len(pools)
+    states = [AS.random_state(pl, 40 + i, tokens=False, pool_quota=False) for i, pl in enumerate(pools)]
+    ks = [k if k else pl.pending_jobs.n for pl in pools]
+    cyc = CARRY_CYCLES if k else 1
+    episodes = max(1, -(-(warmup + steps) // cyc))
+    both = A.QueueCarry(offers=True, usage=True)
+    grouped = [pl.groups is not None and pl.pending_jobs.group is not None for pl in pools]
+    jq_of = [np.cumsum(pl.tasks.pending) - 1 for pl in pools]
+    lists = [[None] * (cyc + 1) for _ in pools]   # what queue cycle c of pool i releases (drawn in leg one's first episode)
+    history = [[] for _ in pools]
+    rng = np.random.default_rng(99)
+    gone = [set() for _ in pools]
+    # the churns: drawn up front over the hosts alone (every episode starts from the pool's own offers again)
+    churns = [[None] * (cyc + 1) for _ in pools]
+    for i, pl in enumerate(pools):
+        assert len(set(pl.offers.host.tolist())) == pl.offers.n, "one offer per host"
+        draw = HO.churner(500 + i, CHURN_FRAC, fresh_from=int(pl.offers.host.max()) + 1)  # (new hosts get the next ids: host ids are dense hostname ranks)
+        hosts = pl.offers.host
+        for c in range(1, cyc + 1):
+            h = churns[i][c] = draw([SimpleNamespace(offers=pl.offers)], SimpleNamespace(n=len(hosts), host=hosts))
+            src = HO.new_order(hosts, h)[0]
+            hosts = np.array([hosts[x] if kind == "old" else h.join.host[x] for kind, x in src], np.uint32)
+
+    def rank(engines):
+        if n == 1:
+            engines[0].cycle_run(ks[0])
+        else:
+            cycle_run_rank_multi(engines, ks)
+            cycle_match_multi(engines)
+
+    def note(engines, c, draw):
+        out = [S.fetch(e, False) for e in engines]
+        if draw:
+            for i, (g, pl, e) in enumerate(zip(out, pools, engines)):
+                g.churn = e.churn_info()
+                history[i].append(SimpleNamespace(j2o=g.j2o, jobs=pl.pending_jobs.take(jq_of[i][g.Q[g.pos]]), offers=e.fetch_offers().offers()))
+                if c < cyc:
+                    picks = [q for q in RO.placed_rows(history[i]) if q not in gone[i] and rng.random() < RELEASE_FRAC]
+                    gone[i].update(picks)
+                    lists[i][c + 1] = RO.finished_of(history[i], picks, offers=1, usage=1, groups=int(grouped[i]))
+        return out
+
+    def episode(engines, step, record, draw=False):
+        for e, pl, (st, el) in zip(engines, pools, states):
+            e.cycle_update(offers=pl.offers)
+            e.cycle_set_considerable(st, el)
+        rank(engines)
+        if record is not None:
+            record.append(note(engines, 0, draw))
+        ts = []
+        for c in range(1, cyc + 1):
+            t0 = time.perf_counter()
+            step(engines, c)
+            ts.append(time.perf_counter() - t0)
+            if record is not None:
+                record.append(note(engines, c, draw))
+        return ts
+
+    def leg(step, first_leg=False):
+        engines = [Engine(params) for _ in pools]
+        try:
+            for e, pl in zip(engines, pools):
+                e.cycle_stage(pl.tasks, pl.users, pl.pending_jobs, pl.offers, pl.groups)
+            first, ts = [], []
+            for ep in range(episodes):
+                ts += episode(engines, step, first if ep == 0 else None, draw=first_leg and ep == 0)
+            prof = None
+            if first_leg:  # launches and device time of the advance's parts, in a profiled episode of its own
+                for e in engines:
+                    e.set_profiling(True)
+                episode(engines, step, None)
+                kt = [e.kernel_timings() for e in engines]
+                part = lambda names, x: sum(v[x] for t in kt for nm, v in t.items() if nm in names)
+                prof = dict(launches=round(part(ADVANCE + CARRY + RELEASE + CHURN, 1) / cyc / n, 1), churn_launches=round(part(CHURN, 1) / cyc / n, 1),
+                            carry_us=round(part(CARRY, 0) * 1e3 / cyc, 1), release_us=round(part(RELEASE, 0) * 1e3 / cyc, 1),
+                            churn_us=round(part(CHURN, 0) * 1e3 / cyc, 1))
+            return first, ts[warmup:], prof
+        finally:
+            for e in engines:
+                e.close()
+
+    def step_churn(engines, c):
+        if n == 1:
+            engines[0].cycle_run_queue_hosts(ks[0], both, lists[0][c], churns[0][c])
+        else:
+            cycle_run_queue_hosts_multi(engines, ks, None, [both] * n, [lists[i][c] for i in range(n)], [churns[i][c] for i in range(n)])
+            cycle_match_multi(engines)
+
+    got1, t1, prof = leg(step_churn, first_leg=True)
+    # what the host of leg two supplies: the oracles' carry, release and churn of leg one's own placements and lists (untimed)
+    supply = [[None] * (cyc + 1) for _ in pools]
+    for i, (pl, (st, el)) in enumerate(zip(pools, states)):
+        offers, state, table = pl.offers, st, S.group_table(pl.groups)
+        for c in range(1, cyc + 1):
+            g, h = got1[c - 1][i], history[i][c - 1]
+            hit = g.j2o >= 0
+            if grouped[i]:
+                table = copy.deepcopy(table)
+                for x in np.flatnonzero(hit):
+                    gg = int(h.jobs.group[x])
+                    if gg != A.NONE_U32:
+                        table.run_hosts[gg].append(int(offers.host[g.j2o[x]]))
+                        table.run_attrs[gg].append(S.offer_attr(offers, int(g.j2o[x]), int(table.attr_key[gg])))
+            offers, state = CO.carry_offers(offers, h.jobs, g.j2o, hit), CO.carry_usage(state, h.jobs, hit, spend=False)
+            fin = lists[i][c]
+            if fin is not None:
+                offers, state = RO.release_offers(offers, fin)[0], RO.release_usage(state, fin)
+                if grouped[i]:
+                    table = RO.release_groups(table, fin)[0]
+            offers, info = HO.churn_offers(offers, churns[i][c])
+            assert got1[c][i].churn == info, (name, i, c, got1[c][i].churn, info)
+            supply[i][c] = (offers, state, el, S.build_groups(table) if grouped[i] else None)
+
+    def step_host(engines, c):
+        for i, e in enumerate(engines):  # the read-back a host needs before it can do the arithmetic
+            e.cycle_fetch()
+            e.cycle_fetch_considerable()
+            e.cycle_set_considerable(supply[i][c][1], supply[i][c][2])
+        if n == 1:
+            engines[0].cycle_run_queue(ks[0], offers=supply[0][c][0], groups=supply[0][c][3])
+        else:
+            cycle_run_queue_multi(engines, ks, [dict(offers=supply[i][c][0], groups=supply[i][c][3]) for i in range(n)])
+            cycle_match_multi(engines)
+
+    got2, t2, _ = leg(step_host)
+    for c, (a, b) in enumerate(zip(got1, got2)):
+        for i in range(n):
+            assert np.array_equal(a[i].Q, b[i].Q) and np.array_equal(a[i].pos, b[i].pos) and np.array_equal(a[i].j2o, b[i].j2o), \
+                f"{name}: the legs differ in cycle {c}, pool {i}"
+    churned = [[[int(len(h.leave)), int(h.join.n)] for h in row[1:]] for row in churns]
+    assert all(a > 0 and b > 0 for row in churned for a, b in row), "a timed cycle has no host that leaves or joins"
+    cm, hm = median_ms(t1), median_ms(t2)
+    return {"config": name + ", carry + release + churn", "pools": n, "K": k or "all", "timed_cycles": len(t1), "churn_cycle_ms": cm,
+            "host_supplied_cycle_ms": hm, "churn_over_host": round(cm / hm, 3), "advance_launches_per_pool_without_sort_passes": prof["launches"],
+            "of_them_churn": prof["churn_launches"], "carry_kernels_us_per_cycle": prof["carry_us"], "release_kernels_us_per_cycle": prof["release_us"],
+            "churn_kernels_us_per_cycle": prof["churn_us"], "advance_syncs": 1, "identical_placements": True, "offers_per_pool": [int(pl.offers.n) for pl in pools],
+            "leave_join_per_cycle": churned, "groups": grouped}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--carry", action="store_true", help="also the two legs of the carry")
     ap.add_argument("--carry-only", action="store_true", help="only the two legs of the carry")
     ap.add_argument("--release", action="store_true", help="also the two legs of the release")
     ap.add_argument("--release-only", action="store_true", help="only the two legs of the release (and, with --carry, of the carry)")
+    ap.add_argument("--churn", action="store_true", help="also the two legs of the host churn")
+    ap.add_argument("--churn-only", action="store_true", help="only the two legs of the host churn (and, with --carry / --release, of those)")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--k-all", action="store_true")
@@ -366,18 +519,23 @@ def main():
     spec = workload.ClusterSpec()
     c4 = [workload.make_pool(spec, p) for p in range(spec.pools)]
     rows = []
-    for k in [1000] + ([0] if args.k_all else []):
-        if not args.carry_only and not args.release_only:
-            rows.append(run("one C4 pool", c4[:1], k, args.steps, args.warmup))
-            rows.append(run("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
-        if args.carry or args.carry_only:
-            rows.append(run_carry("one C4 pool", c4[:1], k, args.steps, args.warmup))
-            rows.append(run_carry("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
-        if args.release or args.release_only:
-            rows.append(run_release("one C4 pool", c4[:1], k, args.steps, args.warmup))
-            rows.append(run_release("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
-    for r in rows:
+
+    def add(r):  # (printed as it comes: a long run that is cut short keeps what it has measured)
+        rows.append(r)
         print(json.dumps(r), flush=True)
+    for k in [1000] + ([0] if args.k_all else []):
+        if not args.carry_only and not args.release_only and not args.churn_only:
+            add(run("one C4 pool", c4[:1], k, args.steps, args.warmup))
+            add(run("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
+        if args.carry or args.carry_only:
+            add(run_carry("one C4 pool", c4[:1], k, args.steps, args.warmup))
+            add(run_carry("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
+        if args.release or args.release_only:
+            add(run_release("one C4 pool", c4[:1], k, args.steps, args.warmup))
+            add(run_release("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
+        if args.churn or args.churn_only:
+            add(run_churn("one C4 pool", c4[:1], k, args.steps, args.warmup))
+            add(run_churn("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

@@ -3,7 +3,9 @@
 cycle update and of the rebalancer, both match_algo values, eval split caps, ports / named scalars, k8s gpu maps with several entries;
 `--carry N`: queue cycles with and without the carry (cook_cycle_run_queue / cook_cycle_run_queue_carry) against tests/carry_oracle.py,
 from random draws of their own (the other legs' draws do not depend on N); `--release N`: the same kind of queue cycles with random lists
-of finished tasks beside the carry's draws (cook_cycle_run_queue_release) against tests/release_oracle.py, again from draws of their own.
+of finished tasks beside the carry's draws (cook_cycle_run_queue_release) against tests/release_oracle.py, again from draws of their own;
+`--churn N`: the same again with random lists of hosts that leave and rows that join beside the carry's and the release's draws
+(cook_cycle_run_queue_hosts) against tests/churn_oracle.py, every column of the staged table compared through cook_cycle_fetch_offers.
 `--emu` runs the SIMT-emulator build on the CPU, otherwise libcookmatch.so on the GPU.  Prints one line; exit 1 on the first
 difference (with the configuration that produced it)."""
 import argparse
@@ -26,6 +28,8 @@ def main():
     ap.add_argument("--carry", type=int, default=0, help="queue-cycle configurations: random pools, user states, skipped offers, remove modes, carry flags, token refills")
     ap.add_argument("--release", type=int, default=0, help="queue-cycle configurations as --carry, with random lists of finished tasks: placements of the cycles so far "
                                                             "(some twice), hosts without a row, random release flags")
+    ap.add_argument("--churn", type=int, default=0, help="queue-cycle configurations as --release, with random host churns: hosts that leave (some without a row), "
+                                                          "hosts that return or are new, anchored at random old rows or at the end")
     ap.add_argument("--emu", action="store_true")
     ap.add_argument("--scale", type=float, default=1.0, help="size factor of the configurations")
     ap.add_argument("--algo", type=int, default=-1, help="force cook_params.match_algo (default: drawn per configuration)")
@@ -170,11 +174,8 @@ def main():
         except AssertionError as ex:
             print("FAIL carry", it, kw, p.match_algo, p.good_enough_fitness, k, str(ex)[:300])
             sys.exit(1)
-    rrng = np.random.default_rng([args.seed, 0x4E1EA5E])  # its own stream again
-    for it in range(args.release):
-        from tests import release_cases as X
+    def draw_ends(rrng, pool, cycles, with_state):
         from tests import release_oracle as R
-        kw, p, pool, cycles, k, with_state = draw_queue_case(rrng)
         grouped = pool.groups is not None and pool.pending_jobs.group is not None
 
         def ends(cy):
@@ -199,11 +200,36 @@ def main():
             return draw
         for cy in cycles[1:]:
             cy.finished = ends(cy) if rrng.random() < 0.85 else None
+
+    rrng = np.random.default_rng([args.seed, 0x4E1EA5E])  # its own stream again
+    for it in range(args.release):
+        from tests import release_cases as X
+        from tests import release_oracle as R
+        kw, p, pool, cycles, k, with_state = draw_queue_case(rrng)
+        draw_ends(rrng, pool, cycles, with_state)
         try:
             want = R.oracle(p, pool, cycles)
             X.compare(X.run_engine(make_engine, p, pool, cycles), want, cycles)
         except AssertionError as ex:
             print("FAIL release", it, kw, p.match_algo, p.good_enough_fitness, k, str(ex)[:300])
+            sys.exit(1)
+    hrng = np.random.default_rng([args.seed, 0xC4072])  # and again
+    for it in range(args.churn):
+        from tests import churn_cases as C
+        from tests import churn_oracle as H
+        kw, p, pool, cycles, k, with_state = draw_queue_case(hrng)
+        draw_ends(hrng, pool, cycles, with_state)
+        # as many rows join as leave: the row count stays what the step's offer_skipped was drawn for.  A step that replaces the
+        # offers cannot churn them, and two staged offers on one host refuse a churn
+        draw = H.churner(int(hrng.integers(1, 1 << 30)), float(hrng.uniform(0.01, 0.5)), template="current")  # (ONE: it hands out every new host id once)
+        one_per_host = lambda history, offers: draw(history, offers) if len(set(offers.host.tolist())) == offers.n else None  # noqa: E731
+        for cy in cycles[1:]:
+            cy.hosts = one_per_host if (cy.offers is None and hrng.random() < 0.85) else None
+        try:
+            want = H.oracle(p, pool, cycles)
+            C.compare(C.run_engine(make_engine, p, pool, cycles), want, cycles)
+        except AssertionError as ex:
+            print("FAIL churn", it, kw, p.match_algo, p.good_enough_fitness, k, str(ex)[:300])
             sys.exit(1)
     guard = ""
     if args.guard:
@@ -216,7 +242,7 @@ def main():
             print(f"FAIL guard: {hits} writes outside a device buffer (COOK_GUARD lines on stderr)")
             sys.exit(1)
         guard = ", COOK_GUARD=1: no write outside a device buffer"
-    print(f"fuzz ok: {args.match} match / cycle configurations, {args.multi} multi-pool configurations, {args.rebalance} rebalancer configurations, {args.carry} queue-cycle configurations, {args.release} with releases, seed {args.seed}, "
+    print(f"fuzz ok: {args.match} match / cycle configurations, {args.multi} multi-pool configurations, {args.rebalance} rebalancer configurations, {args.carry} queue-cycle configurations, {args.release} with releases, {args.churn} with host churns, seed {args.seed}, "
           f"{'emulator' if args.emu else 'gpu'}{guard}")
 
 
