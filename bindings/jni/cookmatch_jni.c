@@ -608,6 +608,114 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleFetchOffers(JNIEnv* env, jclass
   dims[0] = (jint)r.n, dims[1] = (jint)r.gpu_slots, dims[2] = (jint)r.disk_slots, dims[3] = (jint)r.n_attr_keys, dims[4] = (jint)r.n_scalars;
   return rc;
 }
+/* cycleRunQueueHosts with the host reservations (cook_cycle_run_queue_reserve; defer != 0: cook_cycle_run_queue_reserve_multi for this one
+ * pool, the placement then runs in cycleMatchMulti).  release_matched / replace: the flags of cook_reservations; rsv_pending / rsv_host:
+ * direct buffers of n_reserve uint32 each (pending ordinal or COOK_NONE_U32, host id), or null with n_reserve = 0. */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueueReserve(JNIEnv* env, jclass c, jlong h, jint num_considerable, jint remove_mode,
+                                                                 jint n_last_offers, jobject offer_skipped, jint n_groups, jobjectArray groups,
+                                                                 jint carry_offers, jint carry_usage, jint n_users, jobject tokens_left,
+                                                                 jint n_finished, jint n_fin_scalars, jobjectArray finished, jint release_offers,
+                                                                 jint release_usage, jint release_groups, jint n_leave, jobject leave_host,
+                                                                 jint m_join, jobject join_dims, jobjectArray join, jobject join_before,
+                                                                 jint release_matched, jint replace, jint n_reserve, jobject rsv_pending,
+                                                                 jobject rsv_host, jint defer) {
+  int bad = 0;
+  const jint mj = m_join > 0 ? m_join : 0, nl = n_leave > 0 ? n_leave : 0, nr = n_reserve > 0 ? n_reserve : 0;
+  cook_offers o = offers_of(env, mj, dims_of(env, join_dims, &bad), join, &bad);
+  cook_groups g = groups_of(env, n_groups, groups, &bad);
+  cook_queue_step s;
+  cook_queue_carry cy;
+  cook_finished f;
+  cook_host_churn hc;
+  cook_reservations rv;
+  const jint nf = n_finished > 0 ? n_finished : 0, ns = n_fin_scalars > 0 ? n_fin_scalars : 0;
+  (void)c;
+  s.offer_skipped = BUFN(const uint8_t, offer_skipped, n_last_offers > 0 ? n_last_offers : 0);
+  s.remove_mode = (uint32_t)remove_mode;
+  s.n_offer_skipped = (uint32_t)(n_last_offers > 0 ? n_last_offers : 0);
+  s.offers = 0;
+  s.groups = groups ? &g : 0;
+  cy.offers = (uint32_t)carry_offers;
+  cy.usage = (uint32_t)carry_usage;
+  cy.tokens_left = BUFN(const int64_t, tokens_left, n_users > 0 ? n_users : 0);
+  f.n = (uint32_t)nf;
+  f.host = EL(const uint32_t, finished, 0, nf);
+  f.user = EL(const uint32_t, finished, 1, nf);
+  f.cpus = EL(const double, finished, 2, nf);
+  f.mem = EL(const double, finished, 3, nf);
+  f.gpus = EL(const double, finished, 4, nf);
+  f.ports = EL(const int32_t, finished, 5, nf);
+  f.scalars = EL(const double, finished, 6, (uint64_t)nf * (uint64_t)ns);
+  f.n_scalars = (uint32_t)ns;
+  f.gpu_model = EL(const uint32_t, finished, 7, nf);
+  f.disk_request = EL(const double, finished, 8, nf);
+  f.disk_type = EL(const uint32_t, finished, 9, nf);
+  f.group = EL(const uint32_t, finished, 10, nf);
+  f.offers = (uint32_t)release_offers;
+  f.usage = (uint32_t)release_usage;
+  f.groups = (uint32_t)release_groups;
+  hc.n_leave = leave_host ? (uint32_t)nl : 0u;
+  hc.leave_host = BUFN(const uint32_t, leave_host, nl);
+  hc.join = join ? &o : 0;
+  hc.join_before = BUFN(const uint32_t, join_before, mj);
+  rv.release_matched = (uint32_t)release_matched;
+  rv.replace = (uint32_t)replace;
+  rv.n = (uint32_t)nr;
+  rv.pending = BUFN(const uint32_t, rsv_pending, nr);
+  rv.host = BUFN(const uint32_t, rsv_host, nr);
+  if (bad) return COOK_E_INVALID;
+  if (defer) {
+    cook_engine* e = H(h);
+    const cook_queue_step* sp = &s;
+    const cook_queue_carry* cp = &cy;
+    const cook_finished* fp = finished ? &f : 0;
+    const cook_host_churn* hp = &hc;
+    const cook_reservations* rp = &rv;
+    const uint32_t k = (uint32_t)num_considerable;
+    return cook_cycle_run_queue_reserve_multi(&e, 1, &sp, &cp, &fp, &hp, &rp, &k);
+  }
+  return cook_cycle_run_queue_reserve(H(h), &s, &cy, finished ? &f : 0, &hc, &rv, (uint32_t)num_considerable);
+}
+/* reserve-hosts! on its own, for the next rank cycle (cook_cycle_set_reservations): rsv_pending / rsv_host as above; n_reserve = 0: no
+ * reservations */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleSetReservations(JNIEnv* env, jclass c, jlong h, jint n_reserve, jobject rsv_pending,
+                                                                 jobject rsv_host) {
+  int bad = 0;
+  const jint nr = n_reserve > 0 ? n_reserve : 0;
+  cook_reservations rv;
+  (void)c;
+  rv.release_matched = 0u;
+  rv.replace = 1u;
+  rv.n = (uint32_t)nr;
+  rv.pending = BUFN(const uint32_t, rsv_pending, nr);
+  rv.host = BUFN(const uint32_t, rsv_host, nr);
+  if (bad) return COOK_E_INVALID;
+  return cook_cycle_set_reservations(H(h), &rv);
+}
+/* the counts of the last call that could change the reservations (cook_cycle_reserve_info): info_out = direct buffer of one cook_reserve_info */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleReserveInfo(JNIEnv* env, jclass c, jlong h, jobject info_out) {
+  int bad = 0;
+  cook_reserve_info* out = BUF(cook_reserve_info, info_out);
+  (void)c;
+  if (bad || !out) return COOK_E_INVALID;
+  return cook_cycle_reserve_info(H(h), out);
+}
+/* the live reservations (cook_cycle_fetch_reservations): pending_out / host_out = direct buffers of cap uint32 each (null: skipped),
+ * n_out = direct buffer of one jint that receives their count (also when cap is too small: COOK_E_INVALID, nothing written) */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleFetchReservations(JNIEnv* env, jclass c, jlong h, jint cap, jobject pending_out,
+                                                                   jobject host_out, jobject n_out) {
+  int bad = 0, rc;
+  const jint cp = cap > 0 ? cap : 0;
+  uint32_t* pending = BUFN(uint32_t, pending_out, cp);
+  uint32_t* host = BUFN(uint32_t, host_out, cp);
+  jint* n = BUFN(jint, n_out, 1);
+  uint32_t got = 0u;
+  (void)c;
+  if (bad || !n) return COOK_E_INVALID;
+  rc = cook_cycle_fetch_reservations(H(h), pending, host, (uint32_t)cp, &got);
+  *n = (jint)got;
+  return rc;
+}
 /* the running usage of n staged engines of one device in ONE call (cook_rank_pool_usage_multi): usage_out = direct buffer of n cook_usage */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_rankPoolUsageMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n, jobject usage_out) {
   cook_engine* es[64];

@@ -239,6 +239,36 @@ class HostChurn:
         return st, (js, self.leave, self.before, self.join)
 
 
+class CookReservations(C.Structure):  # cook_cycle_set_reservations, cook_cycle_run_queue_reserve*
+    _fields_ = [("release_matched", C.c_uint32), ("replace", C.c_uint32), ("n", C.c_uint32), ("pending", _u32p), ("host", _u32p)]
+
+
+class CookReserveInfo(C.Structure):  # cook_cycle_reserve_info
+    _fields_ = [("released", C.c_uint32), ("installed", C.c_uint32), ("dropped_launched", C.c_uint32), ("alive", C.c_uint32)]
+
+
+ReserveInfo = CookReserveInfo
+
+
+class Reservations:
+    """What a queue cycle (or cook_cycle_set_reservations) does to the engine's host reservations (cook_reservations).  pending: per
+    list entry the pending ordinal of the job (NONE_U32: a job outside this pool), host: the host id reserved for it;
+    release_matched: the last cycle's kept matches release theirs first; replace: the list replaces the map (False: it is ignored)."""
+
+    def __init__(self, pending=None, host=None, release_matched: bool = True, replace: bool = True):
+        self.pending = _arr(pending if pending is not None else [], np.uint32)
+        self.host = _arr(host if host is not None else [], np.uint32)
+        assert self.pending.shape == self.host.shape and self.pending.ndim == 1, "pending and host: one entry per reservation"
+        self.release_matched, self.replace = release_matched, replace
+
+    def as_struct(self):
+        """-> (CookReservations, the objects its pointers refer to)"""
+        n = len(self.pending)
+        st = CookReservations(int(self.release_matched), int(self.replace), n, _ptr(self.pending, _u32p) if n else _u32p(),
+                              _ptr(self.host, _u32p) if n else _u32p())
+        return st, (self.pending, self.host)
+
+
 class OfferRows:
     """Caller-allocated columns for cook_cycle_fetch_offers (cook_offer_rows): room for `cap` rows at the given widths; `skip` names
     columns that are passed as NULL.  After the call, offers() returns the fetched table as an Offers with every column."""

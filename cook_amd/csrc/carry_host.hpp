@@ -7,12 +7,13 @@
 #pragma once
 #include "carry_kernels.hpp"
 
-// what a queue cycle's entry point was given (carry, finished, hosts: null = none)
+// what a queue cycle's entry point was given (carry, finished, hosts, reservations: null = none)
 struct QueueArgs {
   const cook_queue_step* step;
   const cook_queue_carry* carry;
   const cook_finished* finished;
   const cook_host_churn* hosts = nullptr;
+  const cook_reservations* reservations = nullptr;
 };
 
 // where a queue cycle's advance lands its read-backs in h_scratch, in 64-bit words: the advance's two counters (1 word), the carry's

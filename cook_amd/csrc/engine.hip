@@ -63,6 +63,7 @@ struct QueueBufs;      // queue_host.hpp
 struct CarryBufs;      // carry_host.hpp
 struct ReleaseBufs;    // release_host.hpp
 struct ChurnBufs;      // churn_host.hpp
+struct ReserveBufs;    // reserve_host.hpp
 
 }  // namespace
 
@@ -205,6 +206,7 @@ struct cook_engine {
   std::unique_ptr<CarryBufs> cyb;              // the carry of a queue cycle (allocated on first use)
   std::unique_ptr<ReleaseBufs> rlb;            // the release of a queue cycle (allocated on first use)
   std::unique_ptr<ChurnBufs> chb;              // the host churn of a queue cycle (allocated on first use)
+  std::unique_ptr<ReserveBufs> rvb;            // the rebalancer's host reservations kept across cycles (allocated on first use)
   // the host's mirror of the staged offers' host ids, ascending (match_stage_offers, cook_cycle_update's offers; a host churn edits it per
   // list entry): what a churn is checked against and sized by before its first launch.  Not known: offers built on the device
   std::vector<uint32_t> o_hosts;
@@ -299,6 +301,7 @@ static std::atomic<int> g_engines_on_device[64];
 #include "pool_batch.hpp"      // the flows of several pools on one stream (defines what launch.hpp and device_buf.hpp only declare)
 #include "rank_host.hpp"       // scan and radix drivers, the rank
 #include "classfit_host.hpp"   // class-ordered best fit: set-up and launch (match_host.hpp attempts it)
+static void reserve_drop(cook_engine* e);  // reserve_host.hpp: a stage or an update drops the engine's own reservation map
 #include "match_host.hpp"      // match staging, one pool's placement, several pools in lockstep rounds
 #include "served_host.hpp"     // several pools by served walkers
 #include "considerable_host.hpp"
@@ -311,6 +314,7 @@ static std::atomic<int> g_engines_on_device[64];
 #include "carry_host.hpp"      // a queue cycle's carry: needs the staged user state (considerable_host.hpp)
 #include "release_host.hpp"    // a queue cycle's release: the carry's segments and column sets
 #include "churn_host.hpp"      // a queue cycle's host churn: the release's host-indexed table, the carry's segments
+#include "reserve_host.hpp"    // the host reservations kept across cycles: the advance's counters (churn_kernels.hpp)
 #include "queue_host.hpp"
 #include "sweep_host.hpp"
 #include "unscheduled_host.hpp"
@@ -532,7 +536,9 @@ int cook_cycle_update(cook_engine* e, const cook_cycle_delta* delta) {
   const double sync0 = tl_sync_ms;
   const unsigned alloc0 = tl_dbuf_allocs;
   const int rc = guarded(e, [&] {
+    ReserveSuspend hold(e);  // the staged reserved hosts are what the update checks, edits and re-points ...
     cycle_update(e, bufs(e->ub), delta);
+    hold.drop();  // ... and, the rows having shifted, what the match reads again (a refused update keeps the engine's map)
     prof_collect(e);
   });
   if (e) {
@@ -594,14 +600,21 @@ int cook_cycle_run_queue_release(cook_engine* e, const cook_queue_step* step, co
 // (with the host churn, churn_host.hpp: hosts that leave or join, applied to the staged offers behind the release)
 int cook_cycle_run_queue_hosts(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
                                const cook_host_churn* hosts, uint32_t num_considerable) {
-  return cycle_run_one(e, [&] { return cycle_queue_part(e, QueueArgs{step, carry, finished, hosts}, num_considerable); }, /*defer=*/false);
+  return cook_cycle_run_queue_reserve(e, step, carry, finished, hosts, nullptr, num_considerable);
+}
+// (with the host reservations, reserve_host.hpp: the kept matches release theirs, a rebalancer's list replaces the map, behind the churn)
+int cook_cycle_run_queue_reserve(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
+                                 const cook_host_churn* hosts, const cook_reservations* reservations, uint32_t num_considerable) {
+  return cycle_run_one(e, [&] { return cycle_queue_part(e, QueueArgs{step, carry, finished, hosts, reservations}, num_considerable); }, /*defer=*/false);
 }
 // ... for every pool of a GPU: one flow per pool in a pool batch, as cook_cycle_run_rank_multi (steps, carries, finished: null = none)
 static int queue_run_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
-                           const cook_finished* const* finished, const cook_host_churn* const* hosts, const uint32_t* num_considerable) {
+                           const cook_finished* const* finished, const cook_host_churn* const* hosts, const cook_reservations* const* reservations,
+                           const uint32_t* num_considerable) {
   if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
   auto args = [&](uint32_t i) {
-    return QueueArgs{steps ? steps[i] : nullptr, carries ? carries[i] : nullptr, finished ? finished[i] : nullptr, hosts ? hosts[i] : nullptr};
+    return QueueArgs{steps ? steps[i] : nullptr, carries ? carries[i] : nullptr, finished ? finished[i] : nullptr, hosts ? hosts[i] : nullptr,
+                     reservations ? reservations[i] : nullptr};
   };
   return run_pools_batched(
       engines, n,
@@ -610,19 +623,39 @@ static int queue_run_multi(cook_engine** engines, uint32_t n, const cook_queue_s
       /*rank_part=*/true);
 }
 int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const uint32_t* num_considerable) {
-  return queue_run_multi(engines, n, steps, nullptr, nullptr, nullptr, num_considerable);
+  return queue_run_multi(engines, n, steps, nullptr, nullptr, nullptr, nullptr, num_considerable);
 }
 int cook_cycle_run_queue_carry_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
                                      const uint32_t* num_considerable) {
-  return queue_run_multi(engines, n, steps, carries, nullptr, nullptr, num_considerable);
+  return queue_run_multi(engines, n, steps, carries, nullptr, nullptr, nullptr, num_considerable);
 }
 int cook_cycle_run_queue_release_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
                                        const cook_finished* const* finished, const uint32_t* num_considerable) {
-  return queue_run_multi(engines, n, steps, carries, finished, nullptr, num_considerable);
+  return queue_run_multi(engines, n, steps, carries, finished, nullptr, nullptr, num_considerable);
 }
 int cook_cycle_run_queue_hosts_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
                                      const cook_finished* const* finished, const cook_host_churn* const* hosts, const uint32_t* num_considerable) {
-  return queue_run_multi(engines, n, steps, carries, finished, hosts, num_considerable);
+  return queue_run_multi(engines, n, steps, carries, finished, hosts, nullptr, num_considerable);
+}
+int cook_cycle_run_queue_reserve_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
+                                       const cook_finished* const* finished, const cook_host_churn* const* hosts,
+                                       const cook_reservations* const* reservations, const uint32_t* num_considerable) {
+  return queue_run_multi(engines, n, steps, carries, finished, hosts, reservations, num_considerable);
+}
+int cook_cycle_set_reservations(cook_engine* e, const cook_reservations* r) {
+  return guarded(e, [&] {
+    reserve_set(e, r);
+    prof_collect(e);
+  });
+}
+int cook_cycle_reserve_info(cook_engine* e, cook_reserve_info* out) {
+  return guarded(e, [&] {
+    if (!out) e->fail(COOK_E_INVALID, "cook_cycle_reserve_info: null out");
+    *out = e->rvb ? e->rvb->info : cook_reserve_info{};
+  });
+}
+int cook_cycle_fetch_reservations(cook_engine* e, uint32_t* pending, uint32_t* host, uint32_t cap, uint32_t* n_out) {
+  return guarded(e, [&] { reserve_fetch(e, pending, host, cap, n_out); });
 }
 int cook_cycle_churn_info(cook_engine* e, cook_churn_info* out) {
   return guarded(e, [&] {

@@ -93,6 +93,7 @@ void match_stage_inputs(cook_engine* e, const cook_jobs* j, const cook_offers* o
     for (unsigned k = 0; k < K; ++k)
       if (j->group[k] != COOK_NONE_U32 && j->group[k] >= G) e->fail(COOK_E_INVALID, "cook_match_stage: group id out of range");
   e->placement_drop();  // (the columns below may move: a set-up would point at freed ones)
+  reserve_drop(e);      // (the engine's own reservation map and `launched` go with the rows they index)
   MatchIn& in = e->min;
   std::memset(&in, 0, sizeof(in));
   in.K = K;

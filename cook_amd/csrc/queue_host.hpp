@@ -5,7 +5,9 @@
 // jobs removed and of cotasks folded in — in ONE synchronisation; the new queue length is the only value the host needs before it
 // sizes the considerable filters' launches.  A carry (carry_host.hpp) is enqueued in the same place, over the same old rows.
 // A release (release_host.hpp) is enqueued behind the carry and the fold, also when there is nothing to advance over; its counters ride
-// in the same synchronisation.  A host churn (churn_host.hpp) is enqueued behind the release; its counter rides there too.
+// in the same synchronisation.  A host churn (churn_host.hpp) is enqueued behind the release; its counter rides there too.  The host
+// reservations (reserve_host.hpp) are enqueued behind the churn: they touch neither the queue nor the offers, and their two counters
+// ride there as well.
 #pragma once
 #include "queue_kernels.hpp"
 
@@ -36,6 +38,7 @@ void queue_check_step(cook_engine* e, const QueueArgs& q) {
   carry_check(e, q);
   release_check(e, q);
   churn_check(e, q);
+  reserve_check(e, q);
   if (!s) return;
   if (s->remove_mode > 1u) e->fail(COOK_E_INVALID, "cook_queue_step.remove_mode: 0 = the kept matches, 1 = every considered job");
   if (s->offer_skipped && s->n_offer_skipped != e->M)
@@ -74,16 +77,17 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   const unsigned n = e->n_ranked, k = e->cycle_considered, G = e->G, M_old = e->M;
   const bool fold = G && k && in.j_group && !(s && s->groups);
   unsigned* cnt = b.counters.ensure(REL_CNT_WORDS);
-  const bool advance = k && n, release = release_active(f), churn = churn_active(q.hosts);
+  const bool advance = k && n, release = release_active(f), churn = churn_active(q.hosts), reserve = reserve_active(q.reservations);
   bool carried = false;
-  if (advance || release || churn) memset_async(e, cnt, 0, REL_CNT_WORDS * 4);
+  const uint8_t* skipped = nullptr;  // the step's offer_skipped on the device (the advance's kernels and the reservations' release read it)
+  if (advance || release || churn || reserve) memset_async(e, cnt, 0, REL_CNT_WORDS * 4);
   if (advance) {
     int* removed = b.removed.ensure(n);
     memset_async(e, removed, 0, (size_t)n * 4);
     unsigned* add_cnt = b.add_cnt.ensure(std::max(1u, G));
     unsigned* cursor = b.cursor.ensure(std::max(1u, G));
     if (fold) memset_async(e, add_cnt, 0, (size_t)G * 4), memset_async(e, cursor, 0, (size_t)G * 4);
-    const uint8_t* skipped = (s && s->offer_skipped && M_old) ? h2d_opt(e, b.skipped, s->offer_skipped, M_old) : nullptr;
+    skipped = (s && s->offer_skipped && M_old) ? h2d_opt(e, b.skipped, s->offer_skipped, M_old) : nullptr;
     const int32_t* j2o = e->m_j2o.ptr();
     const uint32_t* j_index = e->j_index.ptr();
     KM<q_mark_removed, 256>(e, "q_mark_removed", div_up(k, 256), e->q_last_pos, j2o, k, n, skipped, (unsigned)(s && s->remove_mode == 1u), j_index,
@@ -119,7 +123,9 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   if (carry_release_offers(q)) e->o_run_cols_made = true;
   // ---- the host churn: behind the release (all of the above index the OLD rows), in front of the considerable filters ------------------
   if (q.hosts || e->chb) churn_enqueue(e, q.hosts, cnt);
-  if (release || churn) pinned_copy(e, e->h_scratch + REL_H_CNT, cnt, REL_CNT_WORDS * 4, hipMemcpyDeviceToHost);
+  // ---- the host reservations: the last cycle's kept matches release theirs, a rebalancer's list replaces the map ----------------------------
+  if (q.reservations || e->rvb) reserve_enqueue(e, q.reservations, cnt, skipped, advance ? k : 0u);
+  if (release || churn || reserve) pinned_copy(e, e->h_scratch + REL_H_CNT, cnt, REL_CNT_WORDS * 4, hipMemcpyDeviceToHost);
   // ---- the step's groups and offers (behind the kernels above on the stream: the fold read the OLD offers) ------------------------------
   if (s && s->groups && G) {
     const cook_groups* g = s->groups;
@@ -136,7 +142,7 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   if (s && s->offers) match_stage_offers(e, s->offers, false);
   if (e->chb) e->chb->info.n_offers = e->M;  // (the rows behind the advance, whoever set them)
   carry_tokens(e, c);
-  if (advance || release || churn || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
+  if (advance || release || churn || reserve || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
   if (c) carry_finish(e);
   if (advance) {
     unsigned h[2] = {0, 0};
@@ -144,11 +150,12 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
     e->n_ranked = n - h[0];
     if (fold) e->cf_group_run_total += h[1];
   }
-  if (release || churn) {
+  if (release || churn || reserve) {
     unsigned h[REL_CNT_WORDS];
     std::memcpy(h, e->h_scratch + REL_H_CNT, sizeof(h));
     release_finish(e, h);
     churn_finish(e, h);
+    reserve_finish(e, h);
   }
   e->q_advance_us = (uint32_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count();
 }

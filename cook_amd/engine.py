@@ -338,6 +338,46 @@ class Engine:
                                                        int(num_considerable)))
         del keep, fkeep, hkeep
 
+    def cycle_run_queue_reserve(self, num_considerable: int, carry: Optional[A.QueueCarry] = None, finished: Optional[A.Finished] = None,
+                                hosts: Optional[A.HostChurn] = None, reservations: Optional[A.Reservations] = None, **step):
+        """cycle_run_queue_hosts with the host reservations (cook_cycle_run_queue_reserve): behind the churn the last cycle's kept
+        matches release their reservations (reservations.release_matched) and the list replaces the engine's map
+        (reservations.replace), on the device.  reservations None: exactly cycle_run_queue_hosts."""
+        st, keep = self._queue_step(**step)
+        cs = carry.as_struct() if carry is not None else None
+        fs, fkeep = finished.as_struct() if finished is not None else (None, None)
+        hs, hkeep = hosts.as_struct() if hosts is not None else (None, None)
+        rs, rkeep = reservations.as_struct() if reservations is not None else (None, None)
+        self._chk(self._lib.cook_cycle_run_queue_reserve(self._h, C.byref(st), C.byref(cs) if cs is not None else None,
+                                                         C.byref(fs) if fs is not None else None, C.byref(hs) if hs is not None else None,
+                                                         C.byref(rs) if rs is not None else None, int(num_considerable)))
+        del keep, fkeep, hkeep, rkeep
+
+    def cycle_set_reservations(self, reservations: Optional[A.Reservations] = None):
+        """reserve-hosts! on its own (cook_cycle_set_reservations): the list replaces the engine's reservation map for the next cycle,
+        rank cycle or queue cycle; None: no reservations.  Touches neither the standing queue nor the placement."""
+        rs, rkeep = reservations.as_struct() if reservations is not None else (None, None)
+        self._chk(self._lib.cook_cycle_set_reservations(self._h, C.byref(rs) if rs is not None else None))
+        del rkeep
+
+    def reserve_info(self) -> dict:
+        """The counts of the last call that could change the reservation map (cook_cycle_reserve_info)."""
+        out = A.CookReserveInfo()
+        self._chk(self._lib.cook_cycle_reserve_info(self._h, C.byref(out)))
+        return {k: int(getattr(out, k)) for k, _ in A.CookReserveInfo._fields_}
+
+    def fetch_reservations(self):
+        """-> (pending, host): the live reservations in list order (cook_cycle_fetch_reservations); pending NONE_U32: a job outside
+        this pool."""
+        n = C.c_uint32(0)
+        rc = self._lib.cook_cycle_fetch_reservations(self._h, None, None, 0, C.byref(n))
+        if rc != 0 and n.value == 0:
+            self._chk(rc)
+        cap = max(1, n.value)
+        pend, host = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        self._chk(self._lib.cook_cycle_fetch_reservations(self._h, _p(pend, C.c_uint32), _p(host, C.c_uint32), cap, C.byref(n)))
+        return pend[:n.value].copy(), host[:n.value].copy()
+
     def churn_info(self) -> dict:
         """The counts of the last queue cycle's host churn (cook_cycle_churn_info); all 0 (n_offers: the staged rows) when it had none."""
         out = A.CookChurnInfo()
@@ -955,6 +995,53 @@ def cycle_run_queue_hosts_multi(engines: Sequence[Engine], num_considerable, ste
     fptrs = (C.c_void_p * n)(*[C.addressof(f) if f is not None else None for f, _ in fs])
     hptrs = (C.c_void_p * n)(*[C.addressof(h) if h is not None else None for h, _ in hs])
     _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_hosts_multi(arr, n, ptrs, cptrs, fptrs, hptrs, ks))
+
+
+def cycle_run_queue_reserve_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None,
+                                  carries: Optional[Sequence[Optional[A.QueueCarry]]] = None,
+                                  finished: Optional[Sequence[Optional[A.Finished]]] = None,
+                                  hosts: Optional[Sequence[Optional[A.HostChurn]]] = None,
+                                  reservations: Optional[Sequence[Optional[A.Reservations]]] = None):
+    """cycle_run_queue_hosts_multi with one cook_reservations per engine (cook_cycle_run_queue_reserve_multi; None: none for that
+    pool); cycle_match_multi places them.  A pool whose step is refused stays as it was and raises after the others have gone on."""
+    if not engines:
+        return
+    n = len(engines)
+    arr = (C.c_void_p * n)(*[e._h for e in engines])
+    ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
+    assert len(ks) == n
+    ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
+    steps = list(steps) if steps is not None else [None] * n
+    carries = list(carries) if carries is not None else [None] * n
+    finished = list(finished) if finished is not None else [None] * n
+    hosts = list(hosts) if hosts is not None else [None] * n
+    reservations = list(reservations) if reservations is not None else [None] * n
+    assert len(steps) == n and len(carries) == n and len(finished) == n and len(hosts) == n and len(reservations) == n
+    built = [e._queue_step(**(s or {})) for e, s in zip(engines, steps)]
+    cs = [c.as_struct() if c is not None else None for c in carries]
+    fs = [f.as_struct() if f is not None else (None, None) for f in finished]
+    hs = [h.as_struct() if h is not None else (None, None) for h in hosts]
+    rs = [r.as_struct() if r is not None else (None, None) for r in reservations]
+    ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
+    cptrs = (C.c_void_p * n)(*[C.addressof(c) if c is not None else None for c in cs])
+    fptrs = (C.c_void_p * n)(*[C.addressof(f) if f is not None else None for f, _ in fs])
+    hptrs = (C.c_void_p * n)(*[C.addressof(h) if h is not None else None for h, _ in hs])
+    rptrs = (C.c_void_p * n)(*[C.addressof(r) if r is not None else None for r, _ in rs])
+    _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_reserve_multi(arr, n, ptrs, cptrs, fptrs, hptrs, rptrs, ks))
+
+
+def reservations_of(decisions):
+    """reserve-hosts!'s filter (rebalancer.clj:419-432) over the cook_preemption rows of cook_rebalance_fetch: -> (pending_index, host)
+    arrays of the decisions that preempt more than one task.  decisions: the dicts of Engine.rebalance_fetch (`tasks`: the preempted
+    task list), or cook_preemption structs / dicts with task_n.  The NONE_U32 entries count too, as in (count (:task %))."""
+    pend, host = [], []
+    for d in decisions:
+        get = (lambda k, d=d: d[k]) if isinstance(d, dict) else (lambda k, d=d: getattr(d, k))
+        task_n = len(d["tasks"]) if isinstance(d, dict) and "task_n" not in d else int(get("task_n"))
+        if task_n > 1:
+            pend.append(int(get("pending_index")))
+            host.append(int(get("host")))
+    return np.asarray(pend, np.uint32), np.asarray(host, np.uint32)
 
 
 def cycle_match_multi(engines: Sequence[Engine]):

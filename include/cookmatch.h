@@ -451,7 +451,8 @@ int cook_cycle_stage(cook_engine* e, const cook_tasks* tasks, const cook_users* 
  * reported afterwards (cook_cycle_fetch's ranked_pending_idx) refer to the updated arrays: row i of the old arrays that was kept is
  * now at i minus the number of removed rows in front of it; add_tasks[r] is at n_kept + r.  add_pending describes the pending tasks
  * of add_tasks, in order, and may only carry optional columns that the staged jobs carry too (else restage); cpus and mem are
- * required, and so is `user` when the staged jobs carry one.  Users, groups and reserved hosts stay as staged.  The eligible mask
+ * required, and so is `user` when the staged jobs carry one.  Users, groups and reserved hosts stay as staged (a map installed by cook_cycle_set_reservations or a
+ * cook_cycle_run_queue_reserve step is dropped by this call: THE HOST RESERVATIONS below).  The eligible mask
  * of cook_cycle_set_considerable moves with the job rows (the jobs a delta adds start out eligible; send a fresh mask to say
  * otherwise).  The call is all-or-nothing: a delta it refuses (COOK_E_INVALID — a row it cannot append, a remove_task entry out of
  * range or named twice, which the device finds) leaves the resident state as it was; the host arrays are read during the call only.
@@ -515,7 +516,9 @@ int cook_cycle_fetch(cook_engine* e, uint32_t* ranked_pending_idx, uint32_t* n_r
  *     (cook_cycle_run_queue_carry below does, on the device).
  *  4. Considerable -> take num_considerable -> match over Q, exactly as a rank cycle does over the rank's output: the user state is
  *     whatever cook_cycle_set_considerable staged last (refresh usage and tokens between cycles with that call: it does not invalidate
- *     Q; or let cook_cycle_run_queue_carry add the kept placements to the staged usage on the device), the eligible mask follows the job rows, reserved hosts stay as staged, all placement forms apply unchanged.
+ *     Q; or let cook_cycle_run_queue_carry add the kept placements to the staged usage on the device), the eligible mask follows the job rows, reserved hosts stay as staged
+ *     (unless the engine holds a reservation map of its own, which cook_cycle_run_queue_reserve keeps in step with the matches and the
+ *     rebalancer: THE HOST RESERVATIONS below), all placement forms apply unchanged.
  * Afterwards cook_cycle_fetch / cook_cycle_fetch_considerable / cook_match_explain / cook_match_metrics / cook_cycle_autoscale describe
  * THIS cycle: ranked_pending_idx is the current Q (task indices, the index space of the rank), n_ranked its length, rank_pos positions
  * in it.  cook_user_stats / cook_unscheduled / cook_usage_breakdown keep describing the last RANK (they read the per-user order, which a
@@ -728,6 +731,83 @@ typedef struct cook_offer_rows {
   double* scalars;
 } cook_offer_rows;
 int cook_cycle_fetch_offers(cook_engine* e, cook_offer_rows* out);
+
+/* ---- THE HOST RESERVATIONS: the rebalancer's reserved hosts, kept on the device across match cycles -----------------------------------
+ * In the reference one atom {job-uuid->reserved-host, launched-job-uuids} moves on both clocks.  match-offer-to-schedule
+ * (scheduler.clj:645-653) reads reserved-hosts = the values of the map, and every job is kept off all of them except its own
+ * (constraints.clj:242-252).  After every match that matched something update-host-reservations! (scheduler.clj:1050-1057, called at
+ * :1517) removes the matched jobs' reservations and adds those jobs to launched-job-uuids.  After every rebalancer run reserve-hosts!
+ * (rebalancer.clj:419-432, called at :466) REPLACES the map by the decisions that preempt more than one task, minus the jobs in
+ * launched-job-uuids, and clears that set.
+ * The engine keeps exactly that atom, per engine: map = pending row -> host, launched = a set of pending rows.  On the device: a
+ * reservation list (row or COOK_NONE_U32, host id), an engine-owned reserved_host column over the staged pending rows, an engine-owned
+ * bitmap rebuilt from the live list, a byte per pending row.  Reservations are keyed by host ID, not by offer row: the host churn does
+ * not touch them, and a reserved host that leaves and returns is still reserved.  An entry whose pending is COOK_NONE_U32 reserves a
+ * host for a job that is not among this pool's pending rows (the reference's atom is one for all pools, mesos.clj:184): no match
+ * releases it, only a replacement removes it.
+ * 1. Inside a queue cycle's advance (cook_cycle_run_queue_reserve), in this order, behind the host churn and in front of the
+ *    considerable filters, also when the last cycle considered nothing or the queue is empty:
+ *    RELEASE (release_matched = 1): every considered job of the pool's LAST cycle — rank cycle or queue cycle — that has a KEPT match
+ *    (job_to_offer >= 0 and the offer not skipped by step->offer_skipped: the predicate of step 1 of the queue cycles, the fold and the
+ *    carry; remove_mode does not change it) joins `launched`; if it holds a reservation, the reservation goes and is counted in
+ *    `released`.
+ *    REPLACE (replace = 1), then: every old reservation goes; list entry i becomes a reservation unless its row is in `launched`
+ *    (counted in dropped_launched); `launched` is cleared.  This is (apply dissoc reservations launched-job-uuids) followed by
+ *    :launched-job-uuids #{}, literally.
+ *    The bitmap is rebuilt from the live list; the counts ride in the advance's ONE synchronisation.  When nothing is alive behind
+ *    the advance the match reads no bitmap at all, and the class-ordered walk (match_algo 3) is eligible again in that very cycle.
+ * 2. cook_cycle_set_reservations is the REPLACE of point 1 on its own (same drop rule, `launched` cleared, release_matched ignored;
+ *    replace = 0: the list is ignored and nothing changes — a map the engine holds stays, and without one the staged reservations
+ *    keep being read): the way to hand a rebalancer result to the next RANK cycle.
+ *    Like cook_cycle_set_considerable it touches none of the standing queue, the rank or the placement, and the match that ran last
+ *    stays described as it ran: cook_match_explain and cook_match_metrics called behind it still answer from the map that match
+ *    read (the new map goes into a second column and bitmap; the ones that match read are left alone until the next match).  It
+ *    needs cook_cycle_stage (else COOK_E_STATE), and it is refused (COOK_E_STATE, nothing changed) while a placement is set up and
+ *    has not run (between cook_cycle_run_rank* / cook_cycle_run_queue_*_multi and cook_cycle_match_multi): that placement was set
+ *    up with the map as it stands.  r NULL, or n = 0 with replace = 1: no reservations.  From the first such call, or the first _reserve step
+ *    with replace = 1, the engine's own map is what every later match reads, rank cycles and queue cycles alike, the older queue entry
+ *    points included (they leave the map as it stands).
+ * 3. Lifetime: cook_cycle_stage, cook_match_stage* and cook_cycle_update (one that is not refused) drop the engine's map and
+ *    `launched` — they shift the rows —, and the staged reserved_hosts / reserved_host are what the match reads again.  A rank without
+ *    those calls keeps the map.  A _reserve step with replace = 0 and release_matched = 1 on an engine that holds no map of its own is
+ *    refused (COOK_E_STATE): install one first; the staged bitmap does not say which job a host belongs to.
+ * 4. Refused before anything changes (COOK_E_INVALID): a flag above 1; n without pending / host; a pending index >= the staged pending
+ *    count that is not COOK_NONE_U32; a pending row twice in the list; a host id above 2^31 - 1 (cook_jobs.reserved_host is int32).  A
+ *    refused step leaves the queue, the offers, the usage, the groups and the reservations as they were.  reservations NULL, or both
+ *    flags 0: exactly cook_cycle_run_queue_hosts / _hosts_multi.  The arrays are read until the call returns.
+ *    Dense host ids are assumed, as by the host churn: the bitmap has one bit per host id up to the greatest id of the list and is
+ *    filled anew in every step that can change it (a single id near 2^31 costs a 256 MB fill per step).
+ * 5. Afterwards cook_match_explain, cook_match_metrics and cook_cycle_autoscale describe this cycle's match, which read the new map.
+ * (Additive: no existing layout changes.) */
+typedef struct cook_reservations {
+  uint32_t release_matched; /* 1: update-host-reservations! over the LAST cycle's kept matches                    */
+  uint32_t replace;         /* 1: reserve-hosts! with the list below; 0: the list is ignored, the map stays       */
+  uint32_t n;
+  const uint32_t* pending;  /* [n] pending ordinal (index space of cook_cycle_stage's pending_jobs), or
+                               COOK_NONE_U32 = a job outside this pool; a pending row at most once                 */
+  const uint32_t* host;     /* [n] host id, as cook_offers.host                                                   */
+} cook_reservations;
+typedef struct cook_reserve_info {
+  uint32_t released;         /* reservations the kept matches of the last cycle released in this advance          */
+  uint32_t installed;        /* list entries that became reservations                                             */
+  uint32_t dropped_launched; /* list entries whose row was in `launched`                                          */
+  uint32_t alive;            /* reservations held behind the call                                                 */
+} cook_reserve_info;
+int cook_cycle_set_reservations(cook_engine* e, const cook_reservations* r);
+int cook_cycle_run_queue_reserve(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
+                                 const cook_host_churn* hosts, const cook_reservations* reservations, uint32_t num_considerable);
+/* as cook_cycle_run_queue_hosts_multi (then cook_cycle_match_multi); reservations NULL or an entry NULL: none for that pool */
+int cook_cycle_run_queue_reserve_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps,
+                                       const cook_queue_carry* const* carries, const cook_finished* const* finished,
+                                       const cook_host_churn* const* hosts, const cook_reservations* const* reservations,
+                                       const uint32_t* num_considerable);
+/* the counts of the last call that could change the map (a queue cycle, cook_cycle_set_reservations); all 0 (alive = the live
+ * reservations) when it changed nothing; all 0 without a map of the engine's own */
+int cook_cycle_reserve_info(cook_engine* e, cook_reserve_info* out);
+/* the live reservations in list order: pending[i] (a pending ordinal or COOK_NONE_U32) holds host[i]; either array may be NULL;
+ * *n_out = their count; cap smaller than that: COOK_E_INVALID with *n_out set and nothing written.  No map of the engine's own: 0.
+ * Changes no state; one synchronisation */
+int cook_cycle_fetch_reservations(cook_engine* e, uint32_t* pending, uint32_t* host, uint32_t cap, uint32_t* n_out);
 
 /* ---- REBALANCE: replaces init-state + the rebalance loop's decisions ---------------------------------------
  * (rebalancer.clj:222-266, 320-407, 270-309, 434-467; dru.clj:128-144).

@@ -25,7 +25,11 @@ The host churn (cook_cycle_run_queue_hosts*), --churn: the relea
 staged hosts leaving and as many rows joining (hosts that return, new hosts; anchored at random old rows or at the end).  Leg one is a
 queue cycle with carry + release + churn and no table upload; leg two's host supplies the same table through step->offers (its
 arithmetic — the oracles of tests/ — is NOT timed).  Both legs must place every job identically in every cycle, or the run fails.
-    python scripts/bench_queue.py [--steps 50] [--warmup 5] [--k-all] [--carry | --carry-only] [--release | --release-only] [--churn | --churn-only]
+The host reservations (cook_cycle_run_queue_reserve*), --reserve: leg one of --churn through the new entry point, once
+with reservations = NULL and once with, per queue cycle, release_matched = 1 and a replacement list of RESERVE_LIST random entries
+(the two legs place differently: hosts are reserved); the row has both cycle times and the device time of the reserve kernels beside
+the carry's, the release's and the churn's.
+    python scripts/bench_queue.py [--steps 50] [--warmup 5] [--k-all] [--carry | --carry-only] [--release | --release-only] [--churn | --churn-only] [--reserve]
                                   [--out results/queue.json]"""
 import argparse
 import copy
@@ -42,7 +46,7 @@ sys.path.insert(0, ROOT)
 
 from cook_amd import _abi as A  # noqa: E402
 from cook_amd import workload  # noqa: E402
-from cook_amd.engine import (Engine, cycle_match_multi, cycle_run_queue_carry_multi, cycle_run_queue_hosts_multi, cycle_run_queue_multi,  # noqa: E402
+from cook_amd.engine import (Engine, cycle_match_multi, cycle_run_queue_carry_multi, cycle_run_queue_hosts_multi, cycle_run_queue_multi, cycle_run_queue_reserve_multi,  # noqa: E402
                              cycle_run_queue_release_multi, cycle_run_rank_multi)
 from tests import autoscale_cases as AS  # noqa: E402
 from tests import carry_oracle as CO  # noqa: E402
@@ -57,6 +61,8 @@ RELEASE = ("release_host_rows", "release_keys", "release_fold_offers", "release_
            "release_group_scan", "release_group_offsets", "release_group_compact")
 RELEASE_FRAC = 0.3  # of the episode's placements that have not ended yet, per queue cycle
 CHURN = ("churn_mark", "churn_scan", "churn_source", "churn_gather")
+RESERVE = ("resv_release", "resv_retire", "resv_install", "resv_bits")
+RESERVE_LIST = 128  # entries of a cycle's replacement list: max-preemption of the reference's rebalancer tests
 CHURN_FRAC = 0.01  # of the staged hosts leave per queue cycle, and as many rows join
 ADVANCE = ("q_mark_removed", "q_queue_scan", "q_compact_ranked", "q_group_scan", "q_fold_offsets", "q_fold_copy_old", "q_fold_append")
 
@@ -360,9 +366,11 @@ def run_release(name, pools, k, steps, warmup):
             "advance_syncs": 1, "identical_placements": True, "released_per_cycle": released, "groups": grouped}
 
 
-def run_churn(name, pools, k, steps, warmup):
+def run_churn(name, pools, k, steps, warmup, reserve=False):
     """the two legs of the host churn (carry + release + churn against a host that supplies the table, the user state and the groups);
-    -> one result row"""
+    -> one result row.  reserve: instead of the host's leg, the same carry + release + churn cycles through
+    cook_cycle_run_queue_reserve* with reservations = NULL (leg one) and with, per queue cycle, release_matched = 1 and a replacement
+    list of RESERVE_LIST entries (leg two; its placements differ: hosts are reserved)"""
     params = A.default_params()
     n = len(pools)
     states = [AS.random_state(pl, 40 + i, tokens=False, pool_quota=False) for i, pl in enumerate(pools)]
@@ -422,7 +430,8 @@ def run_churn(name, pools, k, steps, warmup):
                 record.append(note(engines, c, draw))
         return ts
 
-    def leg(step, first_leg=False):
+    def leg(step, first_leg=False, profile=None):
+        profile = first_leg if profile is None else profile
         engines = [Engine(params) for _ in pools]
         try:
             for e, pl in zip(engines, pools):
@@ -431,7 +440,7 @@ def run_churn(name, pools, k, steps, warmup):
             for ep in range(episodes):
                 ts += episode(engines, step, first if ep == 0 else None, draw=first_leg and ep == 0)
             prof = None
-            if first_leg:  # launches and device time of the advance's parts, in a profiled episode of its own
+            if profile:  # launches and device time of the advance's parts, in a profiled episode of its own
                 for e in engines:
                     e.set_profiling(True)
                 episode(engines, step, None)
@@ -439,7 +448,8 @@ def run_churn(name, pools, k, steps, warmup):
                 part = lambda names, x: sum(v[x] for t in kt for nm, v in t.items() if nm in names)
                 prof = dict(launches=round(part(ADVANCE + CARRY + RELEASE + CHURN, 1) / cyc / n, 1), churn_launches=round(part(CHURN, 1) / cyc / n, 1),
                             carry_us=round(part(CARRY, 0) * 1e3 / cyc, 1), release_us=round(part(RELEASE, 0) * 1e3 / cyc, 1),
-                            churn_us=round(part(CHURN, 0) * 1e3 / cyc, 1))
+                            churn_us=round(part(CHURN, 0) * 1e3 / cyc, 1), reserve_us=round(part(RESERVE, 0) * 1e3 / cyc, 1),
+                            reserve_launches=round(part(RESERVE, 1) / cyc / n, 1))
             return first, ts[warmup:], prof
         finally:
             for e in engines:
@@ -452,6 +462,27 @@ def run_churn(name, pools, k, steps, warmup):
             cycle_run_queue_hosts_multi(engines, ks, None, [both] * n, [lists[i][c] for i in range(n)], [churns[i][c] for i in range(n)])
             cycle_match_multi(engines)
 
+    if reserve:
+        rr = np.random.default_rng(777)
+        rlists = [[A.Reservations(rr.choice(pl.pending_jobs.n, min(RESERVE_LIST, pl.pending_jobs.n), replace=False),
+                                  rr.choice(pl.offers.host, min(RESERVE_LIST, pl.pending_jobs.n))) for _ in range(cyc + 1)] for pl in pools]
+
+        def step_reserve(with_lists):
+            def step(engines, c):
+                rv = [rlists[i][c] if with_lists else None for i in range(n)]
+                if n == 1:
+                    engines[0].cycle_run_queue_reserve(ks[0], both, lists[0][c], churns[0][c], rv[0])
+                else:
+                    cycle_run_queue_reserve_multi(engines, ks, None, [both] * n, [lists[i][c] for i in range(n)], [churns[i][c] for i in range(n)], rv)
+                    cycle_match_multi(engines)
+            return step
+        _, t0, prof0 = leg(step_reserve(False), first_leg=True)
+        _, t1, prof1 = leg(step_reserve(True), profile=True)
+        return {"config": name + ", carry + release + churn through cook_cycle_run_queue_reserve", "pools": n, "K": k or "all", "timed_cycles": len(t1),
+                "reservations_null_cycle_ms": median_ms(t0), "reservations_cycle_ms": median_ms(t1), "list_entries_per_cycle": RESERVE_LIST,
+                "carry_kernels_us_per_cycle": prof1["carry_us"], "release_kernels_us_per_cycle": prof1["release_us"],
+                "churn_kernels_us_per_cycle": prof1["churn_us"], "reserve_kernels_us_per_cycle": prof1["reserve_us"],
+                "reserve_launches_per_pool": prof1["reserve_launches"], "reserve_kernels_us_per_cycle_null": prof0["reserve_us"], "advance_syncs": 1}
     got1, t1, prof = leg(step_churn, first_leg=True)
     # what the host of leg two supplies: the oracles' carry, release and churn of leg one's own placements and lists (untimed)
     supply = [[None] * (cyc + 1) for _ in pools]
@@ -511,6 +542,7 @@ def main():
     ap.add_argument("--release-only", action="store_true", help="only the two legs of the release (and, with --carry, of the carry)")
     ap.add_argument("--churn", action="store_true", help="also the two legs of the host churn")
     ap.add_argument("--churn-only", action="store_true", help="only the two legs of the host churn (and, with --carry / --release, of those)")
+    ap.add_argument("--reserve", action="store_true", help="only the churn's first leg through cook_cycle_run_queue_reserve*, without and with reservations")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--k-all", action="store_true")
@@ -524,6 +556,10 @@ def main():
         rows.append(r)
         print(json.dumps(r), flush=True)
     for k in [1000] + ([0] if args.k_all else []):
+        if args.reserve:
+            add(run_churn("one C4 pool", c4[:1], k, args.steps, args.warmup, reserve=True))
+            add(run_churn("eight C4 pools, multi form", c4, k, args.steps, args.warmup, reserve=True))
+            continue
         if not args.carry_only and not args.release_only and not args.churn_only:
             add(run("one C4 pool", c4[:1], k, args.steps, args.warmup))
             add(run("eight C4 pools, multi form", c4, k, args.steps, args.warmup))
