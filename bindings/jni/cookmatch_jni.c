@@ -1036,6 +1036,59 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_rebalance(JNIEnv* env, jclass c, jlo
   return CHECKED(cook_rebalance(H(h), &t, cached, &j, job_id, prio, &u, &s, host_attrs ? &a : 0, n_groups ? &g : 0, rp, dec, n_dec, pre,
                                 n_pre, pdru));
 }
+/* the rebalancer's stage from the pool's resident cycle state (cook_cycle_rebalance_stage), then rebalanceRun / cycleRebalanceFetch.
+ * spare (host, cpus, mem, gpus) null: from the staged offers; host_attrs null: the staged offer rows are the attribute table;
+ * offer_skipped (n_offer_skipped bytes, one per offer of the last match) only with skip_matched != 0 */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRebalanceStage(JNIEnv* env, jclass c, jlong h, jobject rparams, jint n_spare, jobjectArray spare,
+                                                                jint n_attr_rows, jobject attr_dims, jobjectArray host_attrs,
+                                                                jint skip_matched, jint n_offer_skipped, jobject offer_skipped) {
+  int bad = 0;
+  cook_offers a = offers_of(env, n_attr_rows, dims_of(env, attr_dims, &bad), host_attrs, &bad);
+  cook_host_spare s;
+  cook_cycle_rebalance req;
+  const cook_rebalance_params* rp = BUF(const cook_rebalance_params, rparams);
+  const jint ns = n_spare > 0 ? n_spare : 0;
+  (void)c;
+  if (bad || !rp) return COOK_E_INVALID;
+  s.n = (uint32_t)ns;
+  s.host = EL(const uint32_t, spare, 0, ns);
+  s.cpus = EL(const double, spare, 1, ns);
+  s.mem = EL(const double, spare, 2, ns);
+  s.gpus = EL(const double, spare, 3, ns);
+  req.params = *rp;
+  req.spare = spare ? &s : 0;
+  req.host_attrs = host_attrs ? &a : 0;
+  req.offer_skipped = BUFN(const uint8_t, offer_skipped, n_offer_skipped > 0 ? n_offer_skipped : 0);
+  req.skip_matched = (uint32_t)skip_matched;
+  req.reserved = 0u;
+  return CHECKED(cook_cycle_rebalance_stage(H(h), &req));
+}
+/* the decision sweep over what was staged (cook_rebalance_run), between cycleRebalanceStage and cycleRebalanceFetch */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_rebalanceRun(JNIEnv* env, jclass c, jlong h) {
+  (void)env;
+  (void)c;
+  return cook_rebalance_run(H(h));
+}
+/* the result in the host's index spaces (cook_cycle_rebalance_fetch): decisions_out / pending_dru_out / selected_task_out /
+ * selected_ord_out hold cap_selected entries (min(max_preemption, ranked jobs)), preempted_out cap_preempted uint32 (running rows +
+ * cap_selected); the three counts go to direct buffers of one uint32 each.  Any output may be null */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRebalanceFetch(JNIEnv* env, jclass c, jlong h, jint cap_selected, jint cap_preempted,
+                                                                jobject decisions_out, jobject n_decisions_out, jobject preempted_out,
+                                                                jobject n_preempted_out, jobject pending_dru_out, jobject selected_task_out,
+                                                                jobject selected_ord_out, jobject n_selected_out) {
+  int bad = 0;
+  const jint cs = cap_selected > 0 ? cap_selected : 0, cp = cap_preempted > 0 ? cap_preempted : 0;
+  cook_preemption* dec = BUFN(cook_preemption, decisions_out, cs);
+  uint32_t* n_dec = BUF(uint32_t, n_decisions_out);
+  uint32_t* pre = BUFN(uint32_t, preempted_out, cp);
+  uint32_t* n_pre = BUF(uint32_t, n_preempted_out);
+  double* pdru = BUFN(double, pending_dru_out, cs);
+  uint32_t* st = BUFN(uint32_t, selected_task_out, cs);
+  uint32_t* so = BUFN(uint32_t, selected_ord_out, cs);
+  uint32_t* n_sel = BUF(uint32_t, n_selected_out);
+  (void)c;
+  return CHECKED(cook_cycle_rebalance_fetch(H(h), dec, n_dec, pre, n_pre, pdru, st, so, n_sel));
+}
 
 /* ---- offers: the numeric core of kubernetes.compute-cluster/generate-offers (compute_cluster.clj:68-190) ------------ */
 static cook_nodes nodes_of(JNIEnv* env, jint n, jint n_attr_keys, jobjectArray a, int* bad_out) {

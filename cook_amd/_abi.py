@@ -322,6 +322,11 @@ class CookPreemption(C.Structure):
     ]
 
 
+class CookCycleRebalance(C.Structure):  # cook_cycle_rebalance_stage
+    _fields_ = [("params", CookRebalanceParams), ("spare", C.POINTER(CookHostSpare)), ("host_attrs", C.c_void_p),
+                ("offer_skipped", C.POINTER(C.c_uint8)), ("skip_matched", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 MAX_SCALARS, MAX_RES_SLOTS = 3, 4  # COOK_MAX_SCALARS, COOK_MAX_RES_SLOTS
 _DT = {_f64p: np.float64, _u32p: np.uint32, _i32p: np.int32, _i64p: np.int64, _u8p: np.uint8}
 _PT = {v: k for k, v in _DT.items()}

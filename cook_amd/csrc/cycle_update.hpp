@@ -345,7 +345,7 @@ void cycle_update(cook_engine* e, UpdateBufs& ub, const cook_cycle_delta* d) {
   stamp(0);
   // ---- the delta as one block -----------------------------------------------------------------------------------------------
   struct Offs {
-    size_t rem, t[9], j[12 + COOK_MAX_SCALARS], eq_off, eq_key, eq_val, nv_off, nv_host;
+    size_t rem, t[10], j[12 + COOK_MAX_SCALARS], eq_off, eq_key, eq_val, nv_off, nv_host;
   } o{};
   const unsigned add_eq = (p_add && aj->eq_off && in.j_eq_off) ? aj->eq_off[p_add] : 0u;
   const unsigned add_nv = (p_add && aj->novel_off && in.j_novel_off) ? aj->novel_off[p_add] : 0u;
@@ -356,6 +356,7 @@ void cycle_update(cook_engine* e, UpdateBufs& ub, const cook_cycle_delta* d) {
       o.t[0] = w.put(at->cpus, n_add), o.t[1] = w.put(at->mem, n_add), o.t[2] = w.put(at->gpus, n_add), o.t[3] = w.put(at->user, n_add);
       o.t[4] = w.put(at->priority, n_add), o.t[5] = w.put(at->start_ms, n_add), o.t[6] = w.put(at->task_id, n_add);
       o.t[7] = w.put(at->job_id, n_add), o.t[8] = w.put(at->pending, n_add);
+      o.t[9] = w.put(e->has_t_host ? at->host : (const uint32_t*)nullptr, n_add);
     }
     if (p_add) {
       int k = 0;
@@ -426,7 +427,9 @@ void cycle_update(cook_engine* e, UpdateBufs& ub, const cook_cycle_delta* d) {
   add_col(ts, 0, e->t_start.b, 8, dev(o.t[5], n_add), 0, N_hi);
   add_col(ts, 0, e->t_task.b, 8, dev(o.t[6], n_add), 0, N_hi);
   add_col(ts, 0, e->t_job.b, 8, dev(o.t[7], n_add), 0, N_hi);
-  add_col(ts, 0, e->t_pending.b, 1, dev(o.t[8], n_add), 0, N_hi);
+  // the running rows' hosts (cook_cycle_rebalance_stage): new rows without one get 0, and the column then counts as incomplete (below)
+  if (e->has_t_host) add_col(ts, 0, e->t_host.b, 4, dev(o.t[9], n_add), 0, N_hi);
+  add_col(ts, 0, e->t_pending.b, 1, dev(o.t[8], n_add), 0, N_hi);  // (the LAST column: pending_new below)
   if (N + n_add) KL("upd_compact_cols", upd_compact_cols, div_up(N + n_add, 256), 256, ts, (const int*)rm, (const SumI*)incl, N, n_add, 0u, out);
   // pending ordinals of the new task array: exclusive count of pending rows in front (reads the NEW pending column)
   uint32_t* pend_ord_new = ub.pend_ord_alt.ensure(std::max(1u, N_hi));
@@ -537,6 +540,7 @@ void cycle_update(cook_engine* e, UpdateBufs& ub, const cook_cycle_delta* d) {
   }
   for (unsigned r = 0; aj && aj->ports && r < p_add && !in.has_x; ++r) in.has_x = aj->ports[r] > 0;
   e->N = N2;
+  if (e->has_t_host && n_add > p_add && !at->host) e->t_host_complete = false;  // running rows were added without their hosts
   e->pool_usage_known = false;
   e->n_pending = P2;
   e->Kjobs = P2;

@@ -64,6 +64,7 @@ struct CarryBufs;      // carry_host.hpp
 struct ReleaseBufs;    // release_host.hpp
 struct ChurnBufs;      // churn_host.hpp
 struct ReserveBufs;    // reserve_host.hpp
+struct ResidentRebalBufs;  // rebal_resident_host.hpp
 
 }  // namespace
 
@@ -105,6 +106,10 @@ struct cook_engine {
   DArr<int32_t> t_prio;
   DArr<int64_t> t_start, t_task, t_job;
   DArr<uint8_t> t_pending, s_pending, head, keep, thead, dhead;
+  // the running rows' host ids (cook_tasks.host), kept when a stage passes them: has_t_host = the column exists, t_host_complete = every
+  // running row has a value (a cook_cycle_update that adds running rows without host clears it until the next stage with host)
+  DArr<uint32_t> t_host;
+  bool has_t_host = false, t_host_complete = false;
   DArr<TieCtl> tie_ctl;
   DArr<uint64_t> w0, w1, w2, dkey, nkkey, ckey;
   DArr<SumU4> s_use, pre, quseA, quseB, qpre, pool_usage;
@@ -194,6 +199,7 @@ struct cook_engine {
   // ---- the standing queue of the queue cycles (queue_host.hpp): `ranked` is the queue a match cycle may consume — the last cycle took its
   // jobs from it and nothing has shifted or dropped the rows it points at since (with rank_done and a match that has run: that cycle is complete)
   bool q_valid = false;
+  bool q_stepped = false;  // a queue cycle has advanced since the last rank: the task table no longer lists what runs (rebal_resident_host.hpp)
   const uint32_t* q_last_pos = nullptr;  // device: rank positions of the last cycle's considered jobs; null: 0 .. cycle_considered - 1
   bool q_groups_own = false;             // min.g_run_* point at a queue cycle's table; the staged one is q_sg_*
   const uint32_t *q_sg_off = nullptr, *q_sg_host = nullptr, *q_sg_attr = nullptr;
@@ -215,6 +221,7 @@ struct cook_engine {
 
   // ---- rebalancer state (allocated on first use) ----
   std::unique_ptr<RebalBufs> rb;
+  std::unique_ptr<ResidentRebalBufs> rrb;  // cook_cycle_rebalance_stage (allocated on first use)
   // ---- considerable-jobs filters (allocated on first use) ----
   std::unique_ptr<ConsBufs> cb;
   // ---- offer construction (allocated on first use) ----
@@ -319,6 +326,7 @@ static void reserve_drop(cook_engine* e);  // reserve_host.hpp: a stage or an up
 #include "sweep_host.hpp"
 #include "unscheduled_host.hpp"
 #include "usage_host.hpp"
+#include "rebal_resident_host.hpp"  // the rebalancer's stage from the resident cycle state: RebalBufs, ConsBufs' eligible mask, cycle_update.hpp's element copies
 #include "cycle_host.hpp"      // a cycle's front parts (rank or queue step, considerable filters) and its single-pool entry: needs the two above them
 
 }  // namespace
@@ -882,6 +890,24 @@ int cook_rebalance_timing(cook_engine* e, double* ms) {
   if (!e || !ms) return COOK_E_INVALID;
   *ms = e->rb ? e->rb->ms : 0.0;
   return COOK_OK;
+}
+int cook_cycle_rebalance_stage(cook_engine* e, const cook_cycle_rebalance* req) {
+  return guarded(e, [&] {
+    rebal_resident_stage(e, req);
+    prof_collect(e);
+  });
+}
+int cook_cycle_rebalance_fetch(cook_engine* e, cook_preemption* decisions, uint32_t* n_decisions, uint32_t* preempted_task_idx,
+                               uint32_t* n_preempted, double* pending_dru, uint32_t* selected_task_idx, uint32_t* selected_pending_ord,
+                               uint32_t* n_selected) {
+  if (n_decisions) *n_decisions = 0;
+  if (n_preempted) *n_preempted = 0;
+  if (n_selected) *n_selected = 0;
+  return guarded(e, [&] {
+    rebal_resident_fetch(e, decisions, n_decisions, preempted_task_idx, n_preempted, pending_dru, selected_task_idx, selected_pending_ord,
+                         n_selected);
+    prof_collect(e);
+  });
 }
 
 int cook_match_explain(cook_engine* e, const uint32_t* job_pos, uint32_t n, uint32_t* counts) {

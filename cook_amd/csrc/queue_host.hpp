@@ -71,6 +71,7 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   const cook_queue_carry* c = q.carry;
   const cook_finished* f = q.finished;
   const auto t_call = std::chrono::steady_clock::now();
+  e->q_stepped = true;
   e->q_valid = false;  // from here on the queue is being edited: a call that fails below leaves no standing queue (cycle_take_part sets it again)
   QueueBufs& b = bufs(e->qb);
   MatchIn& in = e->min;

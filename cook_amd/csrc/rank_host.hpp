@@ -87,6 +87,8 @@ void rank_stage(cook_engine* e, const cook_tasks* t, const cook_users* u) {
   h2d(e, e->t_task, t->task_id, N);
   h2d(e, e->t_job, t->job_id, N);
   h2d(e, e->t_pending, t->pending, N);
+  e->has_t_host = e->t_host_complete = t->host != nullptr;  // (cook_cycle_rebalance_stage reads it; the rank does not)
+  if (t->host) h2d(e, e->t_host, t->host, N);
   h2d(e, e->pend_ord, pend_ord.data(), N);
   h2d(e, e->u_divc, u->div_cpus, U);
   h2d(e, e->u_divm, u->div_mem, U);
@@ -193,6 +195,7 @@ void rank_run(cook_engine* e) {
   e->rank_done = false;
   e->cycle_cons_ran = false;
   e->q_valid = false;  // (the standing queue is rewritten)
+  e->q_stepped = false;
   e->ranked.ensure(std::max(1u, e->n_pending));
   if (N == 0) {
     e->rank_done = true;

@@ -9,6 +9,7 @@ constexpr unsigned RB_FIRST_MIN = COOK_SHAPE(256u, 2u);  // hosts of the first p
 
 struct RebalBufs {
   bool staged = false, done = false;
+  bool resident = false;  // staged by cook_cycle_rebalance_stage (rebal_resident_host.hpp): the slots are compacted spaces of the resident tables
   unsigned R = 0, P = 0, S = 0, U = 0, H = 0, G = 0, n_attr = 0, co_cap = 0;
   bool has_attrs = false;
   cook_rebalance_params rp{};
@@ -78,6 +79,74 @@ struct RebalBufs {
   double ms = 0;
 };
 
+// the dense per-host tables of a stage from the caller's lists (either may be null: its part stays empty), uploaded; the temporaries are
+// read until the caller's synchronisation
+struct RebalHostTmp {
+  std::vector<int32_t> row;
+  std::vector<double> sc, sm, sg;
+  std::vector<uint8_t> hs;
+};
+void rebal_stage_host_tables(cook_engine* e, RebalBufs& b, unsigned H, const cook_host_spare* spare, const cook_offers* attrs, RebalHostTmp& t) {
+  // ---- dense per-host tables -------------------------------------------------------------------------------------------------
+  std::vector<int32_t>& row = t.row;
+  std::vector<double>&sc = t.sc, &sm = t.sm, &sg = t.sg;
+  std::vector<uint8_t>& hs = t.hs;
+  row.assign(H ? H : 1, -1);
+  sc.assign(H ? H : 1, 0.0), sm.assign(H ? H : 1, 0.0), sg.assign(H ? H : 1, 0.0);
+  hs.assign(H ? H : 1, 0);
+  if (attrs)
+    for (unsigned i = 0; i < attrs->n; ++i) row[attrs->host[i]] = (int32_t)i;
+  if (spare)
+    for (unsigned i = 0; i < spare->n; ++i) {
+      const unsigned h = spare->host[i];
+      sc[h] = spare->cpus[i], sm[h] = spare->mem[i], sg[h] = spare->gpus ? spare->gpus[i] : 0.0;
+      hs[h] = 1;
+    }
+  {  // spare resources that cannot make a sum round (rebal_decide<SAFE>, with every user safe)
+    auto okv = [](double v) {
+      const double s = v * 1024.0;
+      return v >= 0.0 && v < 4194304.0 && s == (double)(long long)s;
+    };
+    b.spare_safe = true;
+    for (unsigned h = 0; h < H && b.spare_safe; ++h) b.spare_safe = okv(sc[h]) && okv(sm[h]) && okv(sg[h]);
+  }
+  h2d(e, b.row_of_host, row.data(), H);
+  h2d(e, b.spare0_c, sc.data(), H);
+  h2d(e, b.spare0_m, sm.data(), H);
+  h2d(e, b.spare0_g, sg.data(), H);
+  h2d(e, b.has_spare0, hs.data(), H);
+  b.spare_c.ensure(H), b.spare_m.ensure(H), b.spare_g.ensure(H), b.has_spare.ensure(H);
+}
+// the attribute table of a stage from the caller's rows (null or empty: none)
+void rebal_stage_attr_table(cook_engine* e, RebalBufs& b, const cook_offers* attrs) {
+  // ---- attribute table ----------------------------------------------------------------------------------------------------------
+  b.has_attrs = attrs != nullptr && attrs->n > 0;
+  b.ha_k8s = b.ha_gpu = b.ha_disk = b.ha_attr = b.ha_loc = b.ha_start = false;
+  b.n_attr = 0;
+  if (b.has_attrs) {
+    const unsigned n = attrs->n;
+    h2d(e, b.a_host, attrs->host, n);
+    if ((b.ha_k8s = attrs->k8s != nullptr)) h2d(e, b.a_k8s, attrs->k8s, n);
+    if ((b.ha_gpu = attrs->gpu_model != nullptr)) {
+      if (!attrs->gpu_count) e->fail(COOK_E_INVALID, "cook_rebalance: host_attrs gpu_model without gpu_count");
+      b.a_gpu_slots = res_slots(e, attrs->gpu_slots, "cook_rebalance: host_attrs gpu_slots");
+      h2d(e, b.a_gpu_model, attrs->gpu_model, (size_t)n * b.a_gpu_slots);
+      h2d(e, b.a_gpu_count, attrs->gpu_count, (size_t)n * b.a_gpu_slots);
+    }
+    if ((b.ha_disk = attrs->disk_type != nullptr && attrs->disk_space != nullptr)) {
+      b.a_disk_slots = res_slots(e, attrs->disk_slots, "cook_rebalance: host_attrs disk_slots");
+      h2d(e, b.a_disk_type, attrs->disk_type, (size_t)n * b.a_disk_slots);
+      h2d(e, b.a_disk_space, attrs->disk_space, (size_t)n * b.a_disk_slots);
+    }
+    if ((b.ha_attr = attrs->attr != nullptr && attrs->n_attr_keys > 0)) {
+      b.n_attr = attrs->n_attr_keys;
+      h2d(e, b.a_attr, attrs->attr, (size_t)n * b.n_attr);
+    }
+    if ((b.ha_loc = attrs->location != nullptr)) h2d(e, b.a_location, attrs->location, n);
+    if ((b.ha_start = attrs->host_start_s != nullptr)) h2d(e, b.a_host_start, attrs->host_start_s, n);
+  }
+}
+
 void rebalance_stage(cook_engine* e, RebalBufs& b, const cook_tasks* run, const uint8_t* cached, const cook_jobs* pend,
                      const int64_t* pend_job_id, const int32_t* pend_prio, const cook_users* u, const cook_host_spare* spare,
                      const cook_offers* attrs, const cook_groups* groups, const cook_rebalance_params* rp) {
@@ -89,7 +158,7 @@ void rebalance_stage(cook_engine* e, RebalBufs& b, const cook_tasks* run, const 
     e->fail(COOK_E_INVALID, "cook_rebalance: pending jobs need cpus, mem, user, job ids and priorities");
   if (S && U == 0) e->fail(COOK_E_INVALID, "cook_rebalance: no users");
   const unsigned G = groups ? groups->n : 0;
-  b.staged = b.done = false;
+  b.staged = b.done = b.resident = false;
   b.R = R, b.P = P, b.S = S, b.U = U, b.G = G;
   b.rp = *rp;
   // ---- slots: running ++ one slot per pending job (the task it becomes when placed) ---------------------------------
@@ -149,58 +218,9 @@ void rebalance_stage(cook_engine* e, RebalBufs& b, const cook_tasks* run, const 
   h2d(e, b.qcpus, u->quota_cpus, U);
   h2d(e, b.qmem, u->quota_mem, U);
   h2d(e, b.qgpus, u->quota_gpus, U);
-  // ---- dense per-host tables -------------------------------------------------------------------------------------------------
-  std::vector<int32_t> row(H ? H : 1, -1);
-  std::vector<double> sc(H ? H : 1, 0.0), sm(H ? H : 1, 0.0), sg(H ? H : 1, 0.0);
-  std::vector<uint8_t> hs(H ? H : 1, 0);
-  if (attrs)
-    for (unsigned i = 0; i < attrs->n; ++i) row[attrs->host[i]] = (int32_t)i;
-  if (spare)
-    for (unsigned i = 0; i < spare->n; ++i) {
-      const unsigned h = spare->host[i];
-      sc[h] = spare->cpus[i], sm[h] = spare->mem[i], sg[h] = spare->gpus ? spare->gpus[i] : 0.0;
-      hs[h] = 1;
-    }
-  {  // spare resources that cannot make a sum round (rebal_decide<SAFE>, with every user safe)
-    auto okv = [](double v) {
-      const double s = v * 1024.0;
-      return v >= 0.0 && v < 4194304.0 && s == (double)(long long)s;
-    };
-    b.spare_safe = true;
-    for (unsigned h = 0; h < H && b.spare_safe; ++h) b.spare_safe = okv(sc[h]) && okv(sm[h]) && okv(sg[h]);
-  }
-  h2d(e, b.row_of_host, row.data(), H);
-  h2d(e, b.spare0_c, sc.data(), H);
-  h2d(e, b.spare0_m, sm.data(), H);
-  h2d(e, b.spare0_g, sg.data(), H);
-  h2d(e, b.has_spare0, hs.data(), H);
-  b.spare_c.ensure(H), b.spare_m.ensure(H), b.spare_g.ensure(H), b.has_spare.ensure(H);
-  // ---- attribute table ----------------------------------------------------------------------------------------------------------
-  b.has_attrs = attrs != nullptr && attrs->n > 0;
-  b.ha_k8s = b.ha_gpu = b.ha_disk = b.ha_attr = b.ha_loc = b.ha_start = false;
-  b.n_attr = 0;
-  if (b.has_attrs) {
-    const unsigned n = attrs->n;
-    h2d(e, b.a_host, attrs->host, n);
-    if ((b.ha_k8s = attrs->k8s != nullptr)) h2d(e, b.a_k8s, attrs->k8s, n);
-    if ((b.ha_gpu = attrs->gpu_model != nullptr)) {
-      if (!attrs->gpu_count) e->fail(COOK_E_INVALID, "cook_rebalance: host_attrs gpu_model without gpu_count");
-      b.a_gpu_slots = res_slots(e, attrs->gpu_slots, "cook_rebalance: host_attrs gpu_slots");
-      h2d(e, b.a_gpu_model, attrs->gpu_model, (size_t)n * b.a_gpu_slots);
-      h2d(e, b.a_gpu_count, attrs->gpu_count, (size_t)n * b.a_gpu_slots);
-    }
-    if ((b.ha_disk = attrs->disk_type != nullptr && attrs->disk_space != nullptr)) {
-      b.a_disk_slots = res_slots(e, attrs->disk_slots, "cook_rebalance: host_attrs disk_slots");
-      h2d(e, b.a_disk_type, attrs->disk_type, (size_t)n * b.a_disk_slots);
-      h2d(e, b.a_disk_space, attrs->disk_space, (size_t)n * b.a_disk_slots);
-    }
-    if ((b.ha_attr = attrs->attr != nullptr && attrs->n_attr_keys > 0)) {
-      b.n_attr = attrs->n_attr_keys;
-      h2d(e, b.a_attr, attrs->attr, (size_t)n * b.n_attr);
-    }
-    if ((b.ha_loc = attrs->location != nullptr)) h2d(e, b.a_location, attrs->location, n);
-    if ((b.ha_start = attrs->host_start_s != nullptr)) h2d(e, b.a_host_start, attrs->host_start_s, n);
-  }
+  RebalHostTmp host_tmp;
+  rebal_stage_host_tables(e, b, H, spare, attrs, host_tmp);
+  rebal_stage_attr_table(e, b, attrs);
   // ---- pending jobs ------------------------------------------------------------------------------------------------------------
   h2d(e, b.j_cpus, pend->cpus, P);
   h2d(e, b.j_mem, pend->mem, P);

@@ -520,7 +520,7 @@ class Engine:
         jid = np.ascontiguousarray(pending_job_id, dtype=np.int64)
         pri = np.ascontiguousarray(pending_priority, dtype=np.int32)
         ck = np.ascontiguousarray(attrs_cached, dtype=np.uint8) if attrs_cached is not None else None
-        self._rb_p, self._rb_r = pending.n, running.n
+        self._rb_p, self._rb_r, self._rb_resident = pending.n, running.n, False
         self._chk(self._lib.cook_rebalance_stage(
             self._h, C.byref(rs), _p(ck, C.c_uint8) if ck is not None else None, C.byref(ps), _p(jid, C.c_int64),
             _p(pri, C.c_int32), C.byref(us), C.byref(ss), C.byref(hs) if hs is not None else None,
@@ -531,6 +531,11 @@ class Engine:
 
     def rebalance_fetch(self):
         P, R = self._rb_p, self._rb_r
+        if getattr(self, "_rb_resident", False):  # behind cycle_rebalance_stage _rb_p is a bound: the selected count is the engine's
+            ns = C.c_uint32(0)
+            self._chk(self._lib.cook_cycle_rebalance_fetch(self._h, None, None, None, None, None, None, None, C.byref(ns)))
+            cap, P = P, ns.value
+            assert P <= cap
         dec = (A.CookPreemption * max(1, P))()
         pre = np.zeros(max(1, R + P), dtype=np.uint32)
         pdru = np.zeros(max(1, P), dtype=np.float64)
@@ -556,6 +561,51 @@ class Engine:
         ms = C.c_double(0)
         self._lib.cook_rebalance_timing(self._h, C.byref(ms))
         return ms.value
+
+    # ---- the rebalancer from the pool's resident cycle state ---------------------------------------------------
+    def cycle_rebalance_stage(self, rparams: A.CookRebalanceParams, spare: Optional[A.HostSpare] = None,
+                              host_attrs: Optional[A.Offers] = None, skip_matched: bool = False, offer_skipped=None):
+        """cook_cycle_rebalance_stage: the rebalancer's stage built on the device from the resident task table (staged with hosts), the
+        standing queue, the pending-job columns, the staged users, groups and offers.  spare / host_attrs None: from the staged offers.
+        skip_matched: the jobs the last placement matched and kept do not count as pending (offer_skipped: per offer of that match).
+        Then rebalance_run() and cycle_rebalance_fetch()."""
+        ss = spare.as_struct() if spare is not None else None
+        hs = host_attrs.as_struct() if host_attrs is not None else None
+        sk = np.ascontiguousarray(offer_skipped, dtype=np.uint8) if offer_skipped is not None else None
+        req = A.CookCycleRebalance(rparams, C.pointer(ss) if ss is not None else None,
+                                   C.cast(C.pointer(hs), C.c_void_p) if hs is not None else None,
+                                   _p(sk, C.c_uint8) if sk is not None else None, int(skip_matched), 0)
+        self._rrb_p = max(0, min(int(rparams.max_preemption), getattr(self, "_rank_np", 0)))
+        self._chk(self._lib.cook_cycle_rebalance_stage(self._h, C.byref(req)))
+        self._rb_p, self._rb_r, self._rb_resident = self._rrb_p, getattr(self, "_rank_n", 0), True  # (rebalance_fetch behind a resident stage: the compacted spaces)
+
+    def cycle_rebalance_fetch(self) -> dict:
+        """cook_cycle_rebalance_fetch -> the dict of rebalance_fetch with `tasks` as rows of the resident task table (NONE_U32 = a job
+        placed earlier in this call) and pending_index into the selected list, plus selected_task_idx (task rows, the space of
+        cycle_fetch's ranked) and selected_pending_ord (pending ordinals, the key of Reservations) of that list."""
+        P, R = self._rrb_p, getattr(self, "_rank_n", 0)
+        dec = (A.CookPreemption * max(1, P))()
+        pre = np.zeros(max(1, R + P), dtype=np.uint32)
+        pdru = np.zeros(max(1, P), dtype=np.float64)
+        st, so = np.zeros(max(1, P), dtype=np.uint32), np.zeros(max(1, P), dtype=np.uint32)
+        nd, npre, ns = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._lib.cook_cycle_rebalance_fetch(self._h, dec, C.byref(nd), _p(pre, C.c_uint32), C.byref(npre), _p(pdru, C.c_double),
+                                                       _p(st, C.c_uint32), _p(so, C.c_uint32), C.byref(ns)))
+        out = []
+        for i in range(nd.value):
+            d = dec[i]
+            out.append(dict(pending_index=d.pending_index, host=d.host, dru=d.dru, cpus=d.cpus, mem=d.mem, gpus=d.gpus,
+                            tasks=[int(x) for x in pre[d.task_off: d.task_off + d.task_n]]))
+        n = ns.value
+        return dict(decisions=out, pending_dru=pdru[:n].copy(), final=None, selected_task_idx=st[:n].copy(), selected_pending_ord=so[:n].copy())
+
+    def cycle_rebalance(self, rparams: A.CookRebalanceParams, spare: Optional[A.HostSpare] = None, host_attrs: Optional[A.Offers] = None,
+                        skip_matched: bool = False, offer_skipped=None) -> dict:
+        """stage + run + fetch of the rebalancer over the resident cycle state (at a rank trigger: cycle_update -> cycle ->
+        cycle_rebalance -> reservations_of(decisions, pending_ord=...) -> cycle_set_reservations)."""
+        self.cycle_rebalance_stage(rparams, spare, host_attrs, skip_matched, offer_skipped)
+        self.rebalance_run()
+        return self.cycle_rebalance_fetch()
 
     # ---- consumers of the placement's by-products ----------------------------------------------------------------
     def match_explain(self, job_pos) -> np.ndarray:
@@ -1030,10 +1080,12 @@ def cycle_run_queue_reserve_multi(engines: Sequence[Engine], num_considerable, s
     _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_reserve_multi(arr, n, ptrs, cptrs, fptrs, hptrs, rptrs, ks))
 
 
-def reservations_of(decisions):
+def reservations_of(decisions, pending_ord=None):
     """reserve-hosts!'s filter (rebalancer.clj:419-432) over the cook_preemption rows of cook_rebalance_fetch: -> (pending_index, host)
     arrays of the decisions that preempt more than one task.  decisions: the dicts of Engine.rebalance_fetch (`tasks`: the preempted
-    task list), or cook_preemption structs / dicts with task_n.  The NONE_U32 entries count too, as in (count (:task %))."""
+    task list), or cook_preemption structs / dicts with task_n.  The NONE_U32 entries count too, as in (count (:task %)).
+    pending_ord (optional): the selected_pending_ord of Engine.cycle_rebalance_fetch; the first array then holds pending ordinals,
+    the key of Reservations, instead of indices into the selected list."""
     pend, host = [], []
     for d in decisions:
         get = (lambda k, d=d: d[k]) if isinstance(d, dict) else (lambda k, d=d: getattr(d, k))
@@ -1041,7 +1093,10 @@ def reservations_of(decisions):
         if task_n > 1:
             pend.append(int(get("pending_index")))
             host.append(int(get("host")))
-    return np.asarray(pend, np.uint32), np.asarray(host, np.uint32)
+    pend = np.asarray(pend, np.uint32)
+    if pending_ord is not None:
+        pend = np.asarray(pending_ord, np.uint32)[pend]
+    return pend, np.asarray(host, np.uint32)
 
 
 def cycle_match_multi(engines: Sequence[Engine]):

@@ -100,7 +100,8 @@ typedef struct cook_tasks {
   const int64_t* task_id;  /* :db/id of the instance; ignored for pending (nil sorts first)            */
   const int64_t* job_id;   /* :db/id of the job                                                        */
   const uint8_t* pending;  /* 1 = synthetic task of a waiting job, 0 = running instance                */
-  const uint32_t* host;    /* running: host id (only used by cook_rebalance); may be NULL for cook_rank */
+  const uint32_t* host;    /* running: host id (cook_rebalance; kept resident by cook_cycle_stage / cook_cycle_update for
+                              cook_cycle_rebalance_stage); may be NULL for cook_rank; never read for pending rows */
 } cook_tasks;
 
 /* ---- users: DRU divisors (share.clj:75-119,189-210) and quotas (quota.clj:272-295) ---------------------- */
@@ -837,6 +838,56 @@ int cook_rebalance_fetch(cook_engine* e, cook_preemption* decisions, uint32_t* n
                          uint32_t* n_preempted, double* pending_dru);
 /* HIP-event time of the last cook_rebalance_run in milliseconds */
 int cook_rebalance_timing(cook_engine* e, double* ms);
+
+/* ---- REBALANCE FROM THE RESIDENT CYCLE STATE: cook_rebalance_stage without the host rebuilding and uploading what the engine holds ------
+ * For a pool driven through cook_cycle_*: the stage is built on the device from the resident task table (cook_cycle_stage /
+ * cook_cycle_update, with cook_tasks.host), the standing ranked queue, the pending-job columns, the staged users, groups and offers.
+ * It is followed by cook_rebalance_run, cook_rebalance_timing and cook_cycle_rebalance_fetch; the run and its kernels are those of
+ * cook_rebalance.  The host column: cook_cycle_stage keeps cook_tasks.host when it is given (without it there is no column);
+ * cook_cycle_update carries it, new rows take add_tasks->host.  A delta that adds RUNNING rows without host to an engine that has the
+ * column is not refused: the column counts as incomplete until the next cook_cycle_stage that passes host.
+ * THE DERIVED INPUTS.  stage -> run -> fetch equals cook_rebalance called with:
+ *  - running: the rows of the resident task table with pending == 0, in ascending row order, every column, host included;
+ *    running_attrs_cached = NULL.
+ *  - pending: the standing queue in order (the ranked_pending_idx cook_cycle_fetch would return now), without the jobs whose byte in
+ *    the eligible mask of cook_cycle_set_considerable is 0 (no mask: all eligible — the host evaluates job-allowed-to-start? there);
+ *    with skip_matched also without the jobs the last placement considered, matched and kept (job_to_offer >= 0 and the offer not in
+ *    offer_skipped: the predicate of step 1 of the queue cycles; no placement since the rank: none); of those the first
+ *    params.max_preemption (<= 0: none).  Job columns: the resident pending-job columns by pending ordinal, the two CSR columns
+ *    included (user: the job column, without one the task row's); pending_job_id and pending_priority: the job's task row.
+ *  - users: the staged cook_users.  groups: the staged group table as it stands (type, attr_key, minimum, run_off / run_host).
+ *  - spare == NULL: one entry per staged offer row: host, cpus and mem are the row's; gpus is the sum of the row's gpu_count slots in
+ *    slot order (0.0 without the column).  That sum is defined by the oracle, not by the reference, which reads
+ *    host->spare-resources from view-incubating-offers with one gpus figure per host.
+ *  - host_attrs == NULL: the staged offer rows are the attribute table.
+ *  - a non-NULL spare or host_attrs is uploaded as cook_rebalance_stage does.  Dense host ids are assumed (H = greatest id + 1).
+ * COOK_E_INVALID: spare or host_attrs NULL while two staged offers share a host; skip_matched above 1; offer_skipped without
+ * skip_matched; reserved not 0; what cook_rebalance_stage refuses.
+ * COOK_E_STATE: before a completed rank since the last cook_cycle_stage / cook_cycle_update (as cook_unscheduled); without a
+ * complete host column; after any queue cycle since that rank (the task table then no longer lists what runs: a queue cycle adds no
+ * running rows); while a placement is set up and has not run.  So the host runs the rebalancer at a rank trigger:
+ * cook_cycle_update -> cycle -> cook_cycle_rebalance_stage -> cook_rebalance_run -> cook_cycle_rebalance_fetch ->
+ * cook_cycle_set_reservations.  The call changes nothing that a cycle, a queue cycle, explain, metrics, user stats, unscheduled or
+ * usage reads.  The arrays are read until the call returns; two stream synchronisations. */
+typedef struct cook_cycle_rebalance {
+  cook_rebalance_params params;
+  const cook_host_spare* spare;  /* NULL: from the staged offers                                                             */
+  const cook_offers* host_attrs; /* NULL: the staged offer rows are the attribute table                                      */
+  const uint8_t* offer_skipped;  /* with skip_matched: per offer of the last match, as cook_queue_step's; NULL = none skipped */
+  uint32_t skip_matched;         /* 1: jobs the last placement matched and kept do not count as pending                      */
+  uint32_t reserved;             /* 0 */
+} cook_cycle_rebalance;
+int cook_cycle_rebalance_stage(cook_engine* e, const cook_cycle_rebalance* req);
+/* The result in the host's index spaces (any pointer may be NULL).  decisions[].pending_index indexes the selected list:
+ * selected_task_idx[p] is that job's task index (the space of cook_cycle_fetch's ranked_pending_idx), selected_pending_ord[p] its
+ * pending ordinal (the key of cook_reservations); *n_selected their count.  preempted_task_idx holds rows of the resident task
+ * table, translated on the device (COOK_NONE_U32 = a job placed earlier in this call).  Capacities: decisions, pending_dru and the two
+ * maps min(max_preemption, ranked jobs); preempted_task_idx the running rows + that.  COOK_E_STATE unless the last stage was
+ * cook_cycle_rebalance_stage and cook_rebalance_run has run.  cook_rebalance_fetch behind a resident stage keeps working and reports
+ * the compacted spaces: preempted = ordinal among the running rows, pending_index = index into the selected list. */
+int cook_cycle_rebalance_fetch(cook_engine* e, cook_preemption* decisions, uint32_t* n_decisions, uint32_t* preempted_task_idx,
+                               uint32_t* n_preempted, double* pending_dru, uint32_t* selected_task_idx,
+                               uint32_t* selected_pending_ord, uint32_t* n_selected);
 
 /* ---- EXPLAIN: the placement-failure summary of a job ("why unscheduled") --------------------------------------------
  * Replaces fenzo-utils/summarize-placement-failure over the TaskAssignmentResults Fenzo returns for an unassigned task
