@@ -170,6 +170,61 @@ static cook_groups groups_of(JNIEnv* env, jint n, jobjectArray a, int* bad) {
   g.run_attr = EL(const uint32_t, a, 5, nr);
   return g;
 }
+/* the parts of a queue cycle (cycleRunQueue*), each from the jints and buffers its exports take; o / g: the step's offers and groups
+ * as the export built them, or null */
+#define BUFP(T, b, count) ((T*)buf_n(env, (b), (uint64_t)(count) * sizeof(T), bad))
+static cook_queue_step step_of(JNIEnv* env, jint remove_mode, jint n_last_offers, jobject offer_skipped, const cook_offers* o,
+                               const cook_groups* g, int* bad) {
+  cook_queue_step s;
+  const jint nl = n_last_offers > 0 ? n_last_offers : 0;
+  s.offer_skipped = BUFP(const uint8_t, offer_skipped, nl);
+  s.remove_mode = (uint32_t)remove_mode;
+  s.n_offer_skipped = (uint32_t)nl; /* the library refuses a count other than the last cycle's offers */
+  s.offers = o;
+  s.groups = g;
+  return s;
+}
+static cook_queue_carry carry_of(JNIEnv* env, jint carry_offers, jint carry_usage, jint n_users, jobject tokens_left, int* bad) {
+  cook_queue_carry cy;
+  cy.offers = (uint32_t)carry_offers;
+  cy.usage = (uint32_t)carry_usage;
+  cy.tokens_left = BUFP(const int64_t, tokens_left, n_users > 0 ? n_users : 0);
+  return cy;
+}
+static cook_finished finished_of(JNIEnv* env, jint n_finished, jint n_fin_scalars, jobjectArray a, jint release_offers, jint release_usage,
+                                 jint release_groups, int* bad) {
+  cook_finished f;
+  const jint nf = n_finished > 0 ? n_finished : 0, ns = n_fin_scalars > 0 ? n_fin_scalars : 0;
+  f.n = (uint32_t)nf;
+  f.host = EL(const uint32_t, a, 0, nf);
+  f.user = EL(const uint32_t, a, 1, nf);
+  f.cpus = EL(const double, a, 2, nf);
+  f.mem = EL(const double, a, 3, nf);
+  f.gpus = EL(const double, a, 4, nf);
+  f.ports = EL(const int32_t, a, 5, nf);
+  f.scalars = EL(const double, a, 6, (uint64_t)nf * (uint64_t)ns);
+  f.n_scalars = (uint32_t)ns;
+  f.gpu_model = EL(const uint32_t, a, 7, nf);
+  f.disk_request = EL(const double, a, 8, nf);
+  f.disk_type = EL(const uint32_t, a, 9, nf);
+  f.group = EL(const uint32_t, a, 10, nf);
+  f.offers = (uint32_t)release_offers;
+  f.usage = (uint32_t)release_usage;
+  f.groups = (uint32_t)release_groups;
+  return f;
+}
+static cook_reservations reservations_of(JNIEnv* env, jint release_matched, jint replace, jint n_reserve, jobject rsv_pending,
+                                         jobject rsv_host, int* bad) {
+  cook_reservations rv;
+  const jint nr = n_reserve > 0 ? n_reserve : 0;
+  rv.release_matched = (uint32_t)release_matched;
+  rv.replace = (uint32_t)replace;
+  rv.n = (uint32_t)nr;
+  rv.pending = BUFP(const uint32_t, rsv_pending, nr);
+  rv.host = BUFP(const uint32_t, rsv_host, nr);
+  return rv;
+}
+#undef BUFP
 #undef EL
 #define EL(T, a, i, count) ((T*)elem_n(env, (a), (i), (uint64_t)(count) * sizeof(T), &bad))
 
@@ -389,13 +444,8 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueue(JNIEnv* env, jclass c,
   int bad = 0;
   cook_offers o = offers_of(env, m, dims_of(env, offer_dims, &bad), offers, &bad);
   cook_groups g = groups_of(env, n_groups, groups, &bad);
-  cook_queue_step s;
+  const cook_queue_step s = step_of(env, remove_mode, n_last_offers, offer_skipped, offers ? &o : 0, groups ? &g : 0, &bad);
   (void)c;
-  s.offer_skipped = BUFN(const uint8_t, offer_skipped, n_last_offers > 0 ? n_last_offers : 0);
-  s.remove_mode = (uint32_t)remove_mode;
-  s.n_offer_skipped = (uint32_t)(n_last_offers > 0 ? n_last_offers : 0); /* the library refuses a count other than the last cycle's offers */
-  s.offers = offers ? &o : 0;
-  s.groups = groups ? &g : 0;
   if (bad) return COOK_E_INVALID;
   return defer ? cook_cycle_run_queue_rank(H(h), &s, (uint32_t)num_considerable) : cook_cycle_run_queue(H(h), &s, (uint32_t)num_considerable);
 }
@@ -410,26 +460,15 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueueCarry(JNIEnv* env, jcla
   int bad = 0;
   cook_offers o = offers_of(env, m, dims_of(env, offer_dims, &bad), offers, &bad);
   cook_groups g = groups_of(env, n_groups, groups, &bad);
-  cook_queue_step s;
-  cook_queue_carry cy;
+  const cook_queue_step s = step_of(env, remove_mode, n_last_offers, offer_skipped, offers ? &o : 0, groups ? &g : 0, &bad);
+  const cook_queue_carry cy = carry_of(env, carry_offers, carry_usage, n_users, tokens_left, &bad);
+  cook_engine* e = H(h);
+  const cook_queue_step* sp = &s;
+  const uint32_t k = (uint32_t)num_considerable;
+  const cook_queue_carry* cp = &cy;
   (void)c;
-  s.offer_skipped = BUFN(const uint8_t, offer_skipped, n_last_offers > 0 ? n_last_offers : 0);
-  s.remove_mode = (uint32_t)remove_mode;
-  s.n_offer_skipped = (uint32_t)(n_last_offers > 0 ? n_last_offers : 0);
-  s.offers = offers ? &o : 0;
-  s.groups = groups ? &g : 0;
-  cy.offers = (uint32_t)carry_offers;
-  cy.usage = (uint32_t)carry_usage;
-  cy.tokens_left = BUFN(const int64_t, tokens_left, n_users > 0 ? n_users : 0);
   if (bad) return COOK_E_INVALID;
-  if (defer) {
-    cook_engine* e = H(h);
-    const cook_queue_step* sp = &s;
-    const cook_queue_carry* cp = &cy;
-    const uint32_t k = (uint32_t)num_considerable;
-    return cook_cycle_run_queue_carry_multi(&e, 1, &sp, &cp, &k);
-  }
-  return cook_cycle_run_queue_carry(H(h), &s, &cy, (uint32_t)num_considerable);
+  return defer ? cook_cycle_run_queue_carry_multi(&e, 1, &sp, &cp, &k) : cook_cycle_run_queue_carry(e, sp, cp, k);
 }
 /* cycleRunQueueCarry with the release (cook_cycle_run_queue_release; defer != 0: cook_cycle_run_queue_release_multi for this one pool, the
  * placement then runs in cycleMatchMulti).  finished: the n_finished tasks that ended since the last cycle, in the host's order, as an
@@ -446,45 +485,17 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueueRelease(JNIEnv* env, jc
   int bad = 0;
   cook_offers o = offers_of(env, m, dims_of(env, offer_dims, &bad), offers, &bad);
   cook_groups g = groups_of(env, n_groups, groups, &bad);
-  cook_queue_step s;
-  cook_queue_carry cy;
-  cook_finished f;
-  const jint nf = n_finished > 0 ? n_finished : 0, ns = n_fin_scalars > 0 ? n_fin_scalars : 0;
+  const cook_queue_step s = step_of(env, remove_mode, n_last_offers, offer_skipped, offers ? &o : 0, groups ? &g : 0, &bad);
+  const cook_queue_carry cy = carry_of(env, carry_offers, carry_usage, n_users, tokens_left, &bad);
+  const cook_finished f = finished_of(env, n_finished, n_fin_scalars, finished, release_offers, release_usage, release_groups, &bad);
+  cook_engine* e = H(h);
+  const cook_queue_step* sp = &s;
+  const uint32_t k = (uint32_t)num_considerable;
+  const cook_queue_carry* cp = &cy;
+  const cook_finished* fp = finished ? &f : 0;
   (void)c;
-  s.offer_skipped = BUFN(const uint8_t, offer_skipped, n_last_offers > 0 ? n_last_offers : 0);
-  s.remove_mode = (uint32_t)remove_mode;
-  s.n_offer_skipped = (uint32_t)(n_last_offers > 0 ? n_last_offers : 0);
-  s.offers = offers ? &o : 0;
-  s.groups = groups ? &g : 0;
-  cy.offers = (uint32_t)carry_offers;
-  cy.usage = (uint32_t)carry_usage;
-  cy.tokens_left = BUFN(const int64_t, tokens_left, n_users > 0 ? n_users : 0);
-  f.n = (uint32_t)nf;
-  f.host = EL(const uint32_t, finished, 0, nf);
-  f.user = EL(const uint32_t, finished, 1, nf);
-  f.cpus = EL(const double, finished, 2, nf);
-  f.mem = EL(const double, finished, 3, nf);
-  f.gpus = EL(const double, finished, 4, nf);
-  f.ports = EL(const int32_t, finished, 5, nf);
-  f.scalars = EL(const double, finished, 6, (uint64_t)nf * (uint64_t)ns);
-  f.n_scalars = (uint32_t)ns;
-  f.gpu_model = EL(const uint32_t, finished, 7, nf);
-  f.disk_request = EL(const double, finished, 8, nf);
-  f.disk_type = EL(const uint32_t, finished, 9, nf);
-  f.group = EL(const uint32_t, finished, 10, nf);
-  f.offers = (uint32_t)release_offers;
-  f.usage = (uint32_t)release_usage;
-  f.groups = (uint32_t)release_groups;
   if (bad) return COOK_E_INVALID;
-  if (defer) {
-    cook_engine* e = H(h);
-    const cook_queue_step* sp = &s;
-    const cook_queue_carry* cp = &cy;
-    const cook_finished* fp = finished ? &f : 0;
-    const uint32_t k = (uint32_t)num_considerable;
-    return cook_cycle_run_queue_release_multi(&e, 1, &sp, &cp, &fp, &k);
-  }
-  return cook_cycle_run_queue_release(H(h), &s, &cy, finished ? &f : 0, (uint32_t)num_considerable);
+  return defer ? cook_cycle_run_queue_release_multi(&e, 1, &sp, &cp, &fp, &k) : cook_cycle_run_queue_release(e, sp, cp, fp, k);
 }
 /* the counts of the last queue cycle's release (cook_cycle_release_info): info_out = direct buffer of one cook_release_info */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleReleaseInfo(JNIEnv* env, jclass c, jlong h, jobject info_out) {
@@ -510,51 +521,23 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueueHosts(JNIEnv* env, jcla
   const jint mj = m_join > 0 ? m_join : 0, nl = n_leave > 0 ? n_leave : 0;
   cook_offers o = offers_of(env, mj, dims_of(env, join_dims, &bad), join, &bad);
   cook_groups g = groups_of(env, n_groups, groups, &bad);
-  cook_queue_step s;
-  cook_queue_carry cy;
-  cook_finished f;
+  const cook_queue_step s = step_of(env, remove_mode, n_last_offers, offer_skipped, 0, groups ? &g : 0, &bad);
+  const cook_queue_carry cy = carry_of(env, carry_offers, carry_usage, n_users, tokens_left, &bad);
+  const cook_finished f = finished_of(env, n_finished, n_fin_scalars, finished, release_offers, release_usage, release_groups, &bad);
   cook_host_churn hc;
-  const jint nf = n_finished > 0 ? n_finished : 0, ns = n_fin_scalars > 0 ? n_fin_scalars : 0;
+  cook_engine* e = H(h);
+  const cook_queue_step* sp = &s;
+  const uint32_t k = (uint32_t)num_considerable;
+  const cook_queue_carry* cp = &cy;
+  const cook_finished* fp = finished ? &f : 0;
+  const cook_host_churn* hp = &hc;
   (void)c;
-  s.offer_skipped = BUFN(const uint8_t, offer_skipped, n_last_offers > 0 ? n_last_offers : 0);
-  s.remove_mode = (uint32_t)remove_mode;
-  s.n_offer_skipped = (uint32_t)(n_last_offers > 0 ? n_last_offers : 0);
-  s.offers = 0;
-  s.groups = groups ? &g : 0;
-  cy.offers = (uint32_t)carry_offers;
-  cy.usage = (uint32_t)carry_usage;
-  cy.tokens_left = BUFN(const int64_t, tokens_left, n_users > 0 ? n_users : 0);
-  f.n = (uint32_t)nf;
-  f.host = EL(const uint32_t, finished, 0, nf);
-  f.user = EL(const uint32_t, finished, 1, nf);
-  f.cpus = EL(const double, finished, 2, nf);
-  f.mem = EL(const double, finished, 3, nf);
-  f.gpus = EL(const double, finished, 4, nf);
-  f.ports = EL(const int32_t, finished, 5, nf);
-  f.scalars = EL(const double, finished, 6, (uint64_t)nf * (uint64_t)ns);
-  f.n_scalars = (uint32_t)ns;
-  f.gpu_model = EL(const uint32_t, finished, 7, nf);
-  f.disk_request = EL(const double, finished, 8, nf);
-  f.disk_type = EL(const uint32_t, finished, 9, nf);
-  f.group = EL(const uint32_t, finished, 10, nf);
-  f.offers = (uint32_t)release_offers;
-  f.usage = (uint32_t)release_usage;
-  f.groups = (uint32_t)release_groups;
   hc.n_leave = leave_host ? (uint32_t)nl : 0u;
   hc.leave_host = BUFN(const uint32_t, leave_host, nl);
   hc.join = join ? &o : 0;
   hc.join_before = BUFN(const uint32_t, join_before, mj);
   if (bad) return COOK_E_INVALID;
-  if (defer) {
-    cook_engine* e = H(h);
-    const cook_queue_step* sp = &s;
-    const cook_queue_carry* cp = &cy;
-    const cook_finished* fp = finished ? &f : 0;
-    const cook_host_churn* hp = &hc;
-    const uint32_t k = (uint32_t)num_considerable;
-    return cook_cycle_run_queue_hosts_multi(&e, 1, &sp, &cp, &fp, &hp, &k);
-  }
-  return cook_cycle_run_queue_hosts(H(h), &s, &cy, finished ? &f : 0, &hc, (uint32_t)num_considerable);
+  return defer ? cook_cycle_run_queue_hosts_multi(&e, 1, &sp, &cp, &fp, &hp, &k) : cook_cycle_run_queue_hosts(e, sp, cp, fp, hp, k);
 }
 /* the counts of the last queue cycle's host churn (cook_cycle_churn_info): info_out = direct buffer of one cook_churn_info */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleChurnInfo(JNIEnv* env, jclass c, jlong h, jobject info_out) {
@@ -620,75 +603,36 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueueReserve(JNIEnv* env, jc
                                                                  jint release_matched, jint replace, jint n_reserve, jobject rsv_pending,
                                                                  jobject rsv_host, jint defer) {
   int bad = 0;
-  const jint mj = m_join > 0 ? m_join : 0, nl = n_leave > 0 ? n_leave : 0, nr = n_reserve > 0 ? n_reserve : 0;
+  const jint mj = m_join > 0 ? m_join : 0, nl = n_leave > 0 ? n_leave : 0;
   cook_offers o = offers_of(env, mj, dims_of(env, join_dims, &bad), join, &bad);
   cook_groups g = groups_of(env, n_groups, groups, &bad);
-  cook_queue_step s;
-  cook_queue_carry cy;
-  cook_finished f;
+  const cook_queue_step s = step_of(env, remove_mode, n_last_offers, offer_skipped, 0, groups ? &g : 0, &bad);
+  const cook_queue_carry cy = carry_of(env, carry_offers, carry_usage, n_users, tokens_left, &bad);
+  const cook_finished f = finished_of(env, n_finished, n_fin_scalars, finished, release_offers, release_usage, release_groups, &bad);
+  const cook_reservations rv = reservations_of(env, release_matched, replace, n_reserve, rsv_pending, rsv_host, &bad);
   cook_host_churn hc;
-  cook_reservations rv;
-  const jint nf = n_finished > 0 ? n_finished : 0, ns = n_fin_scalars > 0 ? n_fin_scalars : 0;
+  cook_engine* e = H(h);
+  const cook_queue_step* sp = &s;
+  const uint32_t k = (uint32_t)num_considerable;
+  const cook_queue_carry* cp = &cy;
+  const cook_finished* fp = finished ? &f : 0;
+  const cook_host_churn* hp = &hc;
+  const cook_reservations* rp = &rv;
   (void)c;
-  s.offer_skipped = BUFN(const uint8_t, offer_skipped, n_last_offers > 0 ? n_last_offers : 0);
-  s.remove_mode = (uint32_t)remove_mode;
-  s.n_offer_skipped = (uint32_t)(n_last_offers > 0 ? n_last_offers : 0);
-  s.offers = 0;
-  s.groups = groups ? &g : 0;
-  cy.offers = (uint32_t)carry_offers;
-  cy.usage = (uint32_t)carry_usage;
-  cy.tokens_left = BUFN(const int64_t, tokens_left, n_users > 0 ? n_users : 0);
-  f.n = (uint32_t)nf;
-  f.host = EL(const uint32_t, finished, 0, nf);
-  f.user = EL(const uint32_t, finished, 1, nf);
-  f.cpus = EL(const double, finished, 2, nf);
-  f.mem = EL(const double, finished, 3, nf);
-  f.gpus = EL(const double, finished, 4, nf);
-  f.ports = EL(const int32_t, finished, 5, nf);
-  f.scalars = EL(const double, finished, 6, (uint64_t)nf * (uint64_t)ns);
-  f.n_scalars = (uint32_t)ns;
-  f.gpu_model = EL(const uint32_t, finished, 7, nf);
-  f.disk_request = EL(const double, finished, 8, nf);
-  f.disk_type = EL(const uint32_t, finished, 9, nf);
-  f.group = EL(const uint32_t, finished, 10, nf);
-  f.offers = (uint32_t)release_offers;
-  f.usage = (uint32_t)release_usage;
-  f.groups = (uint32_t)release_groups;
   hc.n_leave = leave_host ? (uint32_t)nl : 0u;
   hc.leave_host = BUFN(const uint32_t, leave_host, nl);
   hc.join = join ? &o : 0;
   hc.join_before = BUFN(const uint32_t, join_before, mj);
-  rv.release_matched = (uint32_t)release_matched;
-  rv.replace = (uint32_t)replace;
-  rv.n = (uint32_t)nr;
-  rv.pending = BUFN(const uint32_t, rsv_pending, nr);
-  rv.host = BUFN(const uint32_t, rsv_host, nr);
   if (bad) return COOK_E_INVALID;
-  if (defer) {
-    cook_engine* e = H(h);
-    const cook_queue_step* sp = &s;
-    const cook_queue_carry* cp = &cy;
-    const cook_finished* fp = finished ? &f : 0;
-    const cook_host_churn* hp = &hc;
-    const cook_reservations* rp = &rv;
-    const uint32_t k = (uint32_t)num_considerable;
-    return cook_cycle_run_queue_reserve_multi(&e, 1, &sp, &cp, &fp, &hp, &rp, &k);
-  }
-  return cook_cycle_run_queue_reserve(H(h), &s, &cy, finished ? &f : 0, &hc, &rv, (uint32_t)num_considerable);
+  return defer ? cook_cycle_run_queue_reserve_multi(&e, 1, &sp, &cp, &fp, &hp, &rp, &k) : cook_cycle_run_queue_reserve(e, sp, cp, fp, hp, rp, k);
 }
 /* reserve-hosts! on its own, for the next rank cycle (cook_cycle_set_reservations): rsv_pending / rsv_host as above; n_reserve = 0: no
  * reservations */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleSetReservations(JNIEnv* env, jclass c, jlong h, jint n_reserve, jobject rsv_pending,
                                                                  jobject rsv_host) {
   int bad = 0;
-  const jint nr = n_reserve > 0 ? n_reserve : 0;
-  cook_reservations rv;
+  const cook_reservations rv = reservations_of(env, 0, 1, n_reserve, rsv_pending, rsv_host, &bad);
   (void)c;
-  rv.release_matched = 0u;
-  rv.replace = 1u;
-  rv.n = (uint32_t)nr;
-  rv.pending = BUFN(const uint32_t, rsv_pending, nr);
-  rv.host = BUFN(const uint32_t, rsv_host, nr);
   if (bad) return COOK_E_INVALID;
   return cook_cycle_set_reservations(H(h), &rv);
 }

@@ -142,8 +142,9 @@ class QueueCarry:
         self.offers, self.usage = int(offers), int(usage)
         self.tokens_left = _arr(tokens_left, np.int64)
 
-    def as_struct(self) -> CookQueueCarry:
-        return CookQueueCarry(self.offers, self.usage, _ptr(self.tokens_left, _i64p))
+    def as_struct(self):
+        """-> (CookQueueCarry, the objects its pointers refer to)"""
+        return CookQueueCarry(self.offers, self.usage, _ptr(self.tokens_left, _i64p)), (self.tokens_left,)
 
 
 class CookFinished(C.Structure):  # cook_cycle_run_queue_release*

@@ -1,19 +1,20 @@
 // carry_host.hpp — host orchestration of the carry (cook_cycle_run_queue_carry*, cookmatch.h), and in front of it what
-// the carry, the release and the advance share: QueueArgs, the read-back slots, groups_install, SegSort.  Included by engine.hip inside
+// the carry, the release, the churn and the advance share: QueueArgs, the read-back slots, groups_install, SegSort, host_rows.  Included by engine.hip inside
 // its anonymous namespace, behind match_host.hpp (MatchIn's staging), considerable_host.hpp (ConsBufs) and rank_host.hpp
 // (radix_sort_masked); queue_host.hpp calls carry_check from queue_check_step and carry_enqueue / carry_finish from queue_advance.
 // Everything is enqueued on the advance's stream over the OLD offers and the OLD considered rows; the only thing the host reads back,
 // the pool's four sums, rides in the advance's one synchronisation.
 #pragma once
 #include "carry_kernels.hpp"
+#include "release_kernels.hpp"  // (release_host_rows, for host_rows below)
 
 // what a queue cycle's entry point was given (carry, finished, hosts, reservations: null = none)
 struct QueueArgs {
   const cook_queue_step* step;
   const cook_queue_carry* carry;
   const cook_finished* finished;
-  const cook_host_churn* hosts = nullptr;
-  const cook_reservations* reservations = nullptr;
+  const cook_host_churn* hosts;
+  const cook_reservations* reservations;
 };
 
 // where a queue cycle's advance lands its read-backs in h_scratch, in 64-bit words: the advance's two counters (1 word), the carry's
@@ -61,7 +62,27 @@ struct CarryBufs {
   } cols[2];
   unsigned cur = 0;
   bool pool_pending = false;  // this advance reads the pool's sums back
+  DArr<uint32_t> h2row;       // host id -> row of the staged offers (host_rows)
+  bool h2row_built = false;   // ... as THIS advance built it (queue_advance clears the mark)
 };
+
+// host id -> row of the staged offers, for the release and the churn of one advance: the table and its entries, or null and 0 where the
+// greatest host id is not known (offers built on the device) or far above the row count — the callers' kernels then look a host up in
+// o_host itself.  The first caller of an advance builds the table, the second finds it built.
+static const uint32_t* host_rows(cook_engine* e, unsigned& n_hosts) {
+  const unsigned M = e->M;
+  n_hosts = 0;
+  if (e->cf_max_host == 0xFFFFFFFFu || (size_t)e->cf_max_host > 8u * (size_t)M + 65536u) return nullptr;
+  CarryBufs& b = bufs(e->cyb);
+  n_hosts = e->cf_max_host + 1u;
+  uint32_t* t = b.h2row.ensure(n_hosts);
+  if (!b.h2row_built) {
+    memset_async(e, t, 0xFF, (size_t)n_hosts * 4);
+    KM<release_host_rows, 256>(e, "release_host_rows", div_up(M, 256), e->min.o_host, M, n_hosts, t);
+    b.h2row_built = true;
+  }
+  return t;
+}
 
 // what can refuse a carry, before anything changes (queue_check_step)
 void carry_check(cook_engine* e, const QueueArgs& q) {

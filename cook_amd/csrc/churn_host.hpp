@@ -1,6 +1,6 @@
 // churn_host.hpp — host orchestration of the host churn (cook_cycle_run_queue_hosts*, cook_cycle_fetch_offers, cookmatch.h; DESIGN.md
-// §21).  Included by engine.hip inside its anonymous namespace, behind release_host.hpp (its host-indexed table, SegSort, the counters'
-// read-back); queue_host.hpp calls churn_check from queue_check_step and churn_enqueue / churn_finish from queue_advance.  Everything
+// §21).  Included by engine.hip inside its anonymous namespace, behind release_host.hpp (carry_host.hpp's host-indexed table and SegSort, the
+// counters' read-back); queue_host.hpp calls churn_check from queue_check_step and churn_enqueue / churn_finish from queue_advance.  Everything
 // is enqueued on the advance's stream behind the carry, the groups' fold and the release, which still index the OLD rows; the one
 // counter the host reads back rides in the advance's one synchronisation.  The host knows the new row count before the first launch
 // from its mirror of the staged host ids (cook_engine::o_hosts), so no launch waits for a read-back.
@@ -21,7 +21,7 @@ struct ChurnBufs {
   // carry's) and writes the set the last match cannot have read
   Cols set[2];
   unsigned cur = 0;
-  DArr<uint32_t> h2row, src;
+  DArr<uint32_t> src;
   DArr<uint8_t> keep;
   DArr<uint64_t> akey;
   SegSort a;
@@ -156,19 +156,8 @@ void churn_enqueue(cook_engine* e, const cook_host_churn* h, unsigned* cnt) {
       jc.scal[s] = (j->scalars && s < j->n_scalars) ? h2d_opt(e, w.scal[s], j->scalars + (size_t)s * nj, nj) : nullptr;
   }
   // ---- rows of the leaving hosts and of the anchors --------------------------------------------------------------------------------------
-  const uint32_t* h2row = nullptr;
   unsigned n_hosts = 0;
-  if (M_old && e->cf_max_host != 0xFFFFFFFFu && (size_t)e->cf_max_host <= 8u * (size_t)M_old + 65536u) {  // (else churn_row_of looks through o_host)
-    n_hosts = e->cf_max_host + 1u;
-    if (e->rlb && e->rlb->h2row_hosts == n_hosts) {  // the release of this advance has built it, over the same rows
-      h2row = e->rlb->h2row.ptr();
-    } else {
-      uint32_t* t = b.h2row.ensure(n_hosts);
-      memset_async(e, t, 0xFF, (size_t)n_hosts * 4);
-      KM<release_host_rows, 256>(e, "release_host_rows", div_up(M_old, 256), in.o_host, M_old, n_hosts, t);
-      h2row = t;
-    }
-  }
+  const uint32_t* h2row = M_old ? host_rows(e, n_hosts) : nullptr;  // (null: churn_row_of looks through o_host; built by this advance's release: found)
   uint8_t* keep = b.keep.ensure(M_old);
   memset_async(e, keep, 1, M_old);
   uint64_t* akey = b.akey.ensure(nj);

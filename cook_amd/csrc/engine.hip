@@ -590,43 +590,42 @@ int cook_cycle_run_rank_multi(cook_engine** engines, uint32_t n, const uint32_t*
       /*rank_part=*/true);
 }
 // ---- queue cycles: match cycles on the standing ranked queue, without a re-rank (cookmatch.h) -----------------------------------
-// (with the carry, carry_host.hpp: the kept placements into the staged offers and the staged user state, inside the advance; with the
-// release, release_host.hpp: finished tasks' resources back into the staged offers, user state and groups, behind the carry)
+// The parts of the advance, each behind the one before: the carry (carry_host.hpp), the release (release_host.hpp), the host churn
+// (churn_host.hpp), the host reservations (reserve_host.hpp).  One pool; defer: the placement is set up and runs in cook_cycle_match_multi
+static int queue_run_one(cook_engine* e, const QueueArgs& q, uint32_t num_considerable, bool defer) {
+  return cycle_run_one(e, [&] { return cycle_queue_part(e, q, num_considerable); }, defer);
+}
 int cook_cycle_run_queue(cook_engine* e, const cook_queue_step* step, uint32_t num_considerable) {
-  return cook_cycle_run_queue_release(e, step, nullptr, nullptr, num_considerable);
+  return queue_run_one(e, QueueArgs{step, nullptr, nullptr, nullptr, nullptr}, num_considerable, /*defer=*/false);
 }
 int cook_cycle_run_queue_rank(cook_engine* e, const cook_queue_step* step, uint32_t num_considerable) {
-  return cycle_run_one(e, [&] { return cycle_queue_part(e, QueueArgs{step, nullptr, nullptr}, num_considerable); }, /*defer=*/true);
+  return queue_run_one(e, QueueArgs{step, nullptr, nullptr, nullptr, nullptr}, num_considerable, /*defer=*/true);
 }
 int cook_cycle_run_queue_carry(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, uint32_t num_considerable) {
-  return cook_cycle_run_queue_release(e, step, carry, nullptr, num_considerable);
+  return queue_run_one(e, QueueArgs{step, carry, nullptr, nullptr, nullptr}, num_considerable, /*defer=*/false);
 }
 int cook_cycle_run_queue_release(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
                                  uint32_t num_considerable) {
-  return cook_cycle_run_queue_hosts(e, step, carry, finished, nullptr, num_considerable);
+  return queue_run_one(e, QueueArgs{step, carry, finished, nullptr, nullptr}, num_considerable, /*defer=*/false);
 }
-// (with the host churn, churn_host.hpp: hosts that leave or join, applied to the staged offers behind the release)
 int cook_cycle_run_queue_hosts(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
                                const cook_host_churn* hosts, uint32_t num_considerable) {
-  return cook_cycle_run_queue_reserve(e, step, carry, finished, hosts, nullptr, num_considerable);
+  return queue_run_one(e, QueueArgs{step, carry, finished, hosts, nullptr}, num_considerable, /*defer=*/false);
 }
-// (with the host reservations, reserve_host.hpp: the kept matches release theirs, a rebalancer's list replaces the map, behind the churn)
 int cook_cycle_run_queue_reserve(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
                                  const cook_host_churn* hosts, const cook_reservations* reservations, uint32_t num_considerable) {
-  return cycle_run_one(e, [&] { return cycle_queue_part(e, QueueArgs{step, carry, finished, hosts, reservations}, num_considerable); }, /*defer=*/false);
+  return queue_run_one(e, QueueArgs{step, carry, finished, hosts, reservations}, num_considerable, /*defer=*/false);
 }
 // ... for every pool of a GPU: one flow per pool in a pool batch, as cook_cycle_run_rank_multi (steps, carries, finished: null = none)
 static int queue_run_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
                            const cook_finished* const* finished, const cook_host_churn* const* hosts, const cook_reservations* const* reservations,
                            const uint32_t* num_considerable) {
   if (!engines || n == 0 || !num_considerable) return COOK_E_INVALID;
-  auto args = [&](uint32_t i) {
-    return QueueArgs{steps ? steps[i] : nullptr, carries ? carries[i] : nullptr, finished ? finished[i] : nullptr, hosts ? hosts[i] : nullptr,
-                     reservations ? reservations[i] : nullptr};
-  };
+  auto at = [](auto* const* part, uint32_t i) { return part ? part[i] : nullptr; };
+  auto args = [&](uint32_t i) { return QueueArgs{at(steps, i), at(carries, i), at(finished, i), at(hosts, i), at(reservations, i)}; };
   return run_pools_batched(
       engines, n,
-      [&](uint32_t i) { return cycle_run_one(engines[i], [&] { return cycle_queue_part(engines[i], args(i), num_considerable[i]); }, /*defer=*/true); },
+      [&](uint32_t i) { return queue_run_one(engines[i], args(i), num_considerable[i], /*defer=*/true); },
       [&](uint32_t i) { cycle_match(engines[i], cycle_queue_part(engines[i], args(i), num_considerable[i]), /*defer=*/true); },
       /*rank_part=*/true);
 }

@@ -120,6 +120,10 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
     pinned_copy(e, e->h_scratch + Q_H_ADVANCE, cnt, 8, hipMemcpyDeviceToHost);
   }
   // ---- the release: behind the carry and the fold, whether or not the last cycle considered anything ------------------------------------
+  // (the host-id -> row table of this advance, host_rows: the release or, without one, the churn builds it and the other finds it built.
+  //  Between the two e->M, cf_max_host and min.o_host do not change — the release's carry_stage_cols stages other columns — so one
+  //  table serves both)
+  if (e->cyb) e->cyb->h2row_built = false;
   if (f || e->rlb) release_enqueue(e, f, cnt, carried, (advance && fold) ? k : 0u);
   if (carry_release_offers(q)) e->o_run_cols_made = true;
   // ---- the host churn: behind the release (all of the above index the OLD rows), in front of the considerable filters ------------------

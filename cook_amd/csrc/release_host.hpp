@@ -1,5 +1,5 @@
 // release_host.hpp — host orchestration of the release (cook_cycle_run_queue_release*, cookmatch.h).  Included by
-// engine.hip inside its anonymous namespace, behind carry_host.hpp (SegSort, CarryBufs' column sets); queue_host.hpp calls
+// engine.hip inside its anonymous namespace, behind carry_host.hpp (SegSort, host_rows, CarryBufs' column sets); queue_host.hpp calls
 // release_check from queue_check_step and release_enqueue / release_finish from queue_advance.  Everything is enqueued on the advance's
 // stream behind the carry and the groups' fold; what the host reads back — three counters behind the advance's two, and the pool's four
 // sums — rides in the advance's one synchronisation.
@@ -13,8 +13,6 @@ struct ReleaseBufs {
   DArr<uint32_t> host, user, group, gpu_model, disk_type;
   DArr<double> cpus, mem, gpus, disk_req, scal[3];
   DArr<int32_t> ports;
-  DArr<uint32_t> h2row;  // host id -> row of the staged offers
-  unsigned h2row_hosts = 0;  // entries of h2row as THIS advance's release built it (0: it did not; a churn behind it builds its own)
   DArr<uint64_t> okey, ukey, gkey;
   SegSort o, u, g;
   DArr<double> pool;  // {count, cpus, mem, gpus} of all entries
@@ -79,7 +77,6 @@ void release_enqueue(cook_engine* e, const cook_finished* f, unsigned* cnt, bool
   b.info = cook_release_info{};
   b.pending = b.pool_pending = false;
   b.n_row_entries = b.n_group_entries = 0;
-  b.h2row_hosts = 0;
   if (!release_active(f)) return;
   MatchIn& in = e->min;
   const unsigned n = f->n, M = e->M, G = e->G;
@@ -113,16 +110,8 @@ void release_enqueue(cook_engine* e, const cook_finished* f, unsigned* cnt, bool
   }
   const CarryJobs rows = l.rows();
   // ---- keys ---------------------------------------------------------------------------------------------------------------------------
-  const uint32_t* h2row = nullptr;
   unsigned n_hosts = 0;
-  if (offers && e->cf_max_host != 0xFFFFFFFFu && (size_t)e->cf_max_host <= 8u * (size_t)M + 65536u) {  // (else release_keys looks the host up in o_host)
-    n_hosts = e->cf_max_host + 1u;
-    uint32_t* t = b.h2row.ensure(n_hosts);
-    memset_async(e, t, 0xFF, (size_t)n_hosts * 4);
-    KM<release_host_rows, 256>(e, "release_host_rows", div_up(M, 256), in.o_host, M, n_hosts, t);
-    h2row = t;
-    b.h2row_hosts = n_hosts;
-  }
+  const uint32_t* h2row = offers ? host_rows(e, n_hosts) : nullptr;  // (null: release_keys looks the host up in o_host)
   uint64_t* okey = offers ? b.okey.ensure(n) : nullptr;
   uint64_t* ukey = usage ? b.ukey.ensure(n) : nullptr;
   uint64_t* gkey = groups ? b.gkey.ensure(n) : nullptr;

@@ -290,16 +290,23 @@ class Engine:
                              C.pointer(os_) if os_ is not None else None, C.pointer(gs) if gs is not None else None)
         return st, (sk, os_, gs, offers, groups)
 
+    def _queue_call(self, name: str, num_considerable: int, step: dict, *parts):
+        """One queue cycle of this engine through the C entry `name`: the step's keywords, then the parts that entry takes, in ABI order
+        (carry, finished, hosts, reservations; each None or an object whose as_struct() gives (struct, keep))."""
+        st, keep = self._queue_step(**step)
+        built = [p.as_struct() if p is not None else (None, None) for p in parts]
+        self._chk(getattr(self._lib, name)(self._h, C.byref(st), *[C.byref(s) if s is not None else None for s, _ in built],
+                                           int(num_considerable)))
+        del keep, built
+
     def cycle_run_queue(self, num_considerable: int, offer_skipped=None, remove_mode: int = 0, offers: Optional[A.Offers] = None,
                         groups: Optional[A.Groups] = None, defer: bool = False):
         """A match cycle on the standing ranked queue, without a re-rank (cook_cycle_run_queue): the last cycle's kept matches
         (remove_mode 1: every considered job) leave the queue, their cotasks join their groups on the device (or `groups` replaces the
         table), `offers` replaces the staged offers, then considerable -> take K -> match.  defer: set the placement up only
         (cook_cycle_run_queue_rank); it runs in cycle_match_multi()."""
-        st, keep = self._queue_step(offer_skipped, remove_mode, offers, groups)
-        fn = self._lib.cook_cycle_run_queue_rank if defer else self._lib.cook_cycle_run_queue
-        self._chk(fn(self._h, C.byref(st), int(num_considerable)))
-        del keep
+        self._queue_call("cook_cycle_run_queue_rank" if defer else "cook_cycle_run_queue", num_considerable,
+                         dict(offer_skipped=offer_skipped, remove_mode=remove_mode, offers=offers, groups=groups))
 
     def cycle_run_queue_rank(self, num_considerable: int, **step):
         self.cycle_run_queue(num_considerable, defer=True, **step)
@@ -308,50 +315,27 @@ class Engine:
         """cycle_run_queue with the carry (cook_cycle_run_queue_carry): before the last cycle's jobs leave the queue, its kept placements
         are subtracted from the staged offers (carry.offers; then no `offers` in the step) and added to the staged user state
         (carry.usage), on the device, in considered order.  carry None: exactly cycle_run_queue."""
-        st, keep = self._queue_step(**step)
-        cs = carry.as_struct() if carry is not None else None
-        self._chk(self._lib.cook_cycle_run_queue_carry(self._h, C.byref(st), C.byref(cs) if cs is not None else None, int(num_considerable)))
-        del keep
+        self._queue_call("cook_cycle_run_queue_carry", num_considerable, step, carry)
 
     def cycle_run_queue_release(self, num_considerable: int, carry: Optional[A.QueueCarry] = None, finished: Optional[A.Finished] = None, **step):
         """cycle_run_queue_carry with the release (cook_cycle_run_queue_release): behind the carry and the groups' fold the resources of
         the `finished` tasks go back to the staged offers (finished.offers), out of the staged user state (finished.usage) and out of the
         groups' running cotasks (finished.groups), on the device, in list order.  finished None: exactly cycle_run_queue_carry."""
-        st, keep = self._queue_step(**step)
-        cs = carry.as_struct() if carry is not None else None
-        fs, fkeep = finished.as_struct() if finished is not None else (None, None)
-        self._chk(self._lib.cook_cycle_run_queue_release(self._h, C.byref(st), C.byref(cs) if cs is not None else None,
-                                                         C.byref(fs) if fs is not None else None, int(num_considerable)))
-        del keep, fkeep
+        self._queue_call("cook_cycle_run_queue_release", num_considerable, step, carry, finished)
 
     def cycle_run_queue_hosts(self, num_considerable: int, carry: Optional[A.QueueCarry] = None, finished: Optional[A.Finished] = None,
                               hosts: Optional[A.HostChurn] = None, **step):
         """cycle_run_queue_release with the host churn (cook_cycle_run_queue_hosts): behind the carry, the groups' fold and the release
         the rows of the hosts in hosts.leave go out of the staged offers and the rows of hosts.join come in, each in front of its
         anchor, on the device; the surviving rows keep their order.  hosts None: exactly cycle_run_queue_release."""
-        st, keep = self._queue_step(**step)
-        cs = carry.as_struct() if carry is not None else None
-        fs, fkeep = finished.as_struct() if finished is not None else (None, None)
-        hs, hkeep = hosts.as_struct() if hosts is not None else (None, None)
-        self._chk(self._lib.cook_cycle_run_queue_hosts(self._h, C.byref(st), C.byref(cs) if cs is not None else None,
-                                                       C.byref(fs) if fs is not None else None, C.byref(hs) if hs is not None else None,
-                                                       int(num_considerable)))
-        del keep, fkeep, hkeep
+        self._queue_call("cook_cycle_run_queue_hosts", num_considerable, step, carry, finished, hosts)
 
     def cycle_run_queue_reserve(self, num_considerable: int, carry: Optional[A.QueueCarry] = None, finished: Optional[A.Finished] = None,
                                 hosts: Optional[A.HostChurn] = None, reservations: Optional[A.Reservations] = None, **step):
         """cycle_run_queue_hosts with the host reservations (cook_cycle_run_queue_reserve): behind the churn the last cycle's kept
         matches release their reservations (reservations.release_matched) and the list replaces the engine's map
         (reservations.replace), on the device.  reservations None: exactly cycle_run_queue_hosts."""
-        st, keep = self._queue_step(**step)
-        cs = carry.as_struct() if carry is not None else None
-        fs, fkeep = finished.as_struct() if finished is not None else (None, None)
-        hs, hkeep = hosts.as_struct() if hosts is not None else (None, None)
-        rs, rkeep = reservations.as_struct() if reservations is not None else (None, None)
-        self._chk(self._lib.cook_cycle_run_queue_reserve(self._h, C.byref(st), C.byref(cs) if cs is not None else None,
-                                                         C.byref(fs) if fs is not None else None, C.byref(hs) if hs is not None else None,
-                                                         C.byref(rs) if rs is not None else None, int(num_considerable)))
-        del keep, fkeep, hkeep, rkeep
+        self._queue_call("cook_cycle_run_queue_reserve", num_considerable, step, carry, finished, hosts, reservations)
 
     def cycle_set_reservations(self, reservations: Optional[A.Reservations] = None):
         """reserve-hosts! on its own (cook_cycle_set_reservations): the list replaces the engine's reservation map for the next cycle,
@@ -948,9 +932,9 @@ def cycle_run_rank_multi(engines: Sequence[Engine], num_considerable, user_usage
     return [o[:n_users] for o in outs] if outs is not None else None
 
 
-def cycle_run_queue_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None):
-    """cycle_run_queue_rank of several engines (pools of one device) in ONE call (cook_cycle_run_queue_multi); cycle_match_multi places
-    them.  steps: per engine None or the keywords of Engine.cycle_run_queue (offer_skipped, remove_mode, offers, groups)."""
+def _queue_call_multi(name: str, engines, num_considerable, steps, *parts):
+    """One queue cycle of several engines through the C entry `name`: per engine the step's keywords (or None), then one list per part
+    that entry takes, in ABI order (carries, finished, hosts, reservations; a list None: that part for no pool)."""
     if not engines:
         return
     n = len(engines)
@@ -958,37 +942,25 @@ def cycle_run_queue_multi(engines: Sequence[Engine], num_considerable, steps: Op
     ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
     assert len(ks) == n
     ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
-    steps = list(steps) if steps is not None else [None] * n
-    assert len(steps) == n
-    built = [e._queue_step(**(s or {})) for e, s in zip(engines, steps)]
-    ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
-    rc = engines[0]._lib.cook_cycle_run_queue_multi(arr, n, ptrs, ks)
-    if rc != 0:
-        for e in engines:
-            if e._lib.cook_last_error(e._h):
-                e._chk(rc)
-        engines[0]._chk(rc)
+    steps, *parts = [list(x) if x is not None else [None] * n for x in (steps, *parts)]
+    assert len(steps) == n and all(len(ps) == n for ps in parts)
+    built = [[e._queue_step(**(s or {})) for e, s in zip(engines, steps)]]
+    built += [[p.as_struct() if p is not None else (None, None) for p in ps] for ps in parts]
+    ptrs = [(C.c_void_p * n)(*[C.addressof(st) if st is not None else None for st, _ in b]) for b in built]
+    _check_multi(engines, getattr(engines[0]._lib, name)(arr, n, *ptrs, ks))
+
+
+def cycle_run_queue_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None):
+    """cycle_run_queue_rank of several engines (pools of one device) in ONE call (cook_cycle_run_queue_multi); cycle_match_multi places
+    them.  steps: per engine None or the keywords of Engine.cycle_run_queue (offer_skipped, remove_mode, offers, groups)."""
+    _queue_call_multi("cook_cycle_run_queue_multi", engines, num_considerable, steps)
 
 
 def cycle_run_queue_carry_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None,
                                 carries: Optional[Sequence[Optional[A.QueueCarry]]] = None):
     """cycle_run_queue_multi with one carry per engine (cook_cycle_run_queue_carry_multi; None: no carry for that pool); cycle_match_multi
     places them.  A pool whose step or carry is refused stays as it was and raises after the others have gone on."""
-    if not engines:
-        return
-    n = len(engines)
-    arr = (C.c_void_p * n)(*[e._h for e in engines])
-    ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
-    assert len(ks) == n
-    ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
-    steps = list(steps) if steps is not None else [None] * n
-    carries = list(carries) if carries is not None else [None] * n
-    assert len(steps) == n and len(carries) == n
-    built = [e._queue_step(**(s or {})) for e, s in zip(engines, steps)]
-    cs = [c.as_struct() if c is not None else None for c in carries]
-    ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
-    cptrs = (C.c_void_p * n)(*[C.addressof(c) if c is not None else None for c in cs])
-    _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_carry_multi(arr, n, ptrs, cptrs, ks))
+    _queue_call_multi("cook_cycle_run_queue_carry_multi", engines, num_considerable, steps, carries)
 
 
 def cycle_run_queue_release_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None,
@@ -997,24 +969,7 @@ def cycle_run_queue_release_multi(engines: Sequence[Engine], num_considerable, s
     """cycle_run_queue_carry_multi with one list of finished tasks per engine (cook_cycle_run_queue_release_multi; None: no release for
     that pool); cycle_match_multi places them.  A pool whose step, carry or list is refused stays as it was and raises after the
     others have gone on."""
-    if not engines:
-        return
-    n = len(engines)
-    arr = (C.c_void_p * n)(*[e._h for e in engines])
-    ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
-    assert len(ks) == n
-    ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
-    steps = list(steps) if steps is not None else [None] * n
-    carries = list(carries) if carries is not None else [None] * n
-    finished = list(finished) if finished is not None else [None] * n
-    assert len(steps) == n and len(carries) == n and len(finished) == n
-    built = [e._queue_step(**(s or {})) for e, s in zip(engines, steps)]
-    cs = [c.as_struct() if c is not None else None for c in carries]
-    fs = [f.as_struct() if f is not None else (None, None) for f in finished]
-    ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
-    cptrs = (C.c_void_p * n)(*[C.addressof(c) if c is not None else None for c in cs])
-    fptrs = (C.c_void_p * n)(*[C.addressof(f) if f is not None else None for f, _ in fs])
-    _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_release_multi(arr, n, ptrs, cptrs, fptrs, ks))
+    _queue_call_multi("cook_cycle_run_queue_release_multi", engines, num_considerable, steps, carries, finished)
 
 
 def cycle_run_queue_hosts_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None,
@@ -1024,27 +979,7 @@ def cycle_run_queue_hosts_multi(engines: Sequence[Engine], num_considerable, ste
     """cycle_run_queue_release_multi with one host churn per engine (cook_cycle_run_queue_hosts_multi; None: no churn for that pool);
     cycle_match_multi places them.  A pool whose step, carry, list or churn is refused stays as it was and raises after the others
     have gone on."""
-    if not engines:
-        return
-    n = len(engines)
-    arr = (C.c_void_p * n)(*[e._h for e in engines])
-    ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
-    assert len(ks) == n
-    ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
-    steps = list(steps) if steps is not None else [None] * n
-    carries = list(carries) if carries is not None else [None] * n
-    finished = list(finished) if finished is not None else [None] * n
-    hosts = list(hosts) if hosts is not None else [None] * n
-    assert len(steps) == n and len(carries) == n and len(finished) == n and len(hosts) == n
-    built = [e._queue_step(**(s or {})) for e, s in zip(engines, steps)]
-    cs = [c.as_struct() if c is not None else None for c in carries]
-    fs = [f.as_struct() if f is not None else (None, None) for f in finished]
-    hs = [h.as_struct() if h is not None else (None, None) for h in hosts]
-    ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
-    cptrs = (C.c_void_p * n)(*[C.addressof(c) if c is not None else None for c in cs])
-    fptrs = (C.c_void_p * n)(*[C.addressof(f) if f is not None else None for f, _ in fs])
-    hptrs = (C.c_void_p * n)(*[C.addressof(h) if h is not None else None for h, _ in hs])
-    _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_hosts_multi(arr, n, ptrs, cptrs, fptrs, hptrs, ks))
+    _queue_call_multi("cook_cycle_run_queue_hosts_multi", engines, num_considerable, steps, carries, finished, hosts)
 
 
 def cycle_run_queue_reserve_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None,
@@ -1054,30 +989,7 @@ def cycle_run_queue_reserve_multi(engines: Sequence[Engine], num_considerable, s
                                   reservations: Optional[Sequence[Optional[A.Reservations]]] = None):
     """cycle_run_queue_hosts_multi with one cook_reservations per engine (cook_cycle_run_queue_reserve_multi; None: none for that
     pool); cycle_match_multi places them.  A pool whose step is refused stays as it was and raises after the others have gone on."""
-    if not engines:
-        return
-    n = len(engines)
-    arr = (C.c_void_p * n)(*[e._h for e in engines])
-    ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
-    assert len(ks) == n
-    ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
-    steps = list(steps) if steps is not None else [None] * n
-    carries = list(carries) if carries is not None else [None] * n
-    finished = list(finished) if finished is not None else [None] * n
-    hosts = list(hosts) if hosts is not None else [None] * n
-    reservations = list(reservations) if reservations is not None else [None] * n
-    assert len(steps) == n and len(carries) == n and len(finished) == n and len(hosts) == n and len(reservations) == n
-    built = [e._queue_step(**(s or {})) for e, s in zip(engines, steps)]
-    cs = [c.as_struct() if c is not None else None for c in carries]
-    fs = [f.as_struct() if f is not None else (None, None) for f in finished]
-    hs = [h.as_struct() if h is not None else (None, None) for h in hosts]
-    rs = [r.as_struct() if r is not None else (None, None) for r in reservations]
-    ptrs = (C.c_void_p * n)(*[C.addressof(st) for st, _ in built])
-    cptrs = (C.c_void_p * n)(*[C.addressof(c) if c is not None else None for c in cs])
-    fptrs = (C.c_void_p * n)(*[C.addressof(f) if f is not None else None for f, _ in fs])
-    hptrs = (C.c_void_p * n)(*[C.addressof(h) if h is not None else None for h, _ in hs])
-    rptrs = (C.c_void_p * n)(*[C.addressof(r) if r is not None else None for r, _ in rs])
-    _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_reserve_multi(arr, n, ptrs, cptrs, fptrs, hptrs, rptrs, ks))
+    _queue_call_multi("cook_cycle_run_queue_reserve_multi", engines, num_considerable, steps, carries, finished, hosts, reservations)
 
 
 def reservations_of(decisions, pending_ord=None):

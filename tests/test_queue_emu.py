@@ -72,6 +72,51 @@ def test_queue_state_rule(make_engine):
     S.check_state_rule(make_engine, synth.make_pool(seed=106, n_pending=300, n_running=200, n_users=12, n_offers=16, constraints=True))
 
 
+class _Recorder:
+    """an engine's library, noting the cook_cycle_run_queue* functions as they are called"""
+
+    def __init__(self, lib):
+        self._lib, self.names = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("cook_cycle_run_queue"):
+            return fn
+
+        def call(*args):
+            self.names.append(name)
+            return fn(*args)
+        return call
+
+
+def test_queue_wrappers_reach_their_own_exports(make_engine):
+    """every queue-cycle wrapper of cook_amd.engine calls the C entry of its own name (the wrappers are the only coverage the eleven
+    exports have): one job leaves the queue per cycle, the deferred forms are placed by cycle_match_multi"""
+    from cook_amd import engine as E
+    single = ["cycle_run_queue", "cycle_run_queue_rank", "cycle_run_queue_carry", "cycle_run_queue_release", "cycle_run_queue_hosts",
+              "cycle_run_queue_reserve"]
+    multi = ["cycle_run_queue_multi", "cycle_run_queue_carry_multi", "cycle_run_queue_release_multi", "cycle_run_queue_hosts_multi",
+             "cycle_run_queue_reserve_multi"]
+    pool = S._tiny_pool(len(single) + len(multi) + 1, 2.0, offers=S._offers([2.0, 2.0]))
+    with make_engine(A.default_params(good_enough_fitness=1.0)) as e:
+        e._lib = rec = _Recorder(e._lib)
+        e.cycle_stage(pool.tasks, pool.users, pool.pending_jobs, pool.offers, pool.groups)
+        e.cycle_run(1)
+        for i, name in enumerate(single + multi):
+            step = dict(offers=S._offers([2.0, 2.0]))
+            carry = [] if name in ("cycle_run_queue", "cycle_run_queue_rank", "cycle_run_queue_multi") else [A.QueueCarry()]  # (zero flags)
+            if name in single:
+                getattr(e, name)(1, *carry, **step)
+            else:
+                getattr(E, name)([e], 1, [step], *[carry] * len(carry))
+            if name.endswith(("_rank", "_multi")):
+                E.cycle_match_multi([e])
+            assert rec.names == ["cook_" + name], (name, rec.names)
+            del rec.names[:]
+            Q, j2o, _ = e.cycle_fetch()
+            assert len(Q) == len(single) + len(multi) - i and j2o.tolist() == [0], (name, len(Q), j2o)
+
+
 def test_queue_struct_sizes(tmp_path):
     text, want = S.struct_size_sources()
     src = tmp_path / "sz.c"
