@@ -1,6 +1,6 @@
 // carry_host.hpp — host orchestration of the carry (cook_cycle_run_queue_carry*, cookmatch.h), and in front of it what
 // the carry, the release, the churn and the advance share: QueueArgs, the read-back slots, groups_install, SegSort, host_rows.  Included by engine.hip inside
-// its anonymous namespace, behind match_host.hpp (MatchIn's staging), considerable_host.hpp (ConsBufs) and rank_host.hpp
+// its anonymous namespace, behind offer_table.hpp (the offer columns a fold reads and writes), match_host.hpp (MatchIn's staging), considerable_host.hpp (ConsBufs) and rank_host.hpp
 // (radix_sort_masked); queue_host.hpp calls carry_check from queue_check_step and carry_enqueue / carry_finish from queue_advance.
 // Everything is enqueued on the advance's stream over the OLD offers and the OLD considered rows; the only thing the host reads back,
 // the pool's four sums, rides in the advance's one synchronisation.
@@ -54,12 +54,9 @@ struct CarryBufs {
   DArr<uint64_t> okey, ukey;
   SegSort o, u;
   DArr<double> pool;  // {count, cpus, mem, gpus} of all kept jobs
-  // the engine's own copy of the offer columns a carry changes; two sets: a carry reads the staged columns (which may be the other set)
-  // and writes a fresh one, so the last match's inputs (cook_match_explain) stay as they were
-  struct Cols {
-    DArr<double> cpus, mem, run_cpus, run_mem, scal[3], gpu_count, disk_space;
-    DArr<int32_t> run_count, num_tasks, ports;
-  } cols[2];
+  // the engine's own copy of the offer columns a fold changes (OFFER_FOLDED); two sets: a carry reads the staged columns (which may be
+  // the other set) and writes a fresh one, so the last match's inputs (cook_match_explain) stay as they were
+  OfferStore cols[2];
   unsigned cur = 0;
   bool pool_pending = false;  // this advance reads the pool's sums back
   DArr<uint32_t> h2row;       // host id -> row of the staged offers (host_rows)
@@ -100,31 +97,18 @@ void carry_check(cook_engine* e, const QueueArgs& q) {
   if (c->usage && !e->has_j_user) e->fail(COOK_E_INVALID, "cook_queue_carry: usage = 1 needs pending_jobs->user");
 }
 
-// a fold of the offers: `ci` the staged offer columns, `co` the set w of the engine's own
-static void carry_offer_cols(const MatchIn& in, unsigned M, CarryBufs::Cols& w, CarryOfferIn& ci, CarryOfferCols& co) {
-  const unsigned gs = in.gpu_slots ? in.gpu_slots : 1u, ds = in.disk_slots ? in.disk_slots : 1u;
-  ci = CarryOfferIn{}, co = CarryOfferCols{};
-  ci.cpus = in.o_cpus, ci.mem = in.o_mem, ci.run_cpus = in.o_run_cpus, ci.run_mem = in.o_run_mem;
-  ci.gpu_count = in.o_gpu_count, ci.disk_space = in.o_disk_space;
-  ci.run_count = in.o_run_count, ci.num_tasks = in.o_num_tasks, ci.ports = in.o_ports;
-  ci.k8s = in.o_k8s, ci.gpu_model = in.o_gpu_model, ci.disk_type = in.o_disk_type;
-  ci.gpu_slots = gs, ci.disk_slots = ds;
-  co.cpus = w.cpus.ensure(M), co.mem = w.mem.ensure(M), co.run_cpus = w.run_cpus.ensure(M), co.run_mem = w.run_mem.ensure(M);
-  co.run_count = w.run_count.ensure(M), co.num_tasks = w.num_tasks.ensure(M), co.ports = w.ports.ensure(M);
-  for (unsigned s = 0; s < 3u; ++s) {
-    ci.scal[s] = in.o_scal[s];
-    co.scal[s] = in.o_scal[s] ? w.scal[s].ensure(M) : nullptr;
-  }
-  co.gpu_count = in.o_gpu_count ? w.gpu_count.ensure((size_t)M * gs) : nullptr;
-  co.disk_space = in.o_disk_space ? w.disk_space.ensure((size_t)M * ds) : nullptr;
-}
-// the written columns are the staged offers from here on (hosts, attributes and limits are the same rows: host_dup and the greatest
-// host id stay valid; every match packs its offers afresh, so nothing else is cached per offer table)
-static void carry_stage_cols(MatchIn& in, const CarryOfferCols& co) {
-  in.o_cpus = co.cpus, in.o_mem = co.mem, in.o_run_cpus = co.run_cpus, in.o_run_mem = co.run_mem;
-  in.o_run_count = co.run_count, in.o_num_tasks = co.num_tasks, in.o_ports = co.ports;
-  for (unsigned s = 0; s < 3u; ++s) in.o_scal[s] = co.scal[s];
-  in.o_gpu_count = co.gpu_count, in.o_disk_space = co.disk_space;
+// a fold of the offers: `ci` the staged offer columns, `co` the set w of the engine's own, with room for the columns a fold writes: cpus,
+// mem and the columns a fold makes whatever is staged; of the others (named scalars, the maps' amounts) those the staged table has.
+// -> the written set: the staged offers from here on (offer_cols_stage, only_held: hosts, attributes and limits are the same rows, so
+// host_dup and the greatest host id stay valid; every match packs its offers afresh, so nothing else is cached per offer table)
+static OfferCols<true> carry_offer_cols(const MatchIn& in, unsigned M, OfferStore& w, CarryOfferIn& ci, CarryOfferCols& co) {
+  const OfferDims d = offer_dims(in);
+  const OfferCols<false> staged = offer_cols_of(in);
+  const OfferCols<true> out = w.ensure(d, M, [&](const auto& col) {
+    return (col.flags & OFFER_FOLDED) && ((col.flags & (OFFER_REQUIRED | OFFER_MADE)) || col.col(staged));
+  });
+  ci = fold_offer_in(staged, d), co = fold_offer_cols(out);
+  return out;
 }
 
 // Inside queue_advance, behind q_mark_removed: k > 0 considered jobs of the last cycle, their job_to_offer in e->m_j2o, their rows
@@ -152,11 +136,11 @@ bool carry_enqueue(cook_engine* e, const cook_queue_carry* c, const uint8_t* ski
     const uint32_t* perm = b.o.carry_segments(e, okey, k, M);
     CarryOfferIn ci;
     CarryOfferCols co;
-    carry_offer_cols(in, M, b.cols[b.cur ^ 1u], ci, co);
+    const OfferCols<true> out = carry_offer_cols(in, M, b.cols[b.cur ^ 1u], ci, co);
     KM<fold_offers<false>, FOLD_OT>(e, "carry_fold_offers", M, perm, (const uint32_t*)b.o.start.ptr(), (const uint32_t*)b.o.end.ptr(), M, 1u, j, ci, co,
         (unsigned*)nullptr);
     b.cur ^= 1u;
-    carry_stage_cols(in, co);
+    offer_cols_stage(in, out, offer_dims(in), M, true);
   }
   if (usage) {
     ConsBufs& cb = *e->cb;

@@ -3,23 +3,18 @@
 // counters' read-back); queue_host.hpp calls churn_check from queue_check_step and churn_enqueue / churn_finish from queue_advance.  Everything
 // is enqueued on the advance's stream behind the carry, the groups' fold and the release, which still index the OLD rows; the one
 // counter the host reads back rides in the advance's one synchronisation.  The host knows the new row count before the first launch
-// from its mirror of the staged host ids (cook_engine::o_hosts), so no launch waits for a read-back.
+// from its mirror of the staged host ids (cook_engine::o_hosts), so no launch waits for a read-back.  No column is named here: the
+// refusal "a column the staged offers lack", the joining rows' upload, the new table's columns and the fetch each walk offer_columns
+// (offer_table.hpp), which also says which columns every table has and which a carry makes.
 #pragma once
 #include "churn_kernels.hpp"
 
 struct ChurnBufs {
-  struct Cols {
-    DArr<double> cpus, mem, run_cpus, run_mem, scal[3], gpu_count, disk_space;
-    DArr<uint32_t> host, gpu_model, disk_type, attr, location;
-    DArr<uint8_t> k8s;
-    DArr<int32_t> max_tasks, num_tasks, run_count, ports;
-    DArr<int64_t> host_start;
-  };
   DArr<uint32_t> leave, before;  // the lists on the device
-  Cols join;                     // ... and the joining rows' columns
+  OfferStore join;               // ... and the joining rows' columns
   // the churn's own full column sets, written in turns: a churn reads the staged table (which may be the other set, or partly the
   // carry's) and writes the set the last match cannot have read
-  Cols set[2];
+  OfferStore set[2];
   unsigned cur = 0;
   DArr<uint32_t> src;
   DArr<uint8_t> keep;
@@ -76,11 +71,12 @@ void churn_check(cook_engine* e, const QueueArgs& q) {
     //  very advance included, whether or not it had anything to carry or to release: absent, they read as 0 for every row, and the
     //  gather writes them out when the joining rows bring values)
     const bool made = e->o_run_cols_made || carry_release_offers(q);
-    const bool lacks = (j->k8s && !in.o_k8s) || (j->gpu_model && !in.o_gpu_model) || (j->gpu_count && !in.o_gpu_count) ||
-                       (j->disk_type && !in.o_disk_type) || (j->disk_space && !in.o_disk_space) || (j->attr && !(in.o_attr && in.n_attr)) ||
-                       (j->max_tasks && !in.o_max_tasks) || (j->num_tasks && !in.o_num_tasks && !made) || (j->location && !in.o_location) ||
-                       (j->host_start_s && !in.o_host_start) || (j->run_cpus && !in.o_run_cpus && !made) || (j->run_mem && !in.o_run_mem && !made) ||
-                       (j->run_count && !in.o_run_count && !made) || (j->ports && !in.o_ports && !made) || (j->scalars && !in.o_scal[0]);
+    const OfferCols<false> staged = offer_cols_of(in);
+    bool lacks = false;
+    offer_columns([&](const auto& col) {
+      if ((col.flags & OFFER_REQUIRED) || col.sub) return;  // (the named scalars are one pointer, judged by the first; their count is compared below)
+      lacks |= j->*col.pub && !col.col(staged) && !((col.flags & OFFER_MADE) && made);
+    });
     if (lacks) e->fail(COOK_E_INVALID, "cook_host_churn: join carries a column the staged offers lack");
     auto slots = [](uint32_t x) { return x ? x : 1u; };
     if ((j->gpu_model || j->gpu_count) && slots(j->gpu_slots) != in.gpu_slots) e->fail(COOK_E_INVALID, "cook_host_churn: join->gpu_slots differs from the staged offers'");
@@ -104,28 +100,6 @@ void churn_check(cook_engine* e, const QueueArgs& q) {
   b.plan_left = left, b.plan_new = M_new;
 }
 
-// the columns of a table as the gather reads them
-static ChurnColsT<false> churn_cols_of(const MatchIn& in) {
-  ChurnColsT<false> c{};
-  c.cpus = in.o_cpus, c.mem = in.o_mem, c.host = in.o_host, c.k8s = in.o_k8s;
-  c.gpu_model = in.o_gpu_model, c.gpu_count = in.o_gpu_count, c.disk_type = in.o_disk_type, c.disk_space = in.o_disk_space;
-  c.attr = in.n_attr ? in.o_attr : nullptr;
-  c.max_tasks = in.o_max_tasks, c.num_tasks = in.o_num_tasks, c.location = in.o_location, c.host_start = in.o_host_start;
-  c.run_cpus = in.o_run_cpus, c.run_mem = in.o_run_mem, c.run_count = in.o_run_count, c.ports = in.o_ports;
-  for (unsigned s = 0; s < 3u; ++s) c.scal[s] = in.o_scal[s];
-  return c;
-}
-// the written set is the staged table from here on
-static void churn_stage_cols(MatchIn& in, const ChurnColsT<true>& c, unsigned M) {
-  in.M = M;
-  in.o_cpus = c.cpus, in.o_mem = c.mem, in.o_host = c.host, in.o_k8s = c.k8s;
-  in.o_gpu_model = c.gpu_model, in.o_gpu_count = c.gpu_count, in.o_disk_type = c.disk_type, in.o_disk_space = c.disk_space;
-  in.o_attr = c.attr;
-  in.o_max_tasks = c.max_tasks, in.o_num_tasks = c.num_tasks, in.o_location = c.location, in.o_host_start = c.host_start;
-  in.o_run_cpus = c.run_cpus, in.o_run_mem = c.run_mem, in.o_run_count = c.run_count, in.o_ports = c.ports;
-  for (unsigned s = 0; s < 3u; ++s) in.o_scal[s] = c.scal[s];
-}
-
 // Inside queue_advance, behind the release (so: over the table the NEXT match would have read), also when the last cycle considered
 // nothing.  cnt: QueueBufs::counters, zero on the stream.
 void churn_enqueue(cook_engine* e, const cook_host_churn* h, unsigned* cnt) {
@@ -136,25 +110,16 @@ void churn_enqueue(cook_engine* e, const cook_host_churn* h, unsigned* cnt) {
   MatchIn& in = e->min;
   const cook_offers* j = h->join;
   const unsigned M_old = e->M, n_leave = h->n_leave, nj = j ? j->n : 0u, M_new = b.plan_new;
-  const unsigned gs = in.gpu_slots ? in.gpu_slots : 1u, ds = in.disk_slots ? in.disk_slots : 1u, na = in.n_attr;
+  const OfferDims d = offer_dims(in);
   // ---- the lists (read until the advance's synchronisation) ----------------------------------------------------------------------------
   const uint32_t* leave = h2d_opt(e, b.leave, h->leave_host, n_leave);
   const uint32_t* before = nj ? h2d_opt(e, b.before, h->join_before, nj) : nullptr;
-  ChurnColsT<false> jc{};
-  if (nj) {
-    ChurnBufs::Cols& w = b.join;
-    jc.cpus = h2d_opt(e, w.cpus, j->cpus, nj), jc.mem = h2d_opt(e, w.mem, j->mem, nj), jc.host = h2d_opt(e, w.host, j->host, nj);
-    jc.k8s = h2d_opt(e, w.k8s, j->k8s, nj);
-    jc.gpu_model = h2d_opt(e, w.gpu_model, j->gpu_model, (size_t)nj * gs), jc.gpu_count = h2d_opt(e, w.gpu_count, j->gpu_count, (size_t)nj * gs);
-    jc.disk_type = h2d_opt(e, w.disk_type, j->disk_type, (size_t)nj * ds), jc.disk_space = h2d_opt(e, w.disk_space, j->disk_space, (size_t)nj * ds);
-    jc.attr = na ? h2d_opt(e, w.attr, j->attr, (size_t)nj * na) : nullptr;
-    jc.max_tasks = h2d_opt(e, w.max_tasks, j->max_tasks, nj), jc.num_tasks = h2d_opt(e, w.num_tasks, j->num_tasks, nj);
-    jc.location = h2d_opt(e, w.location, j->location, nj), jc.host_start = h2d_opt(e, w.host_start, j->host_start_s, nj);
-    jc.run_cpus = h2d_opt(e, w.run_cpus, j->run_cpus, nj), jc.run_mem = h2d_opt(e, w.run_mem, j->run_mem, nj);
-    jc.run_count = h2d_opt(e, w.run_count, j->run_count, nj), jc.ports = h2d_opt(e, w.ports, j->ports, nj);
-    for (unsigned s = 0; s < 3u; ++s)
-      jc.scal[s] = (j->scalars && s < j->n_scalars) ? h2d_opt(e, w.scal[s], j->scalars + (size_t)s * nj, nj) : nullptr;
-  }
+  OfferCols<false> jc{};
+  if (nj)
+    offer_columns([&](const auto& col) {
+      const size_t width = d.width(col.kind);
+      col.col(jc) = width ? h2d_opt(e, col.col(b.join), col.of(*j), nj * width) : nullptr;
+    });
   // ---- rows of the leaving hosts and of the anchors --------------------------------------------------------------------------------------
   unsigned n_hosts = 0;
   const uint32_t* h2row = M_old ? host_rows(e, n_hosts) : nullptr;  // (null: churn_row_of looks through o_host; built by this advance's release: found)
@@ -173,26 +138,16 @@ void churn_enqueue(cook_engine* e, const cook_host_churn* h, unsigned* cnt) {
   // ---- ONE gather of every column into the set the staged table is not -------------------------------------------------------------------
   ChurnGather& g = b.h_args;
   g = ChurnGather{};
-  g.old = churn_cols_of(in), g.join = jc;
-  g.M_old = M_old, g.n_join = nj, g.M_new = M_new, g.gpu_slots = gs, g.disk_slots = ds, g.n_attr = na;
-  ChurnBufs::Cols& w = b.set[b.cur ^ 1u];
-  auto col = [&](auto& darr, const void* staged, size_t width) { return staged ? darr.ensure((size_t)M_new * width) : nullptr; };
-  const void* always = &g;  // cpus, mem and host are columns of every table
-  g.out.cpus = col(w.cpus, always, 1), g.out.mem = col(w.mem, always, 1), g.out.host = col(w.host, always, 1);
-  g.out.k8s = col(w.k8s, g.old.k8s, 1);
-  g.out.gpu_model = col(w.gpu_model, g.old.gpu_model, gs), g.out.gpu_count = col(w.gpu_count, g.old.gpu_count, gs);
-  g.out.disk_type = col(w.disk_type, g.old.disk_type, ds), g.out.disk_space = col(w.disk_space, g.old.disk_space, ds);
-  g.out.attr = col(w.attr, g.old.attr, na);
-  auto either = [](const void* a, const void* b) { return a ? a : b; };  // (the five columns a carry makes: also when only the joining rows have values)
-  g.out.max_tasks = col(w.max_tasks, g.old.max_tasks, 1), g.out.num_tasks = col(w.num_tasks, either(g.old.num_tasks, jc.num_tasks), 1);
-  g.out.location = col(w.location, g.old.location, 1), g.out.host_start = col(w.host_start, g.old.host_start, 1);
-  g.out.run_cpus = col(w.run_cpus, either(g.old.run_cpus, jc.run_cpus), 1), g.out.run_mem = col(w.run_mem, either(g.old.run_mem, jc.run_mem), 1);
-  g.out.run_count = col(w.run_count, either(g.old.run_count, jc.run_count), 1), g.out.ports = col(w.ports, either(g.old.ports, jc.ports), 1);
-  for (unsigned s = 0; s < 3u; ++s) g.out.scal[s] = col(w.scal[s], g.old.scal[s], 1);
+  g.old = offer_cols_of(in), g.join = jc;
+  g.M_old = M_old, g.n_join = nj, g.M_new = M_new, g.dims = d;
+  // the new table has the columns the old one has, and of the columns a carry makes also those only the joining rows bring values for
+  g.out = b.set[b.cur ^ 1u].ensure(d, M_new, [&](const auto& col) {
+    return (col.flags & OFFER_REQUIRED) || col.col(g.old) || ((col.flags & OFFER_MADE) && col.col(jc));
+  });
   const ChurnGather* d_args = h2d_opt(e, b.d_args, (const ChurnGather*)&g, 1);
   KM<churn_gather, 256>(e, "churn_gather", div_up(M_new, 256), d_args, (const uint32_t*)src);
   b.cur ^= 1u;
-  churn_stage_cols(in, g.out, M_new);
+  offer_cols_stage(in, g.out, d, M_new);
   e->M = M_new;
   // ---- the mirror: host_dup stays 0, and the greatest host id stays exact (the class-ordered walk's and the release's tables) --------------
   std::vector<uint32_t>& staged = e->o_hosts;
@@ -218,30 +173,23 @@ void churn_fetch_offers(cook_engine* e, cook_offer_rows* out) {
   if (!out) e->fail(COOK_E_INVALID, "cook_cycle_fetch_offers: null out");
   if (!e->match_staged) e->fail(COOK_E_STATE, "cook_cycle_fetch_offers before offers were staged");
   const MatchIn& in = e->min;
-  const unsigned n = e->M, gs = in.gpu_slots ? in.gpu_slots : 1u, ds = in.disk_slots ? in.disk_slots : 1u, na = in.o_attr ? in.n_attr : 0u;
-  const unsigned ns = churn_staged_scalars(in);
-  out->n = n, out->gpu_slots = gs, out->disk_slots = ds, out->n_attr_keys = na, out->n_scalars = ns;
+  const OfferCols<false> staged = offer_cols_of(in);
+  OfferDims d = offer_dims(in);
+  if (!staged.attr) d.n_attr = 0;
+  const unsigned n = e->M;
+  out->n = n, out->gpu_slots = d.gpu_slots, out->disk_slots = d.disk_slots, out->n_attr_keys = d.n_attr, out->n_scalars = churn_staged_scalars(in);
   if (out->cap < n) e->fail(COOK_E_INVALID, "cook_cycle_fetch_offers: cap is smaller than the staged offers' row count (see n)");
   bool copied = false;
-  auto col = [&](auto* dst, const auto* staged, size_t width, auto none) {
-    if (!dst || !n || !width) return;
-    if (staged) {
-      copy_async(e, dst, staged, (size_t)n * width * sizeof(*dst), hipMemcpyDeviceToHost);
+  offer_columns([&](const auto& col) {
+    auto* dst = col.of(*out);
+    const size_t cells = (size_t)n * d.width(col.kind);
+    if (!dst || !cells) return;
+    if (const auto* src = col.col(staged)) {
+      copy_async(e, dst, src, cells * sizeof(*dst), hipMemcpyDeviceToHost);
       copied = true;
     } else {
-      std::fill(dst, dst + (size_t)n * width, none);
+      std::fill(dst, dst + cells, col.none);  // what a NULL column means
     }
-  };
-  col(out->cpus, in.o_cpus, 1, 0.0), col(out->mem, in.o_mem, 1, 0.0), col(out->host, in.o_host, 1, (uint32_t)0u);
-  col(out->k8s, in.o_k8s, 1, (uint8_t)0u);
-  col(out->gpu_model, in.o_gpu_model, gs, (uint32_t)0u), col(out->gpu_count, in.o_gpu_count, gs, 0.0);
-  col(out->disk_type, in.o_disk_type, ds, (uint32_t)0u), col(out->disk_space, in.o_disk_space, ds, 0.0);
-  col(out->attr, in.o_attr, na, (uint32_t)0u);
-  col(out->max_tasks, in.o_max_tasks, 1, (int32_t)-1), col(out->num_tasks, in.o_num_tasks, 1, (int32_t)0);
-  col(out->location, in.o_location, 1, (uint32_t)0u), col(out->host_start_s, in.o_host_start, 1, (int64_t)-1);
-  col(out->run_cpus, in.o_run_cpus, 1, 0.0), col(out->run_mem, in.o_run_mem, 1, 0.0), col(out->run_count, in.o_run_count, 1, (int32_t)0);
-  col(out->ports, in.o_ports, 1, (int32_t)0);
-  if (out->scalars)
-    for (unsigned s = 0; s < ns; ++s) col(out->scalars + (size_t)s * n, in.o_scal[s], 1, 0.0);
+  });
   if (copied) sync(e);
 }

@@ -9,31 +9,19 @@
 // The order rule: old rows keep their relative order; join i lands directly in front of its anchor's OLD position, joins of one anchor
 // in list order (keys -> the STABLE radix passes -> carry_seg_bounds), whether or not the anchor itself leaves.
 #pragma once
-#include <type_traits>
-
+#include "offer_table.hpp"
 #include "release_kernels.hpp"
 
 // word of QueueBufs::counters behind the release's: leave_host entries that have no row
 constexpr unsigned CHURN_CNT_MISSING = 5;
 static_assert(CHURN_CNT_MISSING > REL_CNT_MISSING && CHURN_CNT_MISSING < REL_CNT_WORDS, "the churn's counter lies behind the release's");
 
-// every column of an offer table ([rows] each; gpu_* [rows][gpu_slots], disk_* [rows][disk_slots], attr [rows][n_attr]); null: the
-// table has no such column.  W: the set the gather writes
-template <bool W>
-struct ChurnColsT {
-  template <class T>
-  using P = std::conditional_t<W, T*, const T*>;
-  P<double> cpus, mem, run_cpus, run_mem, scal[3], gpu_count, disk_space;
-  P<uint32_t> host, gpu_model, disk_type, attr, location;
-  P<uint8_t> k8s;
-  P<int32_t> max_tasks, num_tasks, run_count, ports;
-  P<int64_t> host_start;
-};
 // the gather's arguments (by pointer: three column sets do not fit a batched kernel's argument block)
 struct ChurnGather {
-  ChurnColsT<false> old, join;
-  ChurnColsT<true> out;
-  unsigned M_old, n_join, M_new, gpu_slots, disk_slots, n_attr;
+  OfferCols<false> old, join;
+  OfferCols<true> out;
+  unsigned M_old, n_join, M_new;
+  OfferDims dims;
 };
 
 // host id -> row of the OLD table or M (none): through the release's host-indexed table, or (h2row null: the greatest host id is far
@@ -106,33 +94,16 @@ static __device__ __forceinline__ void churn_move(T* __restrict__ out, const T* 
   for (unsigned x = 0; x < width; ++x) out[(size_t)d * width + x] = col ? col[row * width + x] : none;
 }
 
-// One thread per NEW row: every column the new table has moves with its row.  A column the source lacks (the joins' list may leave
-// out what the staged table has) gives the value a NULL column means for every row (the loads of match_kernels.hpp): 0, but -1 for
-// max_tasks (no limit) and host_start (absent).  src is 0xFF-filled beforehand: a row nobody claimed is left alone.
+// One thread per NEW row: every column the new table has (offer_columns) moves with its row.  A column the source lacks (the joins'
+// list may leave out what the staged table has) gives the value a NULL column means for every row, the list's `none`.  src is
+// 0xFF-filled beforehand: a row nobody claimed is left alone.
 COOK_KERNEL void churn_gather(const ChurnGather* __restrict__ gp, const uint32_t* __restrict__ src) {
   const unsigned d = blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned M_old = gp->M_old;
   if (d >= gp->M_new) return;
   const unsigned s = src[d];
   if (s >= M_old + gp->n_join) return;
-  const ChurnColsT<false>&o = gp->old, &j = gp->join;
-  const ChurnColsT<true>& w = gp->out;
-  churn_move(w.cpus, o.cpus, j.cpus, 1u, d, s, M_old, 0.0);
-  churn_move(w.mem, o.mem, j.mem, 1u, d, s, M_old, 0.0);
-  churn_move(w.host, o.host, j.host, 1u, d, s, M_old, (uint32_t)0u);
-  churn_move(w.k8s, o.k8s, j.k8s, 1u, d, s, M_old, (uint8_t)0u);
-  churn_move(w.gpu_model, o.gpu_model, j.gpu_model, gp->gpu_slots, d, s, M_old, (uint32_t)0u);
-  churn_move(w.gpu_count, o.gpu_count, j.gpu_count, gp->gpu_slots, d, s, M_old, 0.0);
-  churn_move(w.disk_type, o.disk_type, j.disk_type, gp->disk_slots, d, s, M_old, (uint32_t)0u);
-  churn_move(w.disk_space, o.disk_space, j.disk_space, gp->disk_slots, d, s, M_old, 0.0);
-  churn_move(w.attr, o.attr, j.attr, gp->n_attr, d, s, M_old, (uint32_t)0u);
-  churn_move(w.max_tasks, o.max_tasks, j.max_tasks, 1u, d, s, M_old, (int32_t)-1);
-  churn_move(w.num_tasks, o.num_tasks, j.num_tasks, 1u, d, s, M_old, (int32_t)0);
-  churn_move(w.location, o.location, j.location, 1u, d, s, M_old, (uint32_t)0u);
-  churn_move(w.host_start, o.host_start, j.host_start, 1u, d, s, M_old, (int64_t)-1);
-  churn_move(w.run_cpus, o.run_cpus, j.run_cpus, 1u, d, s, M_old, 0.0);
-  churn_move(w.run_mem, o.run_mem, j.run_mem, 1u, d, s, M_old, 0.0);
-  churn_move(w.run_count, o.run_count, j.run_count, 1u, d, s, M_old, (int32_t)0);
-  churn_move(w.ports, o.ports, j.ports, 1u, d, s, M_old, (int32_t)0);
-  for (unsigned x = 0; x < 3u; ++x) churn_move(w.scal[x], o.scal[x], j.scal[x], 1u, d, s, M_old, 0.0);
+  offer_columns([&](const auto& col) {
+    churn_move(col.col(gp->out), col.col(gp->old), col.col(gp->join), gp->dims.width(col.kind), d, s, M_old, col.none);
+  });
 }

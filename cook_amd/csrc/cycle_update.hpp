@@ -185,100 +185,46 @@ static void pinned_reserve(void** p, size_t* cap, size_t bytes) {
 
 // the offers of a delta: every column the host gave into one block, one copy, used where it lands.  Two steps so that
 // cook_cycle_update stays all-or-nothing: offers_block_plan validates the struct and reserves every byte the staging needs (it may
-// refuse or fail; nothing resident has been touched), offers_block_commit copies and points the match at the new block.
-struct OffersPlan {
-  size_t off[32];
-  unsigned gs, ds, n_attr;
-};
-template <class W>
-static void offers_block_layout(W& w, const cook_offers* o, OffersPlan& pl) {
-  const unsigned M = o->n;
-  int k = 0;
-  pl.off[k++] = w.put(o->cpus, M);
-  pl.off[k++] = w.put(o->mem, M);
-  pl.off[k++] = w.put(o->host, M);
-  pl.off[k++] = w.put(o->k8s, M);
-  pl.off[k++] = w.put(o->gpu_model, (size_t)M * pl.gs);
-  pl.off[k++] = w.put(o->gpu_count, (size_t)M * pl.gs);
-  pl.off[k++] = w.put(o->disk_type, (size_t)M * pl.ds);
-  pl.off[k++] = w.put(o->disk_space, (size_t)M * pl.ds);
-  pl.off[k++] = w.put(o->ports, M);
-  for (unsigned sc = 0; sc < COOK_MAX_SCALARS; ++sc)
-    pl.off[k++] = w.put((o->scalars && sc < o->n_scalars) ? o->scalars + (size_t)sc * M : (const double*)nullptr, M);
-  pl.off[k++] = w.put(o->attr, (size_t)M * pl.n_attr);
-  pl.off[k++] = w.put(o->max_tasks, M);
-  pl.off[k++] = w.put(o->num_tasks, M);
-  pl.off[k++] = w.put(o->location, M);
-  pl.off[k++] = w.put(o->host_start_s, M);
-  pl.off[k++] = w.put(o->run_cpus, M);
-  pl.off[k++] = w.put(o->run_mem, M);
-  pl.off[k++] = w.put(o->run_count, M);
+// refuse or fail; nothing resident has been touched), offers_block_commit copies and points the match at the new block.  The block's
+// layout is offer_columns' order, each column 16-byte aligned (BlockWriter::put); the plan is the widths the struct was checked at.
+// every column of offer_columns the host gave, into the block behind `w`; with `dev` (where the block lands on the device) also
+// -> the columns there.  The one loop of both steps: what the plan measured is what the commit writes
+static OfferCols<false> offers_block_layout(BlockWriter& w, const cook_offers* o, const OfferDims& d, const char* dev) {
+  OfferCols<false> c{};
+  offer_columns([&](const auto& col) {
+    const auto* given = col.of(*o);
+    const size_t at = w.put(given, (size_t)o->n * d.width(col.kind));
+    if (dev && given) col.col(c) = (decltype(given))(dev + at);
+  });
+  return c;
 }
-OffersPlan offers_block_plan(cook_engine* e, UpdateBufs& ub, const cook_offers* o) {
+OfferDims offers_block_plan(cook_engine* e, UpdateBufs& ub, const cook_offers* o) {
   const unsigned M = o->n;
   if (M && (!o->cpus || !o->mem || !o->host)) e->fail(COOK_E_INVALID, "cook_match_stage: offers need cpus, mem and host");
   if (o->scalars && o->n_scalars > COOK_MAX_SCALARS) e->fail(COOK_E_INVALID, "cook_match_stage: more than COOK_MAX_SCALARS named scalars");
-  OffersPlan pl{};
-  pl.gs = res_slots(e, o->gpu_slots, "cook_match_stage: gpu_slots");
-  pl.ds = res_slots(e, o->disk_slots, "cook_match_stage: disk_slots");
+  OfferDims d{};
+  d.gpu_slots = res_slots(e, o->gpu_slots, "cook_match_stage: gpu_slots");
+  d.disk_slots = res_slots(e, o->disk_slots, "cook_match_stage: disk_slots");
   if (o->gpu_model && !o->gpu_count) e->fail(COOK_E_INVALID, "cook_match_stage: gpu_model without gpu_count");
   if (o->disk_type && !o->disk_space) e->fail(COOK_E_INVALID, "cook_match_stage: disk_type without disk_space");
   match_check_offer_count(e, M);  // the walk's owner table holds one byte per offer of the pool
-  pl.n_attr = o->attr ? o->n_attr_keys : 0;
+  d.n_attr = o->attr ? o->n_attr_keys : 0;
   BlockWriter w(nullptr);
-  offers_block_layout(w, o, pl);
+  offers_block_layout(w, o, d, nullptr);
   pinned_reserve(&ub.h_offers, &ub.h_offers_cap, w.used + 16);
   ub.d_offers[ub.d_offers_cur ^ 1].ensure(w.used + 16);
-  return pl;
+  return d;
 }
-void offers_block_commit(cook_engine* e, UpdateBufs& ub, const cook_offers* o, OffersPlan& pl) {
-  MatchIn& in = e->min;
+void offers_block_commit(cook_engine* e, UpdateBufs& ub, const cook_offers* o, const OfferDims& d) {
   const unsigned M = o->n;
   DBuf& blk = ub.d_offers[ub.d_offers_cur ^ 1];
   BlockWriter w((char*)ub.h_offers);
-  offers_block_layout(w, o, pl);
+  const OfferCols<false> c = offers_block_layout(w, o, d, (const char*)blk.p);
   block_to_device(e, blk.p, ub.h_offers, w.used);
   ub.d_offers_cur ^= 1;
-  const char* d = (const char*)blk.p;
-  const size_t* off = pl.off;
-  const unsigned gs = pl.gs, ds = pl.ds, n_attr = pl.n_attr;
-  auto at = [&](size_t o_) -> const void* { return o_ == (size_t)-1 ? nullptr : (const void*)(d + o_); };
-  int k = 0;
-  in.M = M;
+  offer_cols_stage(e->min, c, d, M);
   e->M = M;
-  in.o_cpus = (const double*)at(off[k++]);
-  in.o_mem = (const double*)at(off[k++]);
-  in.o_host = (const uint32_t*)at(off[k++]);
-  in.o_k8s = (const uint8_t*)at(off[k++]);
-  in.gpu_slots = gs;
-  in.disk_slots = ds;
-  in.o_gpu_model = (const uint32_t*)at(off[k++]);
-  in.o_gpu_count = (const double*)at(off[k++]);
-  in.o_disk_type = (const uint32_t*)at(off[k++]);
-  in.o_disk_space = (const double*)at(off[k++]);
-  in.o_ports = (const int32_t*)at(off[k++]);
-  for (unsigned sc = 0; sc < COOK_MAX_SCALARS; ++sc) in.o_scal[sc] = (const double*)at(off[k++]);
-  in.n_attr = n_attr;
-  in.o_attr = (const uint32_t*)at(off[k++]);
-  in.o_max_tasks = (const int32_t*)at(off[k++]);
-  in.o_num_tasks = (const int32_t*)at(off[k++]);
-  in.o_location = (const uint32_t*)at(off[k++]);
-  in.o_host_start = (const int64_t*)at(off[k++]);
-  in.o_run_cpus = (const double*)at(off[k++]);
-  in.o_run_mem = (const double*)at(off[k++]);
-  in.o_run_count = (const int32_t*)at(off[k++]);
-  in.host_dup = 0;
-  e->cf_max_host = 0xFFFFFFFFu;
-  e->o_hosts.clear();
-  e->o_run_cols_made = false;
-  e->o_hosts_known = true;
-  if (M) {  // two offers on one host?
-    std::vector<uint32_t> hs(o->host, o->host + M);
-    std::sort(hs.begin(), hs.end());
-    in.host_dup = std::adjacent_find(hs.begin(), hs.end()) != hs.end() ? 1u : 0u;
-    e->cf_max_host = hs.back();  // (the class-ordered walk's and the release's host tables are sized by it)
-    e->o_hosts = std::move(hs);  // (the mirror a host churn is checked against)
-  }
+  offers_note_hosts(e, o->host, M, true);
 }
 
 void cycle_update(cook_engine* e, UpdateBufs& ub, const cook_cycle_delta* d) {
@@ -337,7 +283,7 @@ void cycle_update(cook_engine* e, UpdateBufs& ub, const cook_cycle_delta* d) {
   if (p_add && in.j_novel_off) csr_ok(aj->novel_off, aj->novel_host, aj->novel_host, "cook_cycle_update: add_pending novel_off must start at 0 and not decrease, with novel_host behind it");
   // the fresh offers are checked, and everything their staging needs is reserved, BEFORE anything resident changes: a refused
   // offers struct (or an allocation that fails) leaves tasks, jobs and offers as they were
-  OffersPlan offers_plan{};
+  OfferDims offers_plan{};
   if (d->offers) offers_plan = offers_block_plan(e, ub, d->offers);
   const unsigned N2 = N - d->n_remove + n_add;  // (when the removal list is valid; the device says at the end)
   const unsigned N_hi = N + n_add;              // rows the compaction can write whatever the list holds (an entry named twice removes one row)

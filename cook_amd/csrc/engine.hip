@@ -42,7 +42,8 @@
 
 namespace {
 
-#include "device_buf.hpp"  // ahead of the engine: its members are DArr
+#include "device_buf.hpp"   // ahead of the engine: its members are DArr
+#include "offer_table.hpp"  // ... and an OfferStore
 
 struct KernelStat {
   double ms = 0;
@@ -136,15 +137,15 @@ struct cook_engine {
   // ---- match state ----
   bool match_staged = false;
   unsigned K = 0, M = 0, G = 0, Kjobs = 0;
-  DArr<double> j_scal[3], o_scal[3], m_xscal;
-  DArr<int32_t> j_ports, o_ports, m_xports;
-  DArr<double> j_cpus, j_mem, j_gpus, j_disk_req, o_cpus, o_mem, o_gpu_count, o_disk_space, o_run_cpus, o_run_mem, m_ac, m_am;
+  OfferStore offers;  // the offer columns a stage uploads (match_stage_offers)
+  DArr<double> j_scal[3], m_xscal;
+  DArr<int32_t> j_ports, m_xports;
+  DArr<double> j_cpus, j_mem, j_gpus, j_disk_req, m_ac, m_am;
   DArr<uint32_t> j_gpu_model, j_group, j_eq_off, j_eq_key, j_eq_val, j_novel_off, j_novel_host, j_ckpt, j_disk_type, j_index,
-      o_host, o_gpu_model, o_disk_type, o_attr, o_location, g_attr_key, g_run_off, g_run_host, g_run_attr, reserved_bits,
-      m_fail;
-  DArr<int32_t> j_reserved_host, o_max_tasks, o_num_tasks, o_run_count, g_min, m_acount, m_group_last, m_job_prev, m_j2o;
-  DArr<int64_t> j_est_end, o_host_start;
-  DArr<uint8_t> o_k8s, g_type;
+      g_attr_key, g_run_off, g_run_host, g_run_attr, reserved_bits, m_fail;
+  DArr<int32_t> j_reserved_host, g_min, m_acount, m_group_last, m_job_prev, m_j2o;
+  DArr<int64_t> j_est_end;
+  DArr<uint8_t> g_type;
   DArr<unsigned> m_summary;
   DArr<OfferA> v_oa;
   DArr<OfferB> v_ob;

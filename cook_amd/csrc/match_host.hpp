@@ -24,53 +24,44 @@ unsigned res_slots(cook_engine* e, uint32_t slots, const char* what) {
 // =================================================================================================================
 // MATCH
 // =================================================================================================================
-// the offer columns of a staged match (cook_match_stage / cook_cycle_stage / cook_cycle_update)
+// What the host keeps of a freshly staged offer table's host column, for both staging routes (match_stage_offers, cycle_update.hpp's
+// offers_block_commit): two offers on one host?, the greatest host id (the class-ordered walk's and the release's host tables are sized
+// by it), and the ascending mirror a host churn is checked against.  on_host false: the column is on the device, nothing is known
+void offers_note_hosts(cook_engine* e, const uint32_t* host, unsigned M, bool on_host) {
+  e->min.host_dup = 0;
+  e->cf_max_host = 0xFFFFFFFFu;
+  e->o_hosts.clear();
+  e->o_run_cols_made = false;
+  e->o_hosts_known = on_host;
+  if (!on_host || !M) return;
+  std::vector<uint32_t> hs(host, host + M);
+  std::sort(hs.begin(), hs.end());
+  e->min.host_dup = std::adjacent_find(hs.begin(), hs.end()) != hs.end() ? 1u : 0u;
+  e->cf_max_host = hs.back();
+  e->o_hosts = std::move(hs);
+}
+
+// the offer columns of a staged match (cook_match_stage / cook_cycle_stage; cook_cycle_update's come in one block: cycle_update.hpp): every
+// column of offer_columns, a device pointer used in place, a host column uploaded into the engine's OfferStore
 void match_stage_offers(cook_engine* e, const cook_offers* o, bool offers_dev) {
   MatchIn& in = e->min;
   const unsigned M = o->n;
   if (M && (!o->cpus || !o->mem || !o->host)) e->fail(COOK_E_INVALID, "cook_match_stage: offers need cpus, mem and host");
-  in.M = M;
-  e->M = M;
-  in.o_cpus = (offers_dev ? o->cpus : h2d_opt(e, e->o_cpus, o->cpus, M));
-  in.o_mem = (offers_dev ? o->mem : h2d_opt(e, e->o_mem, o->mem, M));
-  in.o_host = (offers_dev ? o->host : h2d_opt(e, e->o_host, o->host, M));
-  in.o_k8s = (offers_dev ? o->k8s : h2d_opt(e, e->o_k8s, o->k8s, M));
-  in.gpu_slots = res_slots(e, o->gpu_slots, "cook_match_stage: gpu_slots");
-  in.disk_slots = res_slots(e, o->disk_slots, "cook_match_stage: disk_slots");
-  in.o_gpu_model = (offers_dev ? o->gpu_model : h2d_opt(e, e->o_gpu_model, o->gpu_model, (size_t)M * in.gpu_slots));
-  in.o_gpu_count = (offers_dev ? o->gpu_count : h2d_opt(e, e->o_gpu_count, o->gpu_count, (size_t)M * in.gpu_slots));
-  if (in.o_gpu_model && !in.o_gpu_count) e->fail(COOK_E_INVALID, "cook_match_stage: gpu_model without gpu_count");
-  in.o_disk_type = (offers_dev ? o->disk_type : h2d_opt(e, e->o_disk_type, o->disk_type, (size_t)M * in.disk_slots));
-  in.o_disk_space = (offers_dev ? o->disk_space : h2d_opt(e, e->o_disk_space, o->disk_space, (size_t)M * in.disk_slots));
+  OfferDims d{};
+  d.gpu_slots = res_slots(e, o->gpu_slots, "cook_match_stage: gpu_slots");
+  d.disk_slots = res_slots(e, o->disk_slots, "cook_match_stage: disk_slots");
+  d.n_attr = o->attr ? o->n_attr_keys : 0;
+  if (o->gpu_model && !o->gpu_count) e->fail(COOK_E_INVALID, "cook_match_stage: gpu_model without gpu_count");
   // ports / named scalars of the leases (offer.clj:57-73); jobs' names beyond the offers' columns find a total of 0
   if (o->scalars && o->n_scalars > COOK_MAX_SCALARS) e->fail(COOK_E_INVALID, "cook_match_stage: more than COOK_MAX_SCALARS named scalars");
-  in.o_ports = (offers_dev ? o->ports : h2d_opt(e, e->o_ports, o->ports, M));
-  for (unsigned sc = 0; sc < COOK_MAX_SCALARS; ++sc) {
-    const double* col = (o->scalars && sc < o->n_scalars) ? o->scalars + (size_t)sc * M : nullptr;
-    in.o_scal[sc] = (offers_dev ? col : h2d_opt(e, e->o_scal[sc], col, M));
-  }
-  in.n_attr = o->attr ? o->n_attr_keys : 0;
-  in.o_attr = (offers_dev ? o->attr : h2d_opt(e, e->o_attr, o->attr, (size_t)M * in.n_attr));
-  in.o_max_tasks = (offers_dev ? o->max_tasks : h2d_opt(e, e->o_max_tasks, o->max_tasks, M));
-  in.o_num_tasks = (offers_dev ? o->num_tasks : h2d_opt(e, e->o_num_tasks, o->num_tasks, M));
-  in.o_location = (offers_dev ? o->location : h2d_opt(e, e->o_location, o->location, M));
-  in.o_host_start = (offers_dev ? o->host_start_s : h2d_opt(e, e->o_host_start, o->host_start_s, M));
-  in.o_run_cpus = (offers_dev ? o->run_cpus : h2d_opt(e, e->o_run_cpus, o->run_cpus, M));
-  in.o_run_mem = (offers_dev ? o->run_mem : h2d_opt(e, e->o_run_mem, o->run_mem, M));
-  in.o_run_count = (offers_dev ? o->run_count : h2d_opt(e, e->o_run_count, o->run_count, M));
-  // two offers on one host?  (offers built on the device are one per node: never)
-  in.host_dup = 0;
-  e->cf_max_host = 0xFFFFFFFFu;
-  e->o_hosts.clear();
-  e->o_run_cols_made = false;
-  e->o_hosts_known = !offers_dev;
-  if (!offers_dev && M) {
-    std::vector<uint32_t> hs(o->host, o->host + M);
-    std::sort(hs.begin(), hs.end());
-    in.host_dup = std::adjacent_find(hs.begin(), hs.end()) != hs.end() ? 1u : 0u;
-    e->cf_max_host = hs.back();
-    e->o_hosts = std::move(hs);  // (the mirror a host churn is checked against)
-  }
+  OfferCols<false> c{};
+  offer_columns([&](const auto& col) {
+    const auto* given = col.of(*o);
+    col.col(c) = offers_dev ? given : h2d_opt(e, col.col(e->offers), given, (size_t)M * d.width(col.kind));
+  });
+  offer_cols_stage(in, c, d, M);
+  e->M = M;
+  offers_note_hosts(e, o->host, M, !offers_dev);  // (offers built on the device are one per node: no two on one host)
 }
 void match_stage_offers(cook_engine* e, const cook_offers* o) {
   match_stage_offers(e, o, false);

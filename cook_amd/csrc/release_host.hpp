@@ -123,11 +123,11 @@ void release_enqueue(cook_engine* e, const cook_finished* f, unsigned* cnt, bool
     // behind a carry of this advance: its fresh set, in place (one wave owns one row); else a fresh set of its own, every row written
     CarryOfferIn ci;
     CarryOfferCols co;
-    carry_offer_cols(in, M, cy.cols[carried ? cy.cur : (cy.cur ^ 1u)], ci, co);
+    const OfferCols<true> out = carry_offer_cols(in, M, cy.cols[carried ? cy.cur : (cy.cur ^ 1u)], ci, co);
     KM<fold_offers<true>, FOLD_OT>(e, "release_fold_offers", M, perm, (const uint32_t*)b.o.start.ptr(), (const uint32_t*)b.o.end.ptr(), M,
         carried ? 0u : 1u, rows, ci, co, cnt + REL_CNT_CLAMPED);
     if (!carried) cy.cur ^= 1u;
-    carry_stage_cols(in, co);
+    offer_cols_stage(in, out, offer_dims(in), M, true);
   }
   // ---- the users and the pool ----------------------------------------------------------------------------------------------------------
   if (usage) {

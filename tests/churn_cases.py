@@ -626,6 +626,77 @@ def check_fetch(make_engine, *, scale=0.5):
             assert np.array_equal(S.fetch(e, False).j2o, want[c].j2o)
 
 
+def distinct_table(slots, n=3, *, bare=False, first=0):
+    """n rows whose values differ from column to column among the columns of one element type, and from row to row: two columns (or two
+    named scalars, or two map entries) that change places show in a fetch.  Host ids do not ascend.  bare: cpus, mem and host alone"""
+    counters = {np.float64: first, np.uint32: first, np.int32: first, np.int64: first}
+
+    def take(dt, *shape, start, step):
+        k = int(np.prod(shape))
+        c = counters[dt]
+        counters[dt] = c + k
+        return (start + step * (c + np.arange(k))).astype(dt).reshape(shape)
+    f64 = lambda *shape: take(np.float64, *shape, start=1.5, step=0.25)
+    u32 = lambda *shape: take(np.uint32, *shape, start=11, step=1)
+    i32 = lambda *shape: take(np.int32, *shape, start=3, step=1)
+    d = dict(cpus=f64(n), mem=f64(n), host=np.roll(u32(n), 1))
+    if not bare:
+        d.update(k8s=(np.arange(n) % 3).astype(np.uint8)[::-1].copy(), gpu_model=u32(n, slots), gpu_count=f64(n, slots), disk_type=u32(n, slots),
+                 disk_space=f64(n, slots), attr=u32(n, 3), max_tasks=i32(n), num_tasks=i32(n), location=u32(n),
+                 host_start_s=take(np.int64, n, start=100_000, step=7), run_cpus=f64(n), run_mem=f64(n), run_count=i32(n), ports=i32(n),
+                 scalars=f64(n, 3))
+    t = A.Offers(**d)
+    for dt in counters:  # the property the case rests on, on the table itself
+        vals = np.concatenate([np.asarray(getattr(t, c)).ravel() for c in H.COLS if getattr(t, c) is not None and np.asarray(getattr(t, c)).dtype == dt] or [np.zeros(0, dt)])
+        assert len(np.unique(vals)) == len(vals), dt
+    assert n < 2 or not (np.diff(t.host.astype(np.int64)) > 0).all()
+    return t
+
+
+def check_fetch_routes(make_engine):
+    """Every route that stages an offer table stages every column where the fetch (and so the next match) reads it: a table of pairwise
+    distinct values comes back as it went in — through cook_match_stage, cook_cycle_stage, cook_cycle_update over another table,
+    cook_cycle_run_queue's step->offers, and a churn that joins all of its rows while the one old row leaves.  The same with cpus, mem
+    and host alone: every other column reads as what NULL means, attr and scalars are absent."""
+    params = P1()
+    for slots, bare in ((1, False), (4, False), (1, True)):
+        t = distinct_table(slots, bare=bare)
+        other = distinct_table(5 - slots, n=2, bare=not bare, first=200)  # (update, step->offers: what was staged before)
+        old = distinct_table(slots, n=1, bare=bare, first=400)             # (the churn: the row that leaves; the columns of t)
+        pool = X.tiny_pool(2, t)
+
+        def stage(e, offers):
+            e.cycle_stage(pool.tasks, pool.users, pool.pending_jobs, offers, None)
+
+        def by_update(e):
+            stage(e, other)
+            e.cycle_update(offers=t)
+
+        def by_queue_step(e):
+            stage(e, other)
+            e.cycle_run(1)
+            e.cycle_run_queue(1, offers=t)
+
+        def by_churn(e):
+            stage(e, old)
+            e.cycle_run(1)
+            e.cycle_run_queue_hosts(1, None, None, A.HostChurn(leave=[int(old.host[0])], join=t))
+            assert e.churn_info() == dict(left=1, leave_missing=0, joined=3, n_offers=3)
+        routes = dict(match_stage=lambda e: e.match_stage(pool.pending_jobs, t), cycle_stage=lambda e: stage(e, t), cycle_update=by_update,
+                      queue_step=by_queue_step, churn=by_churn)
+        for name, route in routes.items():
+            where = f"{name} x{slots}{' bare' if bare else ''}:"
+            with make_engine(params) as e:
+                route(e)
+                f = e.fetch_offers().offers()
+            same_table(f, t, where)
+            if bare:
+                assert f.attr is None and f.scalars is None, where
+                assert f.max_tasks.tolist() == [-1] * 3 and f.host_start_s.tolist() == [-1] * 3, where
+                for c in ("k8s", "gpu_model", "gpu_count", "disk_type", "disk_space", "num_tasks", "location", "run_cpus", "run_mem", "run_count", "ports"):
+                    assert not np.asarray(getattr(f, c)).any(), (where, c)
+
+
 # ---- 11: ABI -------------------------------------------------------------------------------------------------------------------------------
 def struct_layout_sources():
     structs = [("cook_host_churn", A.CookHostChurn), ("cook_churn_info", A.CookChurnInfo), ("cook_offer_rows", A.CookOfferRows)]

@@ -74,3 +74,7 @@ def test_churn_built_offers(make_engine):
 
 def test_fetch_offers(make_engine):
     X.check_fetch(make_engine)
+
+
+def test_fetch_offers_by_every_route(make_engine):
+    X.check_fetch_routes(make_engine)

@@ -82,6 +82,10 @@ def test_fetch_offers(make_engine):
     X.check_fetch(make_engine)
 
 
+def test_fetch_offers_by_every_route(make_engine):
+    X.check_fetch_routes(make_engine)
+
+
 def test_churn_guarded_run():
     """every other test of this file once more in a process of its own with every device buffer between two guard bands (COOK_GUARD=1
     is read when the library is loaded): all pass, and no write outside a buffer is reported"""
