@@ -660,6 +660,76 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleFetchReservations(JNIEnv* env, 
   *n = (jint)got;
   return rc;
 }
+/* the launch-rate limiters the engine keeps from here on (cook_cycle_set_limiters): cols = {per_minute double[n], bucket int64[n],
+ * tokens int64[n], last_update_ms int64[n]} as direct buffers, user = direct buffer of n uint32 or null (entry i is user i);
+ * drop != 0: cook_cycle_set_limiters(NULL), everything else ignored */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleSetLimiters(JNIEnv* env, jclass c, jlong h, jint n, jobject user, jobjectArray cols, jint drop) {
+  int bad = 0;
+  const jint nn = n > 0 ? n : 0;
+  cook_limiters l;
+  (void)c;
+  if (drop) return cook_cycle_set_limiters(H(h), 0);
+  l.n = (uint32_t)nn;
+  l.user = BUFN(const uint32_t, user, nn);
+  l.per_minute = EL(const double, cols, 0, nn);
+  l.bucket = EL(const int64_t, cols, 1, nn);
+  l.tokens = EL(const int64_t, cols, 2, nn);
+  l.last_update_ms = EL(const int64_t, cols, 3, nn);
+  if (bad) return COOK_E_INVALID;
+  return cook_cycle_set_limiters(H(h), &l);
+}
+/* the time of the NEXT cycle (cook_cycle_set_clock); has_clock == 0: none */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleSetClock(JNIEnv* env, jclass c, jlong h, jint has_clock, jlong now_ms, jlong spend_ms) {
+  cook_clock ck;
+  (void)env;
+  (void)c;
+  ck.now_ms = (int64_t)now_ms;
+  ck.spend_ms = (int64_t)spend_ms;
+  return cook_cycle_set_clock(H(h), has_clock ? &ck : 0);
+}
+/* the last cycle's kept placements spend now (cook_cycle_limiters_spend): offer_skipped = direct buffer of n_last_offers uint8, or null */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleLimitersSpend(JNIEnv* env, jclass c, jlong h, jint n_last_offers, jobject offer_skipped,
+                                                               jlong spend_ms) {
+  int bad = 0;
+  const jint nl = n_last_offers > 0 ? n_last_offers : 0;
+  const uint8_t* sk = BUFN(const uint8_t, offer_skipped, nl);
+  (void)c;
+  if (bad) return COOK_E_INVALID;
+  return cook_cycle_limiters_spend(H(h), sk, (uint32_t)nl, (int64_t)spend_ms);
+}
+/* the limiters' state (cook_cycle_fetch_limiters): tokens_out / last_out / until_out = direct buffers of n_users int64 each (null: skipped);
+ * n_users must be the user count the limiters were installed for: the engine writes that many */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleFetchLimiters(JNIEnv* env, jclass c, jlong h, jint n_users, jobject tokens_out, jobject last_out,
+                                                               jobject until_out) {
+  int bad = 0;
+  const jint nu = n_users > 0 ? n_users : 0;
+  int64_t* tokens = BUFN(int64_t, tokens_out, nu);
+  int64_t* last = BUFN(int64_t, last_out, nu);
+  int64_t* until = BUFN(int64_t, until_out, nu);
+  (void)c;
+  if (bad) return COOK_E_INVALID;
+  return cook_cycle_fetch_limiters(H(h), tokens, last, until);
+}
+/* the rate-limit stage's per-user counts of the last cycle (cook_cycle_fetch_rate_limit): direct buffers of n_users uint32 each (null: skipped);
+ * n_users must be the staged user state's count */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleFetchRateLimit(JNIEnv* env, jclass c, jlong h, jint n_users, jobject rate_limited_out,
+                                                                jobject passed_out) {
+  int bad = 0;
+  const jint nu = n_users > 0 ? n_users : 0;
+  uint32_t* rl = BUFN(uint32_t, rate_limited_out, nu);
+  uint32_t* ps = BUFN(uint32_t, passed_out, nu);
+  (void)c;
+  if (bad) return COOK_E_INVALID;
+  return cook_cycle_fetch_rate_limit(H(h), rl, ps);
+}
+/* the limiters' counts of the last cycle (cook_cycle_limiter_info): info_out = direct buffer of one cook_limiter_info */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleLimiterInfo(JNIEnv* env, jclass c, jlong h, jobject info_out) {
+  int bad = 0;
+  cook_limiter_info* out = BUF(cook_limiter_info, info_out);
+  (void)c;
+  if (bad || !out) return COOK_E_INVALID;
+  return cook_cycle_limiter_info(H(h), out);
+}
 /* the running usage of n staged engines of one device in ONE call (cook_rank_pool_usage_multi): usage_out = direct buffer of n cook_usage */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_rankPoolUsageMulti(JNIEnv* env, jclass c, jobject handles /* direct buffer of n jlong */, jint n, jobject usage_out) {
   cook_engine* es[64];

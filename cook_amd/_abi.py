@@ -270,6 +270,41 @@ class Reservations:
         return st, (self.pending, self.host)
 
 
+class CookLimiters(C.Structure):  # cook_cycle_set_limiters
+    _fields_ = [("n", C.c_uint32), ("user", _u32p), ("per_minute", _f64p), ("bucket", _i64p), ("tokens", _i64p), ("last_update_ms", _i64p)]
+
+
+class CookClock(C.Structure):  # cook_cycle_set_clock
+    _fields_ = [("now_ms", C.c_int64), ("spend_ms", C.c_int64)]
+
+
+class CookLimiterInfo(C.Structure):  # cook_cycle_limiter_info
+    _fields_ = [("earned", C.c_uint32), ("spent_users", C.c_uint32), ("in_debt", C.c_uint32), ("reserved", C.c_uint32), ("spent", C.c_int64)]
+
+
+LimiterInfo = CookLimiterInfo
+
+
+class Limiters:
+    """The per-user-per-pool launch-rate limiters of cook_cycle_set_limiters (cook_limiters): per entry the tokens replenished per
+    minute, the bucket size, the current tokens and the time of the last update (ms).  user None: entry i is user i (the whole table);
+    else only the listed users' values are replaced (the host's flush! after a quota edit)."""
+
+    def __init__(self, per_minute, bucket, tokens, last_update_ms, user=None):
+        self.per_minute = _arr(per_minute, np.float64)
+        n = len(self.per_minute)
+        self.bucket, self.tokens, self.last_update_ms = _arr(bucket, np.int64, n), _arr(tokens, np.int64, n), _arr(last_update_ms, np.int64, n)
+        self.user = _arr(user, np.uint32, n) if user is not None else None
+
+    def as_struct(self):
+        """-> (CookLimiters, the objects its pointers refer to)"""
+        n = len(self.per_minute)
+        st = CookLimiters(n, _ptr(self.user, _u32p) if self.user is not None and n else _u32p(), _ptr(self.per_minute, _f64p) if n else _f64p(),
+                          _ptr(self.bucket, _i64p) if n else _i64p(), _ptr(self.tokens, _i64p) if n else _i64p(),
+                          _ptr(self.last_update_ms, _i64p) if n else _i64p())
+        return st, (self.user, self.per_minute, self.bucket, self.tokens, self.last_update_ms)
+
+
 class OfferRows:
     """Caller-allocated columns for cook_cycle_fetch_offers (cook_offer_rows): room for `cap` rows at the given widths; `skip` names
     columns that are passed as NULL.  After the call, offers() returns the fetched table as an Offers with every column."""

@@ -56,7 +56,7 @@ void cycle_autoscale(cook_engine* e, const cook_autoscale_params* p, uint32_t* t
     KM<as_compact_queue, 256>(e, "as_compact_queue", div_up(n, 256), (const int*)matched, (const SumI*)b.scan.ptr(), n, (const double*)c.q_cpus.ptr(),
         (const double*)c.q_mem.ptr(), (const double*)c.q_gpus.ptr(), (const uint32_t*)c.q_user.ptr(), b.a_cpus.ptr(), b.a_mem.ptr(), b.a_gpus.ptr(),
         b.a_user.ptr(), b.a_rpos.ptr());
-    cons_run_device(e, c, b.w, nq, b.a_cpus.ptr(), b.a_mem.ptr(), b.a_gpus.ptr(), b.a_user.ptr(), nullptr, N);
+    cons_run_device(e, c, b.w, nq, b.a_cpus.ptr(), b.a_mem.ptr(), b.a_gpus.ptr(), b.a_user.ptr(), nullptr, N, LIM_READ);
     n_cand = b.w.n_result;
   }
   // ---- Out: A without the host's excluded tasks, after the take (:1319) ------------------------------------------------------------------

@@ -19,7 +19,7 @@ struct QueueArgs {
 
 // where a queue cycle's advance lands its read-backs in h_scratch, in 64-bit words: the advance's two counters (1 word), the carry's
 // pool (4 doubles), the release's counters (REL_CNT_WORDS of 4 bytes) and its pool (4 doubles)
-constexpr unsigned Q_H_ADVANCE = 0, Q_H_CARRY_POOL = 1, REL_H_CNT = 8, REL_H_POOL = 12;  // (release_host.hpp asserts that they do not overlap)
+constexpr unsigned Q_H_ADVANCE = 0, Q_H_CARRY_POOL = 1, REL_H_CNT = 8, REL_H_POOL = 16;  // (release_host.hpp asserts that they do not overlap)
 
 // a queue cycle's table of the groups' cotasks takes the place of the one in use; the staged one is kept for the next rank
 void groups_install(cook_engine* e, const uint32_t* off, const uint32_t* host, const uint32_t* attr) {
@@ -145,7 +145,7 @@ bool carry_enqueue(cook_engine* e, const cook_queue_carry* c, const uint8_t* ski
   if (usage) {
     ConsBufs& cb = *e->cb;
     const uint32_t* perm = b.u.carry_segments(e, ukey, k, U);
-    int64_t* spend = (cb.has_tokens && !c->tokens_left) ? cb.tokens.ptr() : nullptr;
+    int64_t* spend = (cb.has_tokens && !c->tokens_left && !limiter_own(e)) ? cb.tokens.ptr() : nullptr;  // (limiters of the engine's own spend in limiter_enqueue)
     KM<fold_users<false, RowsSorted>, FOLD_UT>(e, "carry_fold_users", U, RowsSorted{perm, j}, (const uint32_t*)b.u.start.ptr(),
         (const uint32_t*)b.u.end.ptr(), U, cb.ucount.ptr(), cb.ucpus.ptr(), cb.umem.ptr(), cb.ugpus.ptr(), spend);
     if (cb.pool_usage_given) {

@@ -38,6 +38,7 @@ struct ConsBufs : ConsWork {  // the considerable pass's own work set, and the s
 void cons_stage_users(cook_engine* e, ConsBufs& c, const cook_user_state* us) {
   if (!us) e->fail(COOK_E_INVALID, "cook_considerable: null user state");
   const unsigned U = us->n;
+  limiter_check_user_state(e, us);  // (limiter_host.hpp: while the engine holds limiters, a tokens_left or another user count is refused)
   if (U && (!us->quota_count || !us->quota_cpus || !us->quota_mem || !us->quota_gpus || !us->usage_count || !us->usage_cpus ||
             !us->usage_mem || !us->usage_gpus))
     e->fail(COOK_E_INVALID, "cook_considerable: user quota / usage arrays are required");
@@ -62,10 +63,16 @@ void cons_stage_users(cook_engine* e, ConsBufs& c, const cook_user_state* us) {
 }
 
 // the filters under the staged user state s over a device-resident queue of n jobs; leaves the first min(K, survivors) queue positions
-// in c.result (c: s itself for the considerable pass, a work set of its own for cook_cycle_autoscale)
+// in c.result (c: s itself for the considerable pass, a work set of its own for cook_cycle_autoscale).  limiters: what the rate-limit
+// stage does with limiters the engine holds (limiter_host.hpp) — LIM_CYCLE: a cycle's filter, which consumes the staged clock, compares
+// with earn(now) and commits the earn of the users with a job at the stage; LIM_READ: the tokens as they stand, nobody earns
+// (cook_cycle_autoscale); LIM_NONE: the staged tokens_left (cook_considerable).  Without limiters all three are the same.
+enum LimUse { LIM_NONE, LIM_CYCLE, LIM_READ };
 void cons_run_device(cook_engine* e, const ConsBufs& s, ConsWork& c, unsigned n, const double* q_cpus, const double* q_mem,
-                     const double* q_gpus, const uint32_t* q_user, const uint8_t* q_elig, unsigned K) {
+                     const double* q_gpus, const uint32_t* q_user, const uint8_t* q_elig, unsigned K, LimUse limiters = LIM_NONE) {
   const unsigned U = s.U;
+  const LimView lim = limiters != LIM_NONE ? limiter_view(e, U, limiters == LIM_CYCLE) : LimView{};
+  const bool lim_commit = limiters == LIM_CYCLE && lim.tokens;
   c.rate_limited.ensure(std::max(1u, U));
   c.passed.ensure(std::max(1u, U));
   memset_async(e, c.rate_limited.ptr(), 0, (size_t)std::max(1u, U) * 4);
@@ -107,16 +114,19 @@ void cons_run_device(cook_engine* e, const ConsBufs& s, ConsWork& c, unsigned n,
       (const double*)s.qcount.ptr(), (const double*)s.qcpus.ptr(), (const double*)s.qmem.ptr(), (const double*)s.qgpus.ptr(), c.flag1.ptr());
   // ---- (ii) launch-rate limit: index of the job among its user's survivors (tools.clj:935-955) -----------------------------
   seg_scan<SumI>(e, "cons_user_index_scan", LoadI{c.flag1.ptr()}, (const uint8_t*)c.head.ptr(), n, c.scan.ptr(), e->tmpI);
+  // (the filter's read-back: the survivors' count and, with limiters, the earn's two counters behind it — one copy, one synchronisation)
+  unsigned* dlen = e->d_counters.ptr() + LIM_F_LEN;
+  const unsigned f_words = lim_commit ? LIM_F_WORDS : 1u;
+  memset_async(e, dlen, 0, f_words * 4);
   KM<cons_rate_limit, 256>(e, "cons_rate_limit", gN, (const int*)c.flag1.ptr(), (const SumI*)c.scan.ptr(), (const uint32_t*)c.g_user.ptr(), permU, n,
-      s.has_tokens ? (const int64_t*)s.tokens.ptr() : (const int64_t*)nullptr, s.enforce, c.keep_q.ptr(), c.rate_limited.ptr(), c.passed.ptr());
+      s.has_tokens ? (const int64_t*)s.tokens.ptr() : (const int64_t*)nullptr, lim, s.enforce, c.keep_q.ptr(), c.rate_limited.ptr(), c.passed.ptr());
+  if (lim_commit) limiter_commit_earn(e, lim, U, c.passed.ptr(), c.rate_limited.ptr(), e->d_counters.ptr());
   // ---- survivors back in queue order ---------------------------------------------------------------------------------------------
   uint32_t* qitem = c.qitemA.ensure(n);
   uint32_t* qitem_o = c.qitemB.ensure(n);
   SumU4* quse = c.quseA.ensure(n);
   SumU4* quse_o = c.quseB.ensure(n);
   seg_scan<SumI>(e, "cons_compact_scan", LoadI{c.keep_q.ptr()}, (const uint8_t*)nullptr, n, c.scan.ptr(), e->tmpI);
-  unsigned* dlen = e->d_counters.ptr() + 12;
-  memset_async(e, dlen, 0, 4);
   KM<cons_compact_queue, 256>(e, "cons_compact_queue", gN, (const int*)c.keep_q.ptr(), (const SumI*)c.scan.ptr(), n, q_cpus, q_mem, q_gpus, qitem, quse, dlen);
   // ---- (iii) pool quota, seeded with the pool usage (tools.clj:917-933, 966) -------------------------------------------------------
   cook_usage base = s.pool_usage;
@@ -128,10 +138,11 @@ void cons_run_device(cook_engine* e, const ConsBufs& s, ConsWork& c, unsigned n,
       pinned_copy(e, e->h_scratch + 8, c.pusage.ptr(), sizeof(SumU4), hipMemcpyDeviceToHost);
     }
   }
-  pinned_copy(e, e->h_scratch, dlen, 4, hipMemcpyDeviceToHost);
+  pinned_copy(e, e->h_scratch, dlen, f_words * 4, hipMemcpyDeviceToHost);
   sync(e);
   unsigned len = 0;
   std::memcpy(&len, e->h_scratch, 4);
+  if (lim_commit) limiter_filter_finish(e, (const unsigned*)e->h_scratch);
   if (s.has_pool_quota && !s.pool_usage_given) {
     SumU4 h = SumU4::zero();
     if (U) std::memcpy(&h, e->h_scratch + 8, sizeof(SumU4));

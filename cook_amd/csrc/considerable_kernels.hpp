@@ -9,6 +9,7 @@
 #pragma once
 #include "common.hpp"
 #include "scan.hpp"
+#include "limiter_kernels.hpp"
 
 COOK_KERNEL void cons_user_keys(const uint32_t* __restrict__ user, unsigned n, uint64_t* __restrict__ key) {
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -93,17 +94,22 @@ COOK_KERNEL void cons_user_quota_flag(const SumU4* __restrict__ pre, const uint3
 }
 
 // tools.clj:935-955: the n-th job of a user that reaches this stage is rate limited iff n > tokens-left; it is dropped only
-// when the limiter is enforcing.  Writes the verdict back in QUEUE order.
+// when the limiter is enforcing.  Writes the verdict back in QUEUE order.  lim.tokens non-null: the engine's own limiters count
+// (limiter_kernels.hpp) — the comparison is with the user's tokens AFTER earn(now), computed here as a pure function (tools.clj:951-953).
 COOK_KERNEL void cons_rate_limit(const int* __restrict__ flag1, const SumI* __restrict__ idx1,
                                                        const uint32_t* __restrict__ g_user, const uint32_t* __restrict__ permU, unsigned n,
-                                                       const int64_t* __restrict__ tokens, int enforce, int* __restrict__ keep_q,
+                                                       const int64_t* __restrict__ tokens, LimView lim, int enforce, int* __restrict__ keep_q,
                                                        uint32_t* __restrict__ rate_limited, uint32_t* __restrict__ passed) {
   const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int keep = 0;
   if (flag1[i]) {
     const unsigned u = g_user[i];
-    const bool limited = tokens ? ((long long)idx1[i].v > (long long)tokens[u]) : false;
+    bool limited = false;
+    if (lim.tokens)
+      limited = (long long)idx1[i].v > (long long)lim_tokens_now(lim, u);
+    else if (tokens)
+      limited = (long long)idx1[i].v > (long long)tokens[u];
     if (limited)
       atomicAdd(&rate_limited[u], 1u);
     else

@@ -10,6 +10,7 @@ COOK_KERNEL void cycle_job_index(const uint32_t* __restrict__ ranked, const uint
 // (considerable filters) -> take K over the standing queue -> the job index array of the match; returns K
 static unsigned cycle_take_part(cook_engine* e, uint32_t num_considerable) {
   e->q_last_pos = nullptr;
+  limiter_new_cycle(e);  // (the placements this cycle makes have not spent their tokens)
   unsigned K = std::min<unsigned>(num_considerable, e->n_ranked);  // (take num-considerable), scheduler.clj:751
   if (e->cb && e->cb->cycle_on) {  // pending-jobs->considerable-jobs between rank and match (scheduler.clj:729-762)
     ConsBufs& c = *e->cb;
@@ -21,7 +22,7 @@ static unsigned cycle_take_part(cook_engine* e, uint32_t num_considerable) {
           e->min.j_cpus, e->min.j_mem, e->min.j_gpus, (const uint32_t*)e->j_user.ptr(),
           c.has_elig_by_pending ? (const uint8_t*)c.elig_by_pending.ptr() : (const uint8_t*)nullptr, c.q_cpus.ptr(), c.q_mem.ptr(), c.q_gpus.ptr(),
           c.q_user.ptr(), c.q_elig.ptr());
-    cons_run_device(e, c, c, n, c.q_cpus.ptr(), c.q_mem.ptr(), c.q_gpus.ptr(), c.q_user.ptr(), c.q_elig.ptr(), num_considerable);
+    cons_run_device(e, c, c, n, c.q_cpus.ptr(), c.q_mem.ptr(), c.q_gpus.ptr(), c.q_user.ptr(), c.q_elig.ptr(), num_considerable, LIM_CYCLE);
     K = c.n_result;
     e->cycle_cons_ran = true;
     e->q_last_pos = c.result;

@@ -66,6 +66,7 @@ struct ReleaseBufs;    // release_host.hpp
 struct ChurnBufs;      // churn_host.hpp
 struct ReserveBufs;    // reserve_host.hpp
 struct ResidentRebalBufs;  // rebal_resident_host.hpp
+struct LimiterBufs;    // limiter_host.hpp
 
 }  // namespace
 
@@ -214,6 +215,7 @@ struct cook_engine {
   std::unique_ptr<ReleaseBufs> rlb;            // the release of a queue cycle (allocated on first use)
   std::unique_ptr<ChurnBufs> chb;              // the host churn of a queue cycle (allocated on first use)
   std::unique_ptr<ReserveBufs> rvb;            // the rebalancer's host reservations kept across cycles (allocated on first use)
+  std::unique_ptr<LimiterBufs> lmb;            // the launch-rate limiters kept across cycles (allocated on first use)
   // the host's mirror of the staged offers' host ids, ascending (match_stage_offers, cook_cycle_update's offers; a host churn edits it per
   // list entry): what a churn is checked against and sized by before its first launch.  Not known: offers built on the device
   std::vector<uint32_t> o_hosts;
@@ -312,6 +314,13 @@ static std::atomic<int> g_engines_on_device[64];
 static void reserve_drop(cook_engine* e);  // reserve_host.hpp: a stage or an update drops the engine's own reservation map
 #include "match_host.hpp"      // match staging, one pool's placement, several pools in lockstep rounds
 #include "served_host.hpp"     // several pools by served walkers
+// limiter_host.hpp: what the considerable filters, a cycle's front part and the carry ask of the launch-rate limiters the engine may hold
+static bool limiter_own(const cook_engine* e);
+static void limiter_check_user_state(cook_engine* e, const cook_user_state* us);
+static void limiter_new_cycle(cook_engine* e);
+static LimView limiter_view(cook_engine* e, unsigned U, bool cycle);
+static void limiter_commit_earn(cook_engine* e, const LimView& v, unsigned U, const uint32_t* passed, const uint32_t* rate_limited, unsigned* fcnt);
+static void limiter_filter_finish(cook_engine* e, const unsigned* h);
 #include "considerable_host.hpp"
 #include "rebalance_host.hpp"
 #include "offers_host.hpp"
@@ -323,6 +332,7 @@ static void reserve_drop(cook_engine* e);  // reserve_host.hpp: a stage or an up
 #include "release_host.hpp"    // a queue cycle's release: the carry's segments and column sets
 #include "churn_host.hpp"      // a queue cycle's host churn: the release's host-indexed table, the carry's segments
 #include "reserve_host.hpp"    // the host reservations kept across cycles: the advance's counters (churn_kernels.hpp)
+#include "limiter_host.hpp"    // the launch-rate limiters kept across cycles: QueueArgs (carry_host.hpp), the advance's counters
 #include "queue_host.hpp"
 #include "sweep_host.hpp"
 #include "unscheduled_host.hpp"
@@ -490,6 +500,7 @@ int cook_cycle_stage_built_offers(cook_engine* e, const cook_tasks* tasks, const
       e->fail(COOK_E_INVALID, "cook_cycle_stage_built_offers: pending_jobs->n must equal the number of pending tasks");
     match_stage_inputs(e, pending_jobs, &o, groups, reserved_hosts, n_reserved, true);
     e->cycle_staged = true;
+    limiter_drop(e);  // (the users are restaged)
     if (e->ub) e->ub->csr_known = false;  // (cycle_update.hpp: the staged CSR columns' sizes are looked up again)
   });
 }
@@ -536,6 +547,7 @@ int cook_cycle_stage(cook_engine* e, const cook_tasks* tasks, const cook_users* 
       e->fail(COOK_E_INVALID, "cook_cycle_stage: pending_jobs->n must equal the number of pending tasks");
     match_stage_inputs(e, pending_jobs, offers, groups, reserved_hosts, n_reserved);
     e->cycle_staged = true;
+    limiter_drop(e);  // (the users are restaged)
     if (e->ub) e->ub->csr_known = false;  // (cycle_update.hpp: the staged CSR columns' sizes are looked up again)
   });
 }
@@ -664,6 +676,33 @@ int cook_cycle_reserve_info(cook_engine* e, cook_reserve_info* out) {
 }
 int cook_cycle_fetch_reservations(cook_engine* e, uint32_t* pending, uint32_t* host, uint32_t cap, uint32_t* n_out) {
   return guarded(e, [&] { reserve_fetch(e, pending, host, cap, n_out); });
+}
+int cook_cycle_set_limiters(cook_engine* e, const cook_limiters* l) {
+  return guarded(e, [&] {
+    limiter_set(e, l);
+    prof_collect(e);
+  });
+}
+int cook_cycle_set_clock(cook_engine* e, const cook_clock* c) {
+  return guarded(e, [&] { limiter_set_clock(e, c); });
+}
+int cook_cycle_limiters_spend(cook_engine* e, const uint8_t* offer_skipped, uint32_t n_offer_skipped, int64_t spend_ms) {
+  return guarded(e, [&] {
+    limiter_spend(e, offer_skipped, n_offer_skipped, spend_ms);
+    prof_collect(e);
+  });
+}
+int cook_cycle_fetch_limiters(cook_engine* e, int64_t* tokens, int64_t* last_update_ms, int64_t* time_until_ms) {
+  return guarded(e, [&] { limiter_fetch(e, tokens, last_update_ms, time_until_ms); });
+}
+int cook_cycle_fetch_rate_limit(cook_engine* e, uint32_t* rate_limited, uint32_t* passed) {
+  return guarded(e, [&] { limiter_fetch_counts(e, rate_limited, passed); });
+}
+int cook_cycle_limiter_info(cook_engine* e, cook_limiter_info* out) {
+  return guarded(e, [&] {
+    if (!out) e->fail(COOK_E_INVALID, "cook_cycle_limiter_info: null out");
+    *out = e->lmb ? e->lmb->info : cook_limiter_info{};
+  });
 }
 int cook_cycle_churn_info(cook_engine* e, cook_churn_info* out) {
   return guarded(e, [&] {

@@ -187,7 +187,7 @@ static __device__ __forceinline__ double chain3(const Load& load, unsigned lo, u
 }
 
 // usage arrays in place (each user is one workgroup's, read before it is written).  Taking spends the tokens too; they may be null
-// (none staged, or the host replaced them).  Giving back leaves them alone and counts the segment's length.
+// (none staged, the host replaced them, or the engine's own limiters spend: limiter_host.hpp).  Giving back leaves them alone and counts the segment's length.
 template <bool GIVE_BACK, class Load>
 COOK_KERNEL void fold_users(Load load, const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ seg_end, unsigned U,
                             double* __restrict__ ucount, double* __restrict__ ucpus, double* __restrict__ umem, double* __restrict__ ugpus,

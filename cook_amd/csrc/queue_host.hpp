@@ -7,7 +7,8 @@
 // A release (release_host.hpp) is enqueued behind the carry and the fold, also when there is nothing to advance over; its counters ride
 // in the same synchronisation.  A host churn (churn_host.hpp) is enqueued behind the release; its counter rides there too.  The host
 // reservations (reserve_host.hpp) are enqueued behind the churn: they touch neither the queue nor the offers, and their two counters
-// ride there as well.
+// ride there as well.  The launch-rate limiters (limiter_host.hpp) spend the last cycle's kept placements behind the reservations; their two
+// counters ride there too.
 #pragma once
 #include "queue_kernels.hpp"
 
@@ -39,6 +40,7 @@ void queue_check_step(cook_engine* e, const QueueArgs& q) {
   release_check(e, q);
   churn_check(e, q);
   reserve_check(e, q);
+  limiter_check(e, q);
   if (!s) return;
   if (s->remove_mode > 1u) e->fail(COOK_E_INVALID, "cook_queue_step.remove_mode: 0 = the kept matches, 1 = every considered job");
   if (s->offer_skipped && s->n_offer_skipped != e->M)
@@ -78,10 +80,11 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   const unsigned n = e->n_ranked, k = e->cycle_considered, G = e->G, M_old = e->M;
   const bool fold = G && k && in.j_group && !(s && s->groups);
   unsigned* cnt = b.counters.ensure(REL_CNT_WORDS);
-  const bool advance = k && n, release = release_active(f), churn = churn_active(q.hosts), reserve = reserve_active(q.reservations);
+  const bool advance = k && n, release = release_active(f), churn = churn_active(q.hosts), reserve = reserve_active(q.reservations),
+             spend = limiter_spend_due(e, advance ? k : 0u);
   bool carried = false;
   const uint8_t* skipped = nullptr;  // the step's offer_skipped on the device (the advance's kernels and the reservations' release read it)
-  if (advance || release || churn || reserve) memset_async(e, cnt, 0, REL_CNT_WORDS * 4);
+  if (advance || release || churn || reserve || spend) memset_async(e, cnt, 0, REL_CNT_WORDS * 4);
   if (advance) {
     int* removed = b.removed.ensure(n);
     memset_async(e, removed, 0, (size_t)n * 4);
@@ -130,7 +133,9 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   if (q.hosts || e->chb) churn_enqueue(e, q.hosts, cnt);
   // ---- the host reservations: the last cycle's kept matches release theirs, a rebalancer's list replaces the map ----------------------------
   if (q.reservations || e->rvb) reserve_enqueue(e, q.reservations, cnt, skipped, advance ? k : 0u);
-  if (release || churn || reserve) pinned_copy(e, e->h_scratch + REL_H_CNT, cnt, REL_CNT_WORDS * 4, hipMemcpyDeviceToHost);
+  // ---- the launch-rate limiters: the last cycle's kept placements spend their tokens, in front of the considerable filters --------------------
+  limiter_enqueue(e, cnt, skipped, advance ? k : 0u);
+  if (release || churn || reserve || spend) pinned_copy(e, e->h_scratch + REL_H_CNT, cnt, REL_CNT_WORDS * 4, hipMemcpyDeviceToHost);
   // ---- the step's groups and offers (behind the kernels above on the stream: the fold read the OLD offers) ------------------------------
   if (s && s->groups && G) {
     const cook_groups* g = s->groups;
@@ -147,7 +152,7 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   if (s && s->offers) match_stage_offers(e, s->offers, false);
   if (e->chb) e->chb->info.n_offers = e->M;  // (the rows behind the advance, whoever set them)
   carry_tokens(e, c);
-  if (advance || release || churn || reserve || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
+  if (advance || release || churn || reserve || spend || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
   if (c) carry_finish(e);
   if (advance) {
     unsigned h[2] = {0, 0};
@@ -155,12 +160,13 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
     e->n_ranked = n - h[0];
     if (fold) e->cf_group_run_total += h[1];
   }
-  if (release || churn || reserve) {
+  if (release || churn || reserve || spend) {
     unsigned h[REL_CNT_WORDS];
     std::memcpy(h, e->h_scratch + REL_H_CNT, sizeof(h));
     release_finish(e, h);
     churn_finish(e, h);
     reserve_finish(e, h);
+    limiter_finish(e, h);
   }
   e->q_advance_us = (uint32_t)std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_call).count();
 }

@@ -11,7 +11,7 @@
 #include "scan.hpp"
 
 // words of QueueBufs::counters behind the advance's two: read back in the advance's one synchronisation
-constexpr unsigned REL_CNT_NO_ROW = 2, REL_CNT_CLAMPED = 3, REL_CNT_MISSING = 4, REL_CNT_WORDS = 8;
+constexpr unsigned REL_CNT_NO_ROW = 2, REL_CNT_CLAMPED = 3, REL_CNT_MISSING = 4, REL_CNT_WORDS = 12;  // (behind the release's: the churn's, the reservations', the limiters')
 
 // the list's columns on the device (null columns: all 0 / no request)
 struct ReleaseList {

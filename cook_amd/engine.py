@@ -362,6 +362,50 @@ class Engine:
         self._chk(self._lib.cook_cycle_fetch_reservations(self._h, _p(pend, C.c_uint32), _p(host, C.c_uint32), cap, C.byref(n)))
         return pend[:n.value].copy(), host[:n.value].copy()
 
+    def cycle_set_limiters(self, limiters: Optional[A.Limiters] = None):
+        """The launch-rate limiters the engine keeps from here on (cook_cycle_set_limiters): every later cycle's considerable filter
+        reads them instead of the staged tokens_left; a Limiters with a user list replaces only the listed users'; None drops them."""
+        ls, keep = limiters.as_struct() if limiters is not None else (None, None)
+        self._chk(self._lib.cook_cycle_set_limiters(self._h, C.byref(ls) if ls is not None else None))
+        del keep
+
+    def cycle_set_clock(self, now_ms: Optional[int] = None, spend_ms: Optional[int] = None):
+        """The time of the NEXT cycle (cook_cycle_set_clock): now_ms the filters' clock reading, spend_ms when the last cycle's kept
+        matches were launched (None: now_ms).  now_ms None: no clock — nobody earns."""
+        if now_ms is None:
+            self._chk(self._lib.cook_cycle_set_clock(self._h, None))
+            return
+        ck = A.CookClock(int(now_ms), int(now_ms if spend_ms is None else spend_ms))
+        self._chk(self._lib.cook_cycle_set_clock(self._h, C.byref(ck)))
+
+    def cycle_limiters_spend(self, spend_ms: int, offer_skipped=None):
+        """The last cycle's kept placements spend their tokens now (cook_cycle_limiters_spend): for the cycle that no queue advance
+        follows.  offer_skipped: per offer of the last cycle, as in a queue step."""
+        sk = np.ascontiguousarray(offer_skipped, np.uint8) if offer_skipped is not None else None
+        self._chk(self._lib.cook_cycle_limiters_spend(self._h, _p(sk, C.c_uint8) if sk is not None else None, len(sk) if sk is not None else 0,
+                                                      int(spend_ms)))
+
+    def fetch_limiters(self, n_users: int):
+        """-> (tokens, last_update_ms, time_until_ms) of the engine's limiters, per user (cook_cycle_fetch_limiters)."""
+        n = max(1, int(n_users))
+        tok, last, until = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int64)
+        self._chk(self._lib.cook_cycle_fetch_limiters(self._h, _p(tok, C.c_int64), _p(last, C.c_int64), _p(until, C.c_int64)))
+        return tok[:n_users].copy(), last[:n_users].copy(), until[:n_users].copy()
+
+    def fetch_rate_limit(self, n_users: int):
+        """-> (rate_limited, passed): the rate-limit stage's per-user counts of the last cycle's considerable filter
+        (cook_cycle_fetch_rate_limit)."""
+        n = max(1, int(n_users))
+        rl, ps = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self._chk(self._lib.cook_cycle_fetch_rate_limit(self._h, _p(rl, C.c_uint32), _p(ps, C.c_uint32)))
+        return rl[:n_users].copy(), ps[:n_users].copy()
+
+    def limiter_info(self) -> dict:
+        """The limiters' counts of the last cycle (cook_cycle_limiter_info)."""
+        out = A.CookLimiterInfo()
+        self._chk(self._lib.cook_cycle_limiter_info(self._h, C.byref(out)))
+        return {k: int(getattr(out, k)) for k, _ in A.CookLimiterInfo._fields_ if k != "reserved"}
+
     def churn_info(self) -> dict:
         """The counts of the last queue cycle's host churn (cook_cycle_churn_info); all 0 (n_offers: the staged rows) when it had none."""
         out = A.CookChurnInfo()

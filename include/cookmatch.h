@@ -571,12 +571,12 @@ int cook_cycle_run_queue_multi(cook_engine** engines, uint32_t n, const cook_que
  *     usage_cpus[u] / usage_mem[u] / usage_gpus[u] += the left-to-right sums (each from 0) of cpus / mem / gpus.  With pool_usage_given
  *     the pool usage grows by the same four quantities summed over ALL kept jobs in considered order; otherwise the engine keeps
  *     summing the users itself.  Tokens: tokens_left non-NULL replaces the staged counts and nothing is spent (the host has done both);
- *     tokens_left NULL with tokens staged: tokens[u] -= kept jobs of u (the spend; the refill with time stays with the host).
+ *     tokens_left NULL with tokens staged: tokens[u] -= kept jobs of u (the spend; the refill with time is the host's, or the engine's: THE LAUNCH-RATE LIMITERS below).
  *     tokens_left is honoured whatever the two flags say.  Quotas, enforce_rate_limit and the eligible mask stay as staged.
  * Refused before anything changes: offers = 1 together with step->offers, a flag above 1, tokens_left while the staged state has no
  * limiter (COOK_E_INVALID); usage = 1 or tokens_left without a staged user state (COOK_E_STATE).
  * Not carried: finished tasks (cook_cycle_run_queue_release below takes their list), hosts that join or leave
- * (cook_cycle_run_queue_hosts below takes their lists); the host's to tell: the time-based token refill (tokens_left).  carry NULL, or both flags 0 and no tokens: exactly cook_cycle_run_queue / _multi. */
+ * (cook_cycle_run_queue_hosts below takes their lists); the time-based token refill (tokens_left from the host, or the engine's own limiters, which need only the time: cook_cycle_set_limiters below).  carry NULL, or both flags 0 and no tokens: exactly cook_cycle_run_queue / _multi. */
 typedef struct cook_queue_carry {
   uint32_t offers;            /* 1: carry the kept placements into the staged offers (then step->offers must be NULL) */
   uint32_t usage;             /* 1: carry them into the staged user state (needs cook_cycle_set_considerable staged)   */
@@ -809,6 +809,88 @@ int cook_cycle_reserve_info(cook_engine* e, cook_reserve_info* out);
  * *n_out = their count; cap smaller than that: COOK_E_INVALID with *n_out set and nothing written.  No map of the engine's own: 0.
  * Changes no state; one synchronisation */
 int cook_cycle_fetch_reservations(cook_engine* e, uint32_t* pending, uint32_t* host, uint32_t cap, uint32_t* n_out);
+
+/* ---- THE LAUNCH-RATE LIMITERS: the per-user-per-pool token buckets, refilled by time on the device --------------------------------------
+ * The considerable filter's rate-limit stage (tools.clj:935-959) reads ratelimit/get-token-count! of the per-user-per-pool launch limiter;
+ * launch-matches! spends one token per launched task (scheduler.clj:871).  With cook_user_state.tokens_left the host computes the
+ * refill every cycle and uploads an int64 per user.  Here the engine keeps the reference's token bucket filter
+ * (rate_limit/token_bucket_filter.clj, rate_limit/generic.clj) per user and the host passes two integers per cycle: the time.  The
+ * compute-cluster launch limiter (filter-matches-for-ratelimit) stays with the host: it arrives as offer_skipped.
+ * The bucket, restated (the device and the tests' oracle follow this to the bit).  Per user {rate (fp64, tokens per ms), bucket, last (ms),
+ * tokens (may be negative)}:
+ *   rate        = per_minute / 60000.0, ONE fp64 division (generic.clj:50).
+ *   earn(t)     : t' = max(t, last).  If t' != last: d = (int64) trunc((double)(t' - last) * rate) — one fp64 multiply, truncation toward
+ *                 zero, the product clamped at 2^62 before the conversion (the reference would throw there).  d != 0: last = t', tokens =
+ *                 min(tokens + d, bucket).  d == 0: NOTHING changes; last stays, so the fraction of a token is not lost.
+ *   spend(t, w) : earn(t); then, w != 0: tokens = min(tokens - w, bucket), last as the earn left it.  n spends at one time t are
+ *                 earn(t); tokens -= n.
+ *   time_until  = max(0, (int64) ceil((double)(-tokens) / rate)), fp64 division (time-until-out-of-debt-millis! without its earn).
+ * Who earns (oracle-defined, like the winner rule).  The reference earns a bucket when it is accessed, and an earn in between changes
+ * the result (each one drops a fraction: at rate 0.01, earn(199); earn(300) gives 2 tokens, earn(300) alone 3).  In a cycle WITH a clock
+ * user u earns at now_ms iff at least one of its jobs reaches the rate-limit stage of that cycle's considerable filter, i.e.
+ * passed[u] + rate_limited[u] > 0 over the whole standing queue (the upper bound of the reference's lazy access set that
+ * cook_considerable documents).  The filter compares the n-th job of a user with tokens AFTER that earn (tools.clj:951-953).  One
+ * clock reading serves the whole cycle (the reference reads the clock per job).  cook_cycle_autoscale reads the tokens as that cycle
+ * left them and earns nothing.
+ *  1. Ownership.  From the first cook_cycle_set_limiters the engine's state is what every later considerable filter of a cycle reads:
+ *     rank cycles and queue cycles, single and _multi (pools with limiters beside pools without), every placement form.  user NULL: n
+ *     must equal the staged users (those of cook_cycle_set_considerable's state if one is staged, else cook_cycle_stage's) and entry i
+ *     is user i.  With a user list only the listed users' four values are replaced (the host's flush! after set-quota! /
+ *     retract-quota!: tokens = bucket, last = now); the first call must cover every user, and its tokens are taken as current: the
+ *     placements of the cycle in front of it do not spend again.  enforce_rate_limit stays in cook_user_state.
+ *     While limiters are held a cook_user_state.tokens_left, a cook_user_state of another n, or a cook_queue_carry.tokens_left is
+ *     refused with COOK_E_INVALID and nothing changes.  cook_cycle_set_limiters(NULL) drops them: the staged tokens_left is read again
+ *     as it was staged.  cook_considerable (the stand-alone filter) never reads them.
+ *  2. Clock.  cook_cycle_set_clock is host-only state: the time of the NEXT cycle.  It is consumed by the next cycle that runs the
+ *     considerable filters on that engine (every existing cook_cycle_run* entry reads it; there are no new ones); a refused step
+ *     leaves it staged; NULL takes it back.  Without a clock nobody earns; spends still subtract, as a spend at t <= last.
+ *  3. Spend, once per cycle, at the first of: (a) the advance of the next queue cycle, in front of the filters, whether or not a carry
+ *     is given: every user with KEPT placements in the pool's last cycle (job_to_offer >= 0 and the offer not in the step's
+ *     offer_skipped: the predicate of step 1, the fold and the carry) does earn(spend_ms); tokens -= its kept jobs.  spend_ms is the
+ *     staged clock's: when the last cycle's kept matches were launched.  With carry.usage = 1 the spend that the carry would have made
+ *     on the staged tokens goes here instead.  (b) cook_cycle_limiters_spend, for the cycle no queue advance follows (the last
+ *     queue cycle in front of a rank trigger, where the host restages).  A second call for the same cycle: COOK_E_STATE; an advance
+ *     behind an explicit spend spends nothing.  A rank cycle never spends: what the cycle in front of it placed and did not spend
+ *     explicitly is the host's to tell (a listed cook_cycle_set_limiters).
+ *  4. Lifetime.  Keyed by user id; survives ranks and cook_cycle_update; cook_cycle_stage* drops it (the users are restaged).
+ *     COOK_E_INVALID, nothing changed: n other than the staged users (user NULL, or the first call), a user out of range or listed
+ *     twice, per_minute not finite or not above 0, bucket outside 0 .. 2^53, |tokens| above 2^53, |last_update_ms| or a clock time above
+ *     2^62, pending_jobs->user not staged.  COOK_E_STATE: before cook_cycle_stage; between a deferred set-up (cook_cycle_run_rank*,
+ *     cook_cycle_run_queue_rank, the _multi queue steps) and cook_cycle_match_multi, as cook_cycle_set_reservations.
+ *  5. Cost.  No synchronisation of its own inside a cycle: at most three small launches of per-user work (two in the advance, one behind
+ *     the rate-limit stage), counters in the advance's and the filter's read-backs.  (Additive: no existing layout changes.) */
+typedef struct cook_limiters {
+  uint32_t n;                    /* entries */
+  const uint32_t* user;          /* [n] user ids, each at most once; NULL: n must equal the staged users, entry i is user i */
+  const double* per_minute;      /* [n] tokens-replenished-per-minute (launch-rate-per-minute, quota.clj:118-133): finite, > 0 */
+  const int64_t* bucket;         /* [n] bucket size, 0 .. 2^53 */
+  const int64_t* tokens;         /* [n] current tokens, |tokens| <= 2^53 */
+  const int64_t* last_update_ms; /* [n] */
+} cook_limiters;
+typedef struct cook_clock {
+  int64_t now_ms;   /* the filters' clock reading of the next cycle */
+  int64_t spend_ms; /* when the LAST cycle's kept matches were launched (read by the next queue cycle's advance) */
+} cook_clock;
+typedef struct cook_limiter_info {
+  uint32_t earned;      /* users whose state the last cycle's earn moved */
+  uint32_t spent_users; /* users that spent in the last advance or cook_cycle_limiters_spend */
+  uint32_t in_debt;     /* users with tokens < 0 behind the last cycle's filters that ran with limiters */
+  uint32_t reserved;
+  int64_t spent;        /* tokens spent there */
+} cook_limiter_info;
+int cook_cycle_set_limiters(cook_engine* e, const cook_limiters* l); /* NULL: drop the engine's limiters */
+int cook_cycle_set_clock(cook_engine* e, const cook_clock* c);       /* the time of the NEXT cycle; NULL: none */
+/* offer_skipped: [offers of the LAST cycle] or NULL, n_offer_skipped as in cook_queue_step.  Needs limiters and a completed cycle
+ * (COOK_E_STATE).  One synchronisation */
+int cook_cycle_limiters_spend(cook_engine* e, const uint8_t* offer_skipped, uint32_t n_offer_skipped, int64_t spend_ms);
+/* tokens, last_update_ms, time_until_ms: each [users] or NULL.  Changes no state; one synchronisation.  Without limiters: COOK_E_STATE */
+int cook_cycle_fetch_limiters(cook_engine* e, int64_t* tokens, int64_t* last_update_ms, int64_t* time_until_ms);
+/* the rate-limit stage's counts of the last cycle that ran the considerable filters (cook_considerable's rate_limited / passed, over the
+ * whole standing queue): each [users of the staged state] or NULL, with or without limiters.  COOK_E_STATE when the last cycle ran no
+ * filters.  One synchronisation */
+int cook_cycle_fetch_rate_limit(cook_engine* e, uint32_t* rate_limited, uint32_t* passed);
+/* the counts of the last cycle; all 0 without limiters */
+int cook_cycle_limiter_info(cook_engine* e, cook_limiter_info* out);
 
 /* ---- REBALANCE: replaces init-state + the rebalance loop's decisions ---------------------------------------
  * (rebalancer.clj:222-266, 320-407, 270-309, 434-467; dru.clj:128-144).

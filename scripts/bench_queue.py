@@ -29,10 +29,15 @@ The host reservations (cook_cycle_run_queue_reserve*), --reserve
 with reservations = NULL and once with, per queue cycle, release_matched = 1 and a replacement list of RESERVE_LIST random entries
 (the two legs place differently: hosts are reserved); the row has both cycle times and the device time of the reserve kernels beside
 the carry's, the release's and the churn's.
-    python scripts/bench_queue.py [--steps 50] [--warmup 5] [--k-all] [--carry | --carry-only] [--release | --release-only] [--churn | --churn-only] [--reserve]
+--limiters: the churn's first leg under an enforcing launch-rate limit, twice each in turns: a host that uploads
+tokens_left per pool per cycle (the counts come from the other leg: its arithmetic is not timed) against limiters kept on the device with
+cook_cycle_set_clock per cycle; identical placements asserted; the row has the four medians, the spread of the host's two runs and the
+limiter kernels' device time per cycle.
+    python scripts/bench_queue.py [--steps 50] [--warmup 5] [--k-all] [--carry | --carry-only] [--release | --release-only] [--churn | --churn-only] [--reserve] [--limiters]
                                   [--out results/queue.json]"""
 import argparse
 import copy
+import dataclasses
 import json
 import os
 import sys
@@ -366,11 +371,13 @@ def run_release(name, pools, k, steps, warmup):
             "advance_syncs": 1, "identical_placements": True, "released_per_cycle": released, "groups": grouped}
 
 
-def run_churn(name, pools, k, steps, warmup, reserve=False):
+def run_churn(name, pools, k, steps, warmup, reserve=False, limiters=False):
     """the two legs of the host churn (carry + release + churn against a host that supplies the table, the user state and the groups);
     -> one result row.  reserve: instead of the host's leg, the same carry + release + churn cycles through
     cook_cycle_run_queue_reserve* with reservations = NULL (leg one) and with, per queue cycle, release_matched = 1 and a replacement
-    list of RESERVE_LIST entries (leg two; its placements differ: hosts are reserved)"""
+    list of RESERVE_LIST entries (leg two; its placements differ: hosts are reserved).  limiters: the same first leg
+    under an enforcing launch-rate limit, twice each in turns: (b) with the limiters on the device and cook_cycle_set_clock per cycle,
+    (a) as a host drives it, uploading tokens_left per pool per cycle (its own arithmetic is not counted: the counts are leg (b)'s)"""
     params = A.default_params()
     n = len(pools)
     states = [AS.random_state(pl, 40 + i, tokens=False, pool_quota=False) for i, pl in enumerate(pools)]
@@ -407,6 +414,9 @@ def run_churn(name, pools, k, steps, warmup, reserve=False):
         if draw:
             for i, (g, pl, e) in enumerate(zip(out, pools, engines)):
                 g.churn = e.churn_info()
+                if limiters:
+                    tokens[i][c] = e.fetch_limiters(states[i][0].n)[0]
+                    limited[0] += int(e.fetch_rate_limit(states[i][0].n)[0].sum())
                 history[i].append(SimpleNamespace(j2o=g.j2o, jobs=pl.pending_jobs.take(jq_of[i][g.Q[g.pos]]), offers=e.fetch_offers().offers()))
                 if c < cyc:
                     picks = [q for q in RO.placed_rows(history[i]) if q not in gone[i] and rng.random() < RELEASE_FRAC]
@@ -414,10 +424,12 @@ def run_churn(name, pools, k, steps, warmup, reserve=False):
                     lists[i][c + 1] = RO.finished_of(history[i], picks, offers=1, usage=1, groups=int(grouped[i]))
         return out
 
-    def episode(engines, step, record, draw=False):
+    def episode(engines, step, record, draw=False, begin=None):
         for e, pl, (st, el) in zip(engines, pools, states):
             e.cycle_update(offers=pl.offers)
             e.cycle_set_considerable(st, el)
+        if begin is not None:
+            begin(engines)
         rank(engines)
         if record is not None:
             record.append(note(engines, 0, draw))
@@ -462,6 +474,81 @@ def run_churn(name, pools, k, steps, warmup, reserve=False):
             cycle_run_queue_hosts_multi(engines, ks, None, [both] * n, [lists[i][c] for i in range(n)], [churns[i][c] for i in range(n)])
             cycle_match_multi(engines)
 
+    if limiters:
+        lr = np.random.default_rng(4242)
+        lims = []
+        for st, _ in states:
+            bucket = lr.integers(20, 200, st.n)
+            lims.append(A.Limiters(lr.choice([60.0, 600.0, 1333.0, 6000.0], size=st.n), bucket, bucket, np.zeros(st.n, np.int64)))
+        states_b = [(dataclasses.replace(st, enforce_rate_limit=True), el) for st, el in states]
+        tokens = [[None] * (cyc + 1) for _ in pools]  # what the filters of cycle c compared with, from leg (b)'s first episode
+        limited = [0]  # jobs the rate-limit stage held back in that episode (the legs must not measure a limit that never binds)
+
+        def limiter_leg(on_device):
+            nonlocal states
+            if on_device:
+                states = states_b
+            else:
+                states = [(dataclasses.replace(st, tokens_left=tokens[i][0]), el) for i, (st, el) in enumerate(states_b)]
+
+            def step(engines, c):
+                if on_device:
+                    for e in engines:
+                        e.cycle_set_clock(1000 * (c + 1), 1000 * (c + 1) - 30)
+                    step_churn(engines, c)
+                    return
+                cy = [A.QueueCarry(offers=True, usage=True, tokens_left=tokens[i][c]) for i in range(n)]
+                if n == 1:
+                    engines[0].cycle_run_queue_hosts(ks[0], cy[0], lists[0][c], churns[0][c])
+                else:
+                    cycle_run_queue_hosts_multi(engines, ks, None, cy, [lists[i][c] for i in range(n)], [churns[i][c] for i in range(n)])
+                    cycle_match_multi(engines)
+            return step
+        LIMITER = ("lim_count_kept", "lim_spend", "lim_commit_earn")
+        results = {}
+        for turn, on_device in enumerate((True, False, True, False)):
+            step = limiter_leg(on_device)
+            engines = [Engine(params) for _ in pools]
+            try:
+                for e, pl in zip(engines, pools):
+                    e.cycle_stage(pl.tasks, pl.users, pl.pending_jobs, pl.offers, pl.groups)
+                first, ts = [], []
+
+                def begin(engines):  # (the limiters and the rank cycle's clock go in behind the episode's cook_cycle_set_considerable)
+                    if on_device:
+                        for e, lm in zip(engines, lims):
+                            e.cycle_set_limiters(lm)
+                            e.cycle_set_clock(1000, 1000)
+                for ep in range(episodes):
+                    if on_device:
+                        for e in engines:
+                            e.cycle_set_limiters(None)  # (the episode restages the user state)
+                    rec = first if ep == 0 else None
+                    ts += episode(engines, step, rec, draw=(turn == 0 and ep == 0), begin=begin)
+                prof_us = prof_launches = None
+                if on_device:
+                    for e in engines:
+                        e.set_profiling(True)
+                        e.cycle_set_limiters(None)
+                    episode(engines, step, None, begin=begin)
+                    kt = [e.kernel_timings() for e in engines]
+                    prof_us = round(sum(v[0] for t in kt for nm, v in t.items() if nm in LIMITER) * 1e3 / cyc, 1)
+                    prof_launches = round(sum(v[1] for t in kt for nm, v in t.items() if nm in LIMITER) / cyc, 1)
+                results[turn] = (first, median_ms(ts[warmup:]), prof_us, prof_launches)
+                if turn == 0:
+                    assert all(t is not None for row in tokens for t in row) and limited[0] > 0, "the limit binds nowhere"
+            finally:
+                for e in engines:
+                    e.close()
+        for c, (a, b) in enumerate(zip(results[0][0], results[1][0])):
+            for i in range(n):
+                assert np.array_equal(a[i].Q, b[i].Q) and np.array_equal(a[i].pos, b[i].pos) and np.array_equal(a[i].j2o, b[i].j2o), \
+                    f"{name}: the limiter legs differ in cycle {c}, pool {i}"
+        a_ms, b_ms = [results[1][1], results[3][1]], [results[0][1], results[2][1]]
+        return {"config": name + ", carry + release + churn under an enforcing launch-rate limit", "pools": n, "K": k or "all", "timed_cycles": len(ts[warmup:]),
+                "host_tokens_left_cycle_ms": a_ms, "device_limiters_cycle_ms": b_ms, "host_runs_spread_ms": round(abs(a_ms[0] - a_ms[1]), 3),
+                "limiter_kernels_us_per_cycle": results[2][2], "limiter_launches_per_cycle": results[2][3], "rate_limited_jobs_first_episode": limited[0],
+                "identical_placements": True}
     if reserve:
         rr = np.random.default_rng(777)
         rlists = [[A.Reservations(rr.choice(pl.pending_jobs.n, min(RESERVE_LIST, pl.pending_jobs.n), replace=False),
@@ -543,6 +630,7 @@ def main():
     ap.add_argument("--churn", action="store_true", help="also the two legs of the host churn")
     ap.add_argument("--churn-only", action="store_true", help="only the two legs of the host churn (and, with --carry / --release, of those)")
     ap.add_argument("--reserve", action="store_true", help="only the churn's first leg through cook_cycle_run_queue_reserve*, without and with reservations")
+    ap.add_argument("--limiters", action="store_true", help="only the churn's first leg under a launch-rate limit: tokens_left from the host against limiters on the device")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--k-all", action="store_true")
@@ -556,6 +644,10 @@ def main():
         rows.append(r)
         print(json.dumps(r), flush=True)
     for k in [1000] + ([0] if args.k_all else []):
+        if args.limiters:
+            add(run_churn("one C4 pool", c4[:1], k, args.steps, args.warmup, limiters=True))
+            add(run_churn("eight C4 pools, multi form", c4, k, args.steps, args.warmup, limiters=True))
+            continue
         if args.reserve:
             add(run_churn("one C4 pool", c4[:1], k, args.steps, args.warmup, reserve=True))
             add(run_churn("eight C4 pools, multi form", c4, k, args.steps, args.warmup, reserve=True))
