@@ -976,6 +976,121 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleAutoscaleMulti(JNIEnv* env, jcl
   return CHECKED(cook_cycle_autoscale_multi(es, (uint32_t)n, pp, outs, cs, info, rcs));
 }
 
+/* (hash uuid) of the pending jobs by pending ordinal (cook_cycle_set_job_hashes): hashes = n int32 values for rows [first, first + n) */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleSetJobHashes(JNIEnv* env, jclass c, jlong h, jobject hashes, jint first, jint n) {
+  int bad = 0;
+  const int32_t* hs = BUFN(const int32_t, hashes, n > 0 ? n : 0);
+  (void)c;
+  if (bad || first < 0 || n < 0 || (n && !hs)) return COOK_E_INVALID;
+  return cook_cycle_set_job_hashes(H(h), hs, (uint32_t)first, (uint32_t)n);
+}
+/* one cook_autoscale_clusters from its columns: cols = {location uint32 [n], max_pods_outstanding, num_synthetic_pods, max_total_nodes,
+ * total_nodes, max_total_pods, total_pods int64 [n], out_off uint32 [n + 1] or null, out_task uint32 [out_off[n]] or null} */
+static cook_autoscale_clusters clusters_of(JNIEnv* env, jint n, jobjectArray cols, int* bad_out) {
+  cook_autoscale_clusters cl;
+  uint32_t total = 0;
+  int bad = 0;
+  if (n < 0 || n > COOK_MAX_CLUSTERS) {
+    bad = 1;
+    n = 0;
+  }
+  cl.n = (uint32_t)n;
+  cl.reserved = 0;
+  cl.location = EL(const uint32_t, cols, 0, n);
+  cl.max_pods_outstanding = EL(const int64_t, cols, 1, n);
+  cl.num_synthetic_pods = EL(const int64_t, cols, 2, n);
+  cl.max_total_nodes = EL(const int64_t, cols, 3, n);
+  cl.total_nodes = EL(const int64_t, cols, 4, n);
+  cl.max_total_pods = EL(const int64_t, cols, 5, n);
+  cl.total_pods = EL(const int64_t, cols, 6, n);
+  cl.out_off = csr_off(env, cols, 7, n, &total, &bad);
+  cl.out_task = EL(const uint32_t, cols, 8, total);
+  if (bad || (total && !cl.out_task)) *bad_out = 1;
+  return cl;
+}
+/* cycleAutoscale, then the distribution to the pool's autoscaling compute clusters and the cut per cluster
+ * (cook_cycle_autoscale_clusters).  params, n_offers, offer_skipped, exclude, cap as cycleAutoscale; n_clusters and cluster_cols as
+ * clusters_of; task_idx_out = cap uint32 slots; cluster_off_out = n_clusters + 1 uint32; info_out = one cook_autoscale_info or null;
+ * cluster_info_out = n_clusters cook_autoscale_cluster_info; no_cluster_out = one cook_autoscale_no_cluster or null */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleAutoscaleClusters(JNIEnv* env, jclass c, jlong h, jobject params, jint n_offers,
+                                                                   jobject offer_skipped, jobject exclude, jint n_clusters,
+                                                                   jobjectArray cluster_cols, jobject task_idx_out, jint cap,
+                                                                   jobject cluster_off_out, jobject info_out, jobject cluster_info_out,
+                                                                   jobject no_cluster_out) {
+  int bad = 0;
+  cook_autoscale_params p;
+  cook_autoscale_clusters cl;
+  const jint nc = n_clusters > 0 ? n_clusters : 0;
+  const cook_autoscale_params* in = BUF(const cook_autoscale_params, params);
+  uint32_t* out = BUFN(uint32_t, task_idx_out, cap > 0 ? cap : 0);
+  uint32_t* off = BUFN(uint32_t, cluster_off_out, (uint64_t)nc + 1u);
+  cook_autoscale_info* info = BUF(cook_autoscale_info, info_out);
+  cook_autoscale_cluster_info* cinfo = BUFN(cook_autoscale_cluster_info, cluster_info_out, nc);
+  cook_autoscale_no_cluster* none = BUF(cook_autoscale_no_cluster, no_cluster_out);
+  (void)c;
+  if (bad || !in || !off || !cinfo || n_offers < 0 || cap < 0 || n_clusters < 1 || in->n_exclude > 0x7fffffffu) return COOK_E_INVALID;
+  cl = clusters_of(env, n_clusters, cluster_cols, &bad);
+  p = *in;
+  p.offer_skipped = BUFN(const uint8_t, offer_skipped, n_offers);
+  p.exclude_task = BUFN(const uint32_t, exclude, p.n_exclude);
+  if ((p.n_exclude && !p.exclude_task) || (cap && !out)) return COOK_E_INVALID;
+  return CHECKED(cook_cycle_autoscale_clusters(H(h), &p, &cl, out, (uint32_t)cap, off, info, cinfo, none));
+}
+/* cycleAutoscaleClusters for n engines of one device in ONE call (cook_cycle_autoscale_clusters_multi).  As cycleAutoscaleMulti, and
+ * n_clusters = direct buffer of n jint; cluster_cols = array of n arrays as clusters_of takes them; cluster_off_out / cluster_info_out =
+ * arrays of n direct buffers (n_clusters[i] + 1 uint32; n_clusters[i] cook_autoscale_cluster_info); no_cluster_out = direct buffer of
+ * n cook_autoscale_no_cluster or null */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleAutoscaleClustersMulti(JNIEnv* env, jclass c, jobject handles, jint n, jobject params,
+                                                                        jobject n_offers, jobjectArray offer_skipped, jobjectArray exclude,
+                                                                        jobject n_clusters, jobjectArray cluster_cols,
+                                                                        jobjectArray task_idx_out, jobject caps, jobjectArray cluster_off_out,
+                                                                        jobject info_out, jobjectArray cluster_info_out,
+                                                                        jobject no_cluster_out, jobject rc_out) {
+  cook_engine* es[64];
+  cook_autoscale_params ps[64];
+  const cook_autoscale_params* pp[64];
+  cook_autoscale_clusters cls[64];
+  const cook_autoscale_clusters* clp[64];
+  uint32_t* outs[64];
+  uint32_t* offs[64];
+  cook_autoscale_cluster_info* cinfos[64];
+  uint32_t cs[64];
+  int bad = 0;
+  const jint cnt = n > 0 ? n : 0;
+  const int64_t* hs = BUFN(const int64_t, handles, cnt);
+  const cook_autoscale_params* in = BUFN(const cook_autoscale_params, params, cnt);
+  const int32_t* no = BUFN(const int32_t, n_offers, cnt);
+  const int32_t* ncl = BUFN(const int32_t, n_clusters, cnt);
+  const int32_t* cp = BUFN(const int32_t, caps, cnt);
+  cook_autoscale_info* info = BUFN(cook_autoscale_info, info_out, cnt);
+  cook_autoscale_no_cluster* none = BUFN(cook_autoscale_no_cluster, no_cluster_out, cnt);
+  int* rcs = BUFN(int, rc_out, cnt);
+  jint i;
+  (void)c;
+  if (bad || !hs || !in || !no || !ncl || !cp || n <= 0 || n > 64 || !cluster_cols) return COOK_E_INVALID;
+  for (i = 0; i < n; ++i) {
+    jobjectArray cols;
+    if (no[i] < 0 || cp[i] < 0 || ncl[i] < 1 || ncl[i] > COOK_MAX_CLUSTERS || in[i].n_exclude > 0x7fffffffu) return COOK_E_INVALID;
+    if (i >= (*env)->GetArrayLength(env, cluster_cols)) return COOK_E_INVALID;
+    es[i] = H(hs[i]);
+    ps[i] = in[i];
+    ps[i].offer_skipped = EL(const uint8_t, offer_skipped, i, no[i]);
+    ps[i].exclude_task = EL(const uint32_t, exclude, i, ps[i].n_exclude);
+    cols = (jobjectArray)(*env)->GetObjectArrayElement(env, cluster_cols, i);
+    if (!cols) return COOK_E_INVALID;
+    cls[i] = clusters_of(env, ncl[i], cols, &bad);
+    (*env)->DeleteLocalRef(env, cols);
+    outs[i] = EL(uint32_t, task_idx_out, i, cp[i]);
+    offs[i] = EL(uint32_t, cluster_off_out, i, (uint64_t)ncl[i] + 1u);
+    cinfos[i] = EL(cook_autoscale_cluster_info, cluster_info_out, i, ncl[i]);
+    cs[i] = (uint32_t)cp[i];
+    pp[i] = &ps[i];
+    clp[i] = &cls[i];
+    if ((ps[i].n_exclude && !ps[i].exclude_task) || (cs[i] && !outs[i]) || !offs[i] || !cinfos[i]) return COOK_E_INVALID;
+  }
+  return CHECKED(cook_cycle_autoscale_clusters_multi(es, (uint32_t)n, pp, clp, outs, cs, offs, info, cinfos, none, rcs));
+}
+
 /* ---- the task killers over the running set (cook_sweep_running) -------------------------------------------------------------------
  * rows = n-entry columns {start_ms int64, unknown uint8, max_runtime_ms int64, cancelled uint8, group uint32} (null elements allowed as
  * the header allows them); group_cols = {type uint8, quantile double, multiplier double, job_count uint32 [n_groups], succ_off uint32

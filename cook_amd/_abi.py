@@ -1231,6 +1231,73 @@ class CookAutoscaleInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# ---- Out distributed to the pool's autoscaling compute clusters (cook_cycle_autoscale_clusters: scheduler.clj:1059-1103, autoscale!) -----
+MAX_CLUSTERS = 32
+
+
+def uuid_hash(u) -> int:
+    """Clojure's (hash uuid) of a java.util.UUID = UUID.hashCode: hilo = msb ^ lsb, (int32)(hilo >> 32) ^ (int32)hilo"""
+    hilo = ((u.int >> 64) ^ u.int) & 0xFFFFFFFFFFFFFFFF
+    v = ((hilo >> 32) ^ hilo) & 0xFFFFFFFF
+    return v - (1 << 32) if v & 0x80000000 else v
+
+
+class CookAutoscaleClusters(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("location", _u32p), ("max_pods_outstanding", _i64p),
+                ("num_synthetic_pods", _i64p), ("max_total_nodes", _i64p), ("total_nodes", _i64p), ("max_total_pods", _i64p),
+                ("total_pods", _i64p), ("out_off", _u32p), ("out_task", _u32p)]
+
+
+class CookAutoscaleClusterInfo(C.Structure):
+    _fields_ = [("assigned", C.c_uint32), ("outstanding_removed", C.c_uint32), ("max_launchable", C.c_int64), ("launched", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class CookAutoscaleNoCluster(C.Structure):
+    _fields_ = [("no_cluster", C.c_uint32), ("n_first", C.c_uint32), ("first_task", C.c_uint32 * 10)]
+
+
+CLUSTER_COLUMNS = ("max_pods_outstanding", "num_synthetic_pods", "max_total_nodes", "total_nodes", "max_total_pods", "total_pods")
+
+
+@dataclass
+class AutoscaleClusters:
+    """The pool's autoscaling compute clusters in the order of the reference's collection.  location: 0 = none; outstanding: per
+    cluster the task indices of the resident jobs with an outstanding synthetic pod there (None: none anywhere)."""
+    location: np.ndarray
+    max_pods_outstanding: np.ndarray
+    num_synthetic_pods: np.ndarray
+    max_total_nodes: np.ndarray
+    total_nodes: np.ndarray
+    max_total_pods: np.ndarray
+    total_pods: np.ndarray
+    outstanding: Optional[list] = None
+
+    @property
+    def n(self) -> int:
+        return len(self.location)
+
+    def as_struct(self):
+        """-> (struct, the arrays it points into: keep them alive across the call)"""
+        keep = [np.ascontiguousarray(self.location, dtype=np.uint32)]
+        keep += [np.ascontiguousarray(getattr(self, c), dtype=np.int64) for c in CLUSTER_COLUMNS]
+        for a in keep:
+            assert len(a) == self.n
+        off = task = None
+        if self.outstanding is not None:
+            assert len(self.outstanding) == self.n
+            off = np.zeros(self.n + 1, dtype=np.uint32)
+            off[1:] = np.cumsum([len(x) for x in self.outstanding])
+            flat = [t for x in self.outstanding for t in x]
+            task = np.ascontiguousarray(flat if flat else [0], dtype=np.uint32)
+            keep += [off, task]
+        st = CookAutoscaleClusters(self.n, 0, _ptr(keep[0], _u32p), *[_ptr(a, _i64p) for a in keep[1:7]], _ptr(off, _u32p), _ptr(task, _u32p))
+        return st, keep
+
+
 # ---- the task killers over the running set (cook_sweep_running: scheduler.clj:1888-2016, group.clj:17-44) -------------------------
 SWEEP_LINGERING, SWEEP_STRAGGLERS, SWEEP_CANCELLED = 1, 2, 4
 SWEEP_ALL = 7

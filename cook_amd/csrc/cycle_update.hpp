@@ -385,6 +385,7 @@ void cycle_update(cook_engine* e, UpdateBufs& ub, const cook_cycle_delta* d) {
     seg_scan<SumI>(e, "upd_scan", LoadPendingFlag{pending_new}, (const uint8_t*)nullptr, N2, fincl, e->tmpI);
     KL("upd_pend_ord", upd_pend_ord, div_up(N2, 256), 256, pending_new, (const SumI*)fincl, N2, pend_ord_new);
   }
+  const bool hash_moves = P && e->hash_set == P;
   UpdColSet js{};
   {
     int k = 0;
@@ -416,6 +417,9 @@ void cycle_update(cook_engine* e, UpdateBufs& ub, const cook_cycle_delta* d) {
     // the eligible mask of cook_cycle_set_considerable is indexed by pending ordinal like the job columns: it moves with them; the
     // jobs the delta adds are eligible until the host says otherwise (a fresh mask through cook_cycle_set_considerable)
     if (e->cb && e->cb->has_elig_by_pending) add_col(js, UPD_MAX_COLS, e->cb->elig_by_pending.b, 1, nullptr, 1ull, P_hi);
+    // the (hash uuid) column of cook_cycle_set_job_hashes, by pending ordinal too: a column with every row set moves with the jobs (the
+    // rows the delta appends are unset: hash_set becomes the kept count below); one that was only partly set is dropped
+    if (hash_moves) add_col(js, UPD_MAX_COLS, e->j_hash.b, 4, nullptr, 0ull, P_hi);
   }
   if (P + p_add) KL("upd_compact_cols", upd_compact_cols, div_up(P + p_add, 256), 256, js, (const int*)rm_p, (const SumI*)incl_p, P, p_add, 1u, out);
   stamp(3);
@@ -489,6 +493,7 @@ void cycle_update(cook_engine* e, UpdateBufs& ub, const cook_cycle_delta* d) {
   if (e->has_t_host && n_add > p_add && !at->host) e->t_host_complete = false;  // running rows were added without their hosts
   e->pool_usage_known = false;
   e->n_pending = P2;
+  e->hash_set = hash_moves ? p_keep : 0u;
   e->Kjobs = P2;
   e->K = P2;
   in.K = P2;

@@ -243,6 +243,9 @@ struct cook_engine {
   unsigned rlog_id = 0;  // suffix of this engine's COOK_ROUND_LOG file
   DArr<uint32_t> j_user;
   bool has_j_user = false;
+  // (hash uuid) of the pending jobs by pending ordinal (cook_cycle_set_job_hashes): the leading hash_set rows are set
+  DArr<int32_t> j_hash;
+  unsigned hash_set = 0;
   // ---- class-ordered best fit (classfit.hpp)
   DArr<CfCtl> cf_ctl;
   DArr<uint64_t> cf_attr8;
@@ -877,6 +880,46 @@ int cook_cycle_autoscale_multi(cook_engine** engines, uint32_t n, const cook_aut
   return run_pools_batched(
       engines, n, [&](uint32_t i) { return cook_cycle_autoscale(engines[i], params[i], out(i), cap[i], info ? &info[i] : nullptr); },
       [&](uint32_t i) { cycle_autoscale(engines[i], params[i], out(i), cap[i], info ? &info[i] : nullptr); }, /*rank_part=*/false, rc);
+}
+int cook_cycle_set_job_hashes(cook_engine* e, const int32_t* hash, uint32_t first, uint32_t n) {
+  return guarded(e, [&] { cycle_set_job_hashes(e, hash, first, n); });
+}
+int cook_cycle_autoscale_clusters(cook_engine* e, const cook_autoscale_params* p, const cook_autoscale_clusters* clusters, uint32_t* task_idx,
+                                  uint32_t cap, uint32_t* cluster_off, cook_autoscale_info* info, cook_autoscale_cluster_info* cluster_info,
+                                  cook_autoscale_no_cluster* no_cluster) {
+  if (info) *info = cook_autoscale_info{};
+  if (no_cluster) *no_cluster = cook_autoscale_no_cluster{};
+  return guarded(e, [&] {
+    const AsClusterReq req{clusters, cluster_off, cluster_info, no_cluster};
+    cycle_autoscale(e, p, task_idx, cap, info, &req);
+    prof_collect(e);
+  });
+}
+int cook_cycle_autoscale_clusters_multi(cook_engine** engines, uint32_t n, const cook_autoscale_params* const* params,
+                                        const cook_autoscale_clusters* const* clusters, uint32_t* const* task_idx, const uint32_t* cap,
+                                        uint32_t* const* cluster_off, cook_autoscale_info* info, cook_autoscale_cluster_info* const* cluster_info,
+                                        cook_autoscale_no_cluster* no_cluster, int* rc) {
+  if (!engines || n == 0 || !params || !clusters || !cap || !cluster_off || !cluster_info) return COOK_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i)
+    if (!engines[i] || !params[i] || !clusters[i]) return COOK_E_INVALID;
+  if (!engines_valid(engines, n, false)) return COOK_E_INVALID;
+  auto out = [&](uint32_t i) { return task_idx ? task_idx[i] : nullptr; };
+  for (uint32_t i = 0; i < n; ++i) {
+    if (info) info[i] = cook_autoscale_info{};
+    if (no_cluster) no_cluster[i] = cook_autoscale_no_cluster{};
+  }
+  auto req = [&](uint32_t i) { return AsClusterReq{clusters[i], cluster_off[i], cluster_info[i], no_cluster ? &no_cluster[i] : nullptr}; };
+  return run_pools_batched(
+      engines, n,
+      [&](uint32_t i) {
+        return cook_cycle_autoscale_clusters(engines[i], params[i], clusters[i], out(i), cap[i], cluster_off[i], info ? &info[i] : nullptr,
+                                             cluster_info[i], no_cluster ? &no_cluster[i] : nullptr);
+      },
+      [&](uint32_t i) {
+        const AsClusterReq r = req(i);
+        cycle_autoscale(engines[i], params[i], out(i), cap[i], info ? &info[i] : nullptr, &r);
+      },
+      /*rank_part=*/false, rc);
 }
 
 int cook_sweep_running(cook_engine* e, const cook_running_set* tasks, const cook_straggler_groups* groups, const cook_sweep_params* p,

@@ -74,6 +74,7 @@ void rank_stage(cook_engine* e, const cook_tasks* t, const cook_users* u) {
   }
   // (nothing of the previous table counts from here on: a stage that fails half-way must not leave its usage or its rank behind)
   e->rank_staged = false, e->pool_usage_known = false, e->rank_done = false;
+  e->hash_set = 0;  // (cook_cycle_set_job_hashes' column is by pending ordinal: a stage drops it)
   e->N = N;
   e->U = U;
   e->n_pending = np;

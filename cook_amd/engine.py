@@ -489,6 +489,24 @@ class Engine:
         self._chk(self._lib.cook_cycle_autoscale(self._h, C.byref(p), _p(out, C.c_uint32), cap, C.byref(info)))
         return out[: info.n_out].copy(), info.as_dict()
 
+    def cycle_set_job_hashes(self, hashes, first: int = 0):
+        """Rows [first, first + len(hashes)) of the engine's (hash uuid) column by pending ordinal (cook_cycle_set_job_hashes; A.uuid_hash
+        gives a java.util.UUID's value).  After a cycle_update: first = the kept pending count."""
+        h = np.ascontiguousarray(hashes, dtype=np.int32)
+        self._chk(self._lib.cook_cycle_set_job_hashes(self._h, _p(h, C.c_int32) if len(h) else None, int(first), len(h)))
+
+    def cycle_autoscale_clusters(self, clusters: "A.AutoscaleClusters", max_jobs: int = 1000, scale_factor: float = 1.0, offer_skipped=None,
+                                 exclude_tasks=None, cap: Optional[int] = None):
+        """cycle_autoscale, then what trigger-autoscaling! does with its result (cook_cycle_autoscale_clusters): the jobs distributed to the
+        pool's autoscaling compute clusters and cut per cluster.  -> (launch lists: one array of task indices per cluster, info dict as
+        cycle_autoscale's, cluster info: one dict per cluster (assigned, outstanding_removed, max_launchable, launched), no_cluster dict
+        (no_cluster, first_tasks))."""
+        call = _ClusterCall(self, dict(clusters=clusters, max_jobs=max_jobs, scale_factor=scale_factor, offer_skipped=offer_skipped,
+                                       exclude_tasks=exclude_tasks, cap=cap))
+        self._chk(self._lib.cook_cycle_autoscale_clusters(self._h, C.byref(call.p), C.byref(call.cl), _p(call.out, C.c_uint32), call.cap,
+                                                          _p(call.off, C.c_uint32), C.byref(call.info), call.cinfo, C.byref(call.none)))
+        return call.result()
+
     def sweep_running(self, start_ms, now_ms: int, default_timeout_ms: int = 0, max_timeout_ms: int = 0, what: int = A.SWEEP_ALL,
                       unknown=None, max_runtime_ms=None, cancelled=None, group=None, groups: Optional[dict] = None, cap: Optional[int] = None):
         """The three task killers over the running set (cook_sweep_running): lingering (get-lingering-tasks), stragglers (find-stragglers
@@ -1081,6 +1099,58 @@ def _multi_results(engines, rc, codes, results, raise_errors):
             if isinstance(r, CookError):
                 raise r
     return out
+
+
+class _ClusterCall:
+    """the arguments and outputs of one cook_cycle_autoscale_clusters call, kept alive across it"""
+
+    def __init__(self, e, kw):
+        clusters = kw["clusters"]
+        self.sk = np.ascontiguousarray(kw["offer_skipped"], dtype=np.uint8) if kw.get("offer_skipped") is not None else None
+        self.ex = np.ascontiguousarray(kw["exclude_tasks"] if kw.get("exclude_tasks") is not None else [], dtype=np.uint32)
+        max_jobs = int(kw.get("max_jobs", 1000))
+        self.p = A.CookAutoscaleParams(max_jobs, len(self.ex), float(kw.get("scale_factor", 1.0)),
+                                       _p(self.sk, C.c_uint8) if self.sk is not None else None, _p(self.ex, C.c_uint32) if len(self.ex) else None)
+        self.cl, self.keep = clusters.as_struct()
+        self.n = clusters.n
+        self.cap = int(kw["cap"]) if kw.get("cap") is not None else max(max_jobs, getattr(e, "_rank_np", 0))  # >= max(max_jobs, K)
+        self.out = np.zeros(max(1, self.cap), dtype=np.uint32)
+        self.off = np.zeros(self.n + 1, dtype=np.uint32)
+        self.info = A.CookAutoscaleInfo()
+        self.cinfo = (A.CookAutoscaleClusterInfo * max(1, self.n))()
+        self.none = A.CookAutoscaleNoCluster()
+
+    def result(self, info=None, none=None):
+        info, none = info if info is not None else self.info, none if none is not None else self.none
+        lists = [self.out[self.off[c]: self.off[c + 1]].copy() for c in range(self.n)]
+        return (lists, info.as_dict(), [self.cinfo[c].as_dict() for c in range(self.n)],
+                dict(no_cluster=none.no_cluster, first_tasks=[int(t) for t in none.first_task[: none.n_first]]))
+
+
+def cycle_autoscale_clusters_multi(engines: Sequence[Engine], calls: Sequence[dict], raise_errors: bool = True) -> list:
+    """cycle_autoscale_clusters of several engines (pools of one device) in ONE call (cook_cycle_autoscale_clusters_multi), as
+    cycle_autoscale_multi.  calls: per engine the keywords of Engine.cycle_autoscale_clusters (`clusters` required)."""
+    n = len(engines)
+    if not n:
+        return []
+    assert len(calls) == n
+    cs = [_ClusterCall(e, dict(kw)) for e, kw in zip(engines, calls)]
+    arr = (C.c_void_p * n)(*[e._h for e in engines])
+    pp = (C.c_void_p * n)(*[C.addressof(c.p) for c in cs])
+    clp = (C.c_void_p * n)(*[C.addressof(c.cl) for c in cs])
+    tp = (C.c_void_p * n)(*[c.out.ctypes.data for c in cs])
+    cp = (C.c_uint32 * n)(*[c.cap for c in cs])
+    op = (C.c_void_p * n)(*[c.off.ctypes.data for c in cs])
+    cip = (C.c_void_p * n)(*[C.addressof(c.cinfo) for c in cs])
+    info = (A.CookAutoscaleInfo * n)()
+    none = (A.CookAutoscaleNoCluster * n)()
+    codes = (C.c_int * n)()
+    rc = engines[0]._lib.cook_cycle_autoscale_clusters_multi(arr, n, pp, clp, tp, cp, op, info, cip, none, codes)
+    res = _multi_results(engines, rc, list(codes), [lambda i=i: cs[i].result(info[i], none[i]) for i in range(n)], raise_errors)
+    for i, r in enumerate(res):
+        if isinstance(r, CookError):
+            r.info = info[i].as_dict()
+    return res
 
 
 def cycle_autoscale_multi(engines: Sequence[Engine], calls: Sequence[Optional[dict]], raise_errors: bool = True) -> list:

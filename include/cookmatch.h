@@ -371,6 +371,78 @@ int cook_cycle_autoscale_multi(cook_engine** engines, uint32_t n,
                                cook_autoscale_info* info,                  /* [n] or NULL                            */
                                int* rc);                                   /* [n] or NULL: every engine's own code   */
 
+/* ---- AUTOSCALE, the next step: Out distributed to the pool's autoscaling compute clusters and cut per cluster ------------------------
+ * What trigger-autoscaling! (scheduler.clj:1178-1202) does with Out: distribute-jobs-to-compute-clusters (:1078-1103) with
+ * job->acceptable-compute-clusters (:1059-1076), then autoscale!'s cut per cluster (kubernetes/compute_cluster.clj:606-731), up to the
+ * list of jobs each cluster launches synthetic pods for.  Building the pods stays with the host.
+ *
+ * The pick needs Clojure's (hash uuid) of every pending job: for a java.util.UUID that is UUID.hashCode, with hilo = msb ^ lsb
+ * (the two 64-bit halves) it is (int32)(hilo >> 32) ^ (int32)hilo.  cook_cycle_set_job_hashes writes rows [first, first + n) of an
+ * engine-owned int32 column indexed by PENDING ORDINAL (like cook_cycle_set_considerable's eligible mask).  The engine tracks how many
+ * LEADING rows are set: a range past the pending count, or one that starts behind the set prefix (a gap): COOK_E_INVALID; before
+ * cook_cycle_stage*: COOK_E_STATE; a refused call changes nothing.  cook_cycle_stage* drops the column.  cook_cycle_update moves it with
+ * the job rows when EVERY row was set (the rows a delta appends are unset: the host sets them with first = the kept pending count,
+ * i.e. the new pending count minus the delta's new pending jobs); a column that was only partly set is dropped by an update.  The
+ * call touches no rank, considerable or match state: it may come before or after the cycle. */
+int cook_cycle_set_job_hashes(cook_engine* e, const int32_t* hash, uint32_t first, uint32_t n);
+
+#define COOK_MAX_CLUSTERS 32
+/* The pool's AUTOSCALING compute clusters only, in the order of the reference's collection (nth indexes it: the order is a contract). */
+typedef struct cook_autoscale_clusters {
+  uint32_t n;                          /* 1 .. COOK_MAX_CLUSTERS                                                                 */
+  uint32_t reserved;                   /* 0                                                                                      */
+  const uint32_t* location;            /* [n] compute-cluster->location in the id space of cook_jobs.ckpt_location; 0 = none     */
+  const int64_t* max_pods_outstanding; /* [n] synthetic-pods-config                                                              */
+  const int64_t* num_synthetic_pods;   /* [n] the host's full count of outstanding synthetic pods                                */
+  const int64_t* max_total_nodes;      /* [n]                                                                                    */
+  const int64_t* total_nodes;          /* [n]                                                                                    */
+  const int64_t* max_total_pods;       /* [n]                                                                                    */
+  const int64_t* total_pods;           /* [n]                                                                                    */
+  const uint32_t* out_off;             /* [n + 1] CSR offsets into out_task, from 0, not decreasing; NULL: no outstanding pods   */
+  const uint32_t* out_task;            /* task indices of the still-resident jobs with an outstanding synthetic pod per cluster  */
+} cook_autoscale_clusters;
+typedef struct cook_autoscale_cluster_info {
+  uint32_t assigned;             /* jobs of Out the distribution gave the cluster                                                */
+  uint32_t outstanding_removed;  /* of them, those with an outstanding synthetic pod there                                       */
+  int64_t max_launchable;        /* min(max_pods_outstanding - num_synthetic_pods, max_total_nodes - total_nodes, max_total_pods - total_pods) */
+  uint32_t launched;             /* length of the cluster's launch list                                                          */
+  uint32_t reserved;
+} cook_autoscale_cluster_info;
+typedef struct cook_autoscale_no_cluster {
+  uint32_t no_cluster;           /* jobs of Out no cluster is acceptable to (:no-acceptable-compute-cluster)                     */
+  uint32_t n_first;              /* min(no_cluster, 10)                                                                          */
+  uint32_t first_task[10];       /* the first of them in Out's order (:first-ten-jobs)                                           */
+} cook_autoscale_no_cluster;
+/* Steps 1-5 are cook_cycle_autoscale's (the same code, state rule and refusals), then for every job j of Out, in Out's order:
+ *  6. acceptable clusters: L = ckpt_location[j] (0 when the staged jobs carry no such column).  L == 0: every cluster; otherwise the
+ *     clusters with location == L, in cluster order (a cluster without a location never equals a job's).  None: the job counts
+ *     towards no_cluster.
+ *  7. the choice is the (hash mod count)-th acceptable cluster, Clojure's mod: a floor modulus, in [0, count) for every int32.
+ *  8. each cluster's jobs stay in Out's order (group-by keeps it).
+ *  9. per cluster the jobs named in its outstanding list go; of the rest the first max_launchable stay (<= 0: none).  An outstanding
+ *     index that is in range and no candidate is ignored, as exclude_task is.
+ * task_idx receives the clusters' launch lists one after another, cluster_off[n + 1] delimits them (cluster c: task_idx[cluster_off[c]
+ * .. cluster_off[c + 1])); cluster_info[n]; no_cluster (optional).  info as cook_cycle_autoscale's (n_out = |Out|, whatever was cut).
+ * COOK_E_INVALID: clusters NULL or n out of range, a NULL column, an outstanding index out of range, out_off not from 0 or decreasing
+ * or without out_task, NULL cluster_off / cluster_info, the launch lists longer than cap (info, cluster_info and no_cluster are still
+ * filled) — cap >= max(max_jobs, k) always suffices.  COOK_E_STATE: the hash column does not cover every pending row.  Everything the
+ * host can know is checked in front of the first launch; a refused call changes nothing.  The call makes the stream synchronisations
+ * cook_cycle_autoscale makes on the same inputs with cap > 0: the distribution is enqueued behind Out and its counts and lists come
+ * back in the read-back that returns |Out|.  Integers only.
+ * Not covered: scheduling-capacity-constrained-job-distributor (:1110-1151) picks with rand-nth. */
+int cook_cycle_autoscale_clusters(cook_engine* e, const cook_autoscale_params* p, const cook_autoscale_clusters* clusters, uint32_t* task_idx,
+                                  uint32_t cap, uint32_t* cluster_off /* [n + 1] */, cook_autoscale_info* info,
+                                  cook_autoscale_cluster_info* cluster_info /* [n] */, cook_autoscale_no_cluster* no_cluster /* or NULL */);
+/* ... for every pool of a GPU in one pool batch, exactly as cook_cycle_autoscale_multi: engine i's results, code and message are those
+ * of cook_cycle_autoscale_clusters(engines[i], params[i], clusters[i], task_idx[i], cap[i], cluster_off[i], &info[i], cluster_info[i],
+ * &no_cluster[i]).  COOK_E_INVALID with nothing run: engines, params, clusters, cap, cluster_off or cluster_info NULL, n == 0, a NULL
+ * entry of engines, params or clusters, an engine twice. */
+int cook_cycle_autoscale_clusters_multi(cook_engine** engines, uint32_t n, const cook_autoscale_params* const* params,
+                                        const cook_autoscale_clusters* const* clusters, uint32_t* const* task_idx, const uint32_t* cap,
+                                        uint32_t* const* cluster_off, cook_autoscale_info* info /* [n] or NULL */,
+                                        cook_autoscale_cluster_info* const* cluster_info, cook_autoscale_no_cluster* no_cluster /* [n] or NULL */,
+                                        int* rc /* [n] or NULL */);
+
 /* ---- SWEEP: the three task killers over the cluster's running set (scheduler.clj:1888-2016, group.clj:17-44) --------------------
  * Stateless, like cook_offers_build: the engine handle only picks the device and stream; no rank, considerable, match, offers or
  * rebalance state is read or written.  The running set is every :instance.status/running or /unknown instance (tools.clj:494-506).
