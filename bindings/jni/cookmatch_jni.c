@@ -1130,6 +1130,165 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_sweepRunning(JNIEnv* env, jclass c, 
   return CHECKED(cook_sweep_running(H(h), &t, group_cols ? &g : 0, p, reason, idx, (uint32_t)cap, thr, info));
 }
 
+/* ---- the distributor of a Kubernetes-scheduler pool (cook_kube_distribute) ------------------------------------------------------------
+ * location = n_jobs uint32 or null; draw = n_jobs doubles or null (then the draws come from seed); cluster_cols = {location uint32 [n],
+ * capacity int64 [n]}; choice_out = n_jobs bytes; pos_idx_out = cap uint32 slots (n_jobs always suffices); cluster_off_out =
+ * n_clusters + 1 uint32; cluster_info_out = n_clusters cook_kube_cluster_info; info_out = one cook_kube_info or null */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_kubeDistribute(JNIEnv* env, jclass c, jlong h, jint n_jobs, jobject location, jobject draw,
+                                                           jlong seed, jint n_clusters, jobjectArray cluster_cols, jobject choice_out,
+                                                           jobject pos_idx_out, jint cap, jobject cluster_off_out,
+                                                           jobject cluster_info_out, jobject info_out) {
+  int bad = 0;
+  cook_kube_clusters cl;
+  const jint nj = n_jobs > 0 ? n_jobs : 0, nc = n_clusters > 0 ? n_clusters : 0;
+  const uint32_t* loc = BUFN(const uint32_t, location, nj);
+  const double* dr = BUFN(const double, draw, nj);
+  uint8_t* choice = BUFN(uint8_t, choice_out, nj);
+  uint32_t* idx = BUFN(uint32_t, pos_idx_out, cap > 0 ? cap : 0);
+  uint32_t* off = BUFN(uint32_t, cluster_off_out, (uint64_t)nc + 1u);
+  cook_kube_cluster_info* cinfo = BUFN(cook_kube_cluster_info, cluster_info_out, nc);
+  cook_kube_info* info = BUF(cook_kube_info, info_out);
+  (void)c;
+  if (bad || n_jobs < 0 || cap < 0 || n_clusters < 0 || n_clusters > COOK_MAX_CLUSTERS || !off) return COOK_E_INVALID;
+  cl.n = (uint32_t)n_clusters;
+  cl.reserved = 0;
+  cl.location = EL(const uint32_t, cluster_cols, 0, n_clusters);
+  cl.capacity = EL(const int64_t, cluster_cols, 1, n_clusters);
+  if ((n_jobs && !choice) || (cap && !idx) || (n_clusters && (!cinfo || !cl.location || !cl.capacity))) return COOK_E_INVALID;
+  return CHECKED(cook_kube_distribute(H(h), (uint32_t)n_jobs, loc, dr, (uint64_t)seed, &cl, choice, idx, (uint32_t)cap, off, cinfo, info));
+}
+
+/* ---- a Kubernetes-scheduler pool's cycle (cook_cycle_run_kube) ------------------------------------------------------------------------
+ * rank_first, max_jobs_considered, min_capacity_threshold, seed as cook_kube_cycle; the queue step's parts as cycleRunQueueRelease takes
+ * them, without offers (such a pool has none to edit: carry_offers / release_offers other than 0 are refused by the library);
+ * cluster_cols = {location uint32 [n], capacity int64 [n]}; draw = n_draw doubles or null; task_idx_out = cap uint32 slots
+ * (max_jobs_considered always suffices); cluster_off_out = n_clusters + 1 uint32; cluster_info_out = n_clusters cook_kube_cluster_info;
+ * info_out = one cook_kube_info or null */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunKube(JNIEnv* env, jclass c, jlong h, jint rank_first, jint max_jobs_considered,
+                                                         jlong min_capacity_threshold, jlong seed, jint n_last_offers, jobject offer_skipped,
+                                                         jint n_groups, jobjectArray groups, jint carry_offers, jint carry_usage, jint n_users,
+                                                         jobject tokens_left, jint n_finished, jint n_fin_scalars, jobjectArray finished,
+                                                         jint release_offers, jint release_usage, jint release_groups, jint n_clusters,
+                                                         jobjectArray cluster_cols, jobject draw, jint n_draw, jobject task_idx_out, jint cap,
+                                                         jobject cluster_off_out, jobject cluster_info_out, jobject info_out) {
+  int bad = 0;
+  cook_groups g = groups_of(env, n_groups, groups, &bad);
+  const cook_queue_step s = step_of(env, 1, n_last_offers, offer_skipped, 0, groups ? &g : 0, &bad);
+  const cook_queue_carry cy = carry_of(env, carry_offers, carry_usage, n_users, tokens_left, &bad);
+  const cook_finished f = finished_of(env, n_finished, n_fin_scalars, finished, release_offers, release_usage, release_groups, &bad);
+  const jint nc = n_clusters > 0 ? n_clusters : 0;
+  cook_kube_clusters cl;
+  cook_kube_cycle k;
+  uint32_t* out = BUFN(uint32_t, task_idx_out, cap > 0 ? cap : 0);
+  uint32_t* off = BUFN(uint32_t, cluster_off_out, (uint64_t)nc + 1u);
+  cook_kube_cluster_info* cinfo = BUFN(cook_kube_cluster_info, cluster_info_out, nc);
+  cook_kube_info* info = BUF(cook_kube_info, info_out);
+  (void)c;
+  if (bad || max_jobs_considered < 0 || cap < 0 || n_draw < 0 || n_clusters < 0 || n_clusters > COOK_MAX_CLUSTERS || !off) return COOK_E_INVALID;
+  cl.n = (uint32_t)n_clusters;
+  cl.reserved = 0;
+  cl.location = EL(const uint32_t, cluster_cols, 0, n_clusters);
+  cl.capacity = EL(const int64_t, cluster_cols, 1, n_clusters);
+  k.rank_first = (uint32_t)rank_first;
+  k.max_jobs_considered = (uint32_t)max_jobs_considered;
+  k.min_capacity_threshold = (int64_t)min_capacity_threshold;
+  k.step = &s;
+  k.carry = &cy;
+  k.finished = finished ? &f : 0;
+  k.clusters = &cl;
+  k.draw = BUFN(const double, draw, n_draw);
+  k.n_draw = (uint32_t)n_draw;
+  k.reserved = 0;
+  k.seed = (uint64_t)seed;
+  if ((cap && !out) || (n_clusters && (!cinfo || !cl.location || !cl.capacity)) || (n_draw && !k.draw)) return COOK_E_INVALID;
+  return CHECKED(cook_cycle_run_kube(H(h), &k, out, (uint32_t)cap, off, cinfo, info));
+}
+/* cycleRunKube for n pools of one device in ONE call (cook_cycle_run_kube_multi), for cycles without a release and without a groups
+ * table (a pool that has either goes through cycleRunKube).  params = direct buffer of n records of eight int64 {rank_first,
+ * max_jobs_considered, min_capacity_threshold, seed, n_clusters, n_draw, carry_usage, cap}; cluster_cols = array of n arrays {location,
+ * capacity}; draws = array of n direct buffers or null elements; the outputs as arrays of n direct buffers; info_out = n cook_kube_info
+ * or null; rc_out = n jint or null */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunKubeMulti(JNIEnv* env, jclass c, jobject handles, jint n, jobject params,
+                                                              jobjectArray cluster_cols, jobjectArray draws, jobjectArray task_idx_out,
+                                                              jobjectArray cluster_off_out, jobjectArray cluster_info_out, jobject info_out,
+                                                              jobject rc_out) {
+  cook_engine* es[64];
+  cook_kube_clusters cls[64];
+  cook_kube_cycle ks[64];
+  const cook_kube_cycle* kp[64];
+  cook_queue_step steps[64];
+  cook_queue_carry carries[64];
+  uint32_t* outs[64];
+  uint32_t* offs[64];
+  cook_kube_cluster_info* cinfos[64];
+  uint32_t caps[64];
+  int bad = 0;
+  const jint cnt = n > 0 ? n : 0;
+  const int64_t* hs = BUFN(const int64_t, handles, cnt);
+  const int64_t* ps = BUFN(const int64_t, params, (uint64_t)cnt * 8u);
+  cook_kube_info* info = BUFN(cook_kube_info, info_out, cnt);
+  int* rcs = BUFN(int, rc_out, cnt);
+  jint i;
+  (void)c;
+  if (bad || !hs || !ps || n <= 0 || n > 64 || !cluster_cols) return COOK_E_INVALID;
+  for (i = 0; i < n; ++i) {
+    const int64_t* p = ps + 8 * i;
+    jobjectArray cols;
+    if (p[1] < 0 || p[1] > 0xffffffffll || p[4] < 0 || p[4] > COOK_MAX_CLUSTERS || p[5] < 0 || p[5] > 0x7fffffff || p[7] < 0 || p[7] > 0x7fffffff)
+      return COOK_E_INVALID;
+    if (i >= (*env)->GetArrayLength(env, cluster_cols)) return COOK_E_INVALID;
+    cols = (jobjectArray)(*env)->GetObjectArrayElement(env, cluster_cols, i);
+    cls[i].n = (uint32_t)p[4];
+    cls[i].reserved = 0;
+    cls[i].location = EL(const uint32_t, cols, 0, p[4]);
+    cls[i].capacity = EL(const int64_t, cols, 1, p[4]);
+    if (cols) (*env)->DeleteLocalRef(env, cols);
+    steps[i].offer_skipped = 0;
+    steps[i].remove_mode = 1;
+    steps[i].n_offer_skipped = 0;
+    steps[i].offers = 0;
+    steps[i].groups = 0;
+    carries[i].offers = 0;
+    carries[i].usage = p[6] ? 1u : 0u;
+    carries[i].tokens_left = 0;
+    es[i] = H(hs[i]);
+    ks[i].rank_first = p[0] ? 1u : 0u;
+    ks[i].max_jobs_considered = (uint32_t)p[1];
+    ks[i].min_capacity_threshold = p[2];
+    ks[i].step = &steps[i];
+    ks[i].carry = &carries[i];
+    ks[i].finished = 0;
+    ks[i].clusters = &cls[i];
+    ks[i].draw = EL(const double, draws, i, p[5]);
+    ks[i].n_draw = (uint32_t)p[5];
+    ks[i].reserved = 0;
+    ks[i].seed = (uint64_t)p[3];
+    kp[i] = &ks[i];
+    caps[i] = (uint32_t)p[7];
+    outs[i] = EL(uint32_t, task_idx_out, i, p[7]);
+    offs[i] = EL(uint32_t, cluster_off_out, i, (uint64_t)p[4] + 1u);
+    cinfos[i] = EL(cook_kube_cluster_info, cluster_info_out, i, p[4]);
+    if ((caps[i] && !outs[i]) || !offs[i] || (p[4] && (!cinfos[i] || !cls[i].location || !cls[i].capacity)) || (p[5] && !ks[i].draw))
+      return COOK_E_INVALID;
+  }
+  return CHECKED(cook_cycle_run_kube_multi(es, (uint32_t)n, kp, outs, caps, offs, cinfos, info, rcs));
+}
+/* the cluster byte per considered position of the last Kubernetes cycle (cook_cycle_fetch_kube): choice_out = cap bytes, cap >= the
+ * cycle's max_considerable; n_out = one uint32 */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleFetchKube(JNIEnv* env, jclass c, jlong h, jobject choice_out, jint cap, jobject n_out) {
+  int bad = 0;
+  uint8_t* choice = BUFN(uint8_t, choice_out, cap > 0 ? cap : 0);
+  uint32_t* n = BUF(uint32_t, n_out);
+  uint32_t k = 0;
+  int rc;
+  (void)c;
+  if (bad || cap < 0 || !n) return COOK_E_INVALID;
+  rc = cook_cycle_fetch_kube(H(h), 0, &k); /* (the count first: the buffer's capacity is checked against it) */
+  if (rc != COOK_OK) return rc;
+  if (k > (uint32_t)cap || (k && !choice)) return COOK_E_INVALID;
+  return cook_cycle_fetch_kube(H(h), choice, n);
+}
+
 /* ---- rebalance: rebalancer/init-state + the rebalance loop's decisions ------------------------------------------------- */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_rebalance(JNIEnv* env, jclass c, jlong h, jint r, jobjectArray running,
                                                       jobject running_attrs_cached, jint p, jobjectArray pending,

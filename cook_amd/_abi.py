@@ -1298,6 +1298,53 @@ class AutoscaleClusters:
         return st, keep
 
 
+# ---- the distributor of a Kubernetes-scheduler pool (cook_kube_distribute: scheduler.clj:1110-1151) ---------------------------------
+KUBE_NO_CLUSTER = 0xFF
+KUBE_TILE = 256
+
+
+class CookKubeClusters(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("location", _u32p), ("capacity", _i64p)]
+
+
+class CookKubeClusterInfo(C.Structure):
+    _fields_ = [("assigned", C.c_uint32), ("reserved", C.c_uint32), ("capacity", C.c_int64)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class CookKubeInfo(C.Structure):
+    _fields_ = [("paused", C.c_uint32), ("max_considerable", C.c_uint32), ("available", C.c_int64), ("n_considered", C.c_uint32),
+                ("launched", C.c_uint32), ("no_cluster", C.c_uint32), ("n_first", C.c_uint32), ("first_task", C.c_uint32 * 10),
+                ("exhaustions", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("reserved", "first_task", "n_first")}
+        d["first_tasks"] = [int(x) for x in self.first_task[: self.n_first]]
+        return d
+
+
+class CookKubeCycle(C.Structure):
+    _fields_ = [("rank_first", C.c_uint32), ("max_jobs_considered", C.c_uint32), ("min_capacity_threshold", C.c_int64),
+                ("step", C.c_void_p), ("carry", C.c_void_p), ("finished", C.c_void_p), ("clusters", C.c_void_p), ("draw", _f64p),
+                ("n_draw", C.c_uint32), ("reserved", C.c_uint32), ("seed", C.c_uint64)]
+
+
+def splitmix64(x: int) -> int:
+    """cook_splitmix64 of include/cookmatch.h, in integers modulo 2^64"""
+    m = (1 << 64) - 1
+    z = (x + 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
+def kube_seed_draw(seed: int, k: int) -> float:
+    """the draw of position k when cook_kube_distribute gets no draw column: a 53-bit integer scaled by 2^-53 (exact)"""
+    return float(splitmix64((seed + k) & ((1 << 64) - 1)) >> 11) * 2.0 ** -53
+
+
 # ---- the task killers over the running set (cook_sweep_running: scheduler.clj:1888-2016, group.clj:17-44) -------------------------
 SWEEP_LINGERING, SWEEP_STRAGGLERS, SWEEP_CANCELLED = 1, 2, 4
 SWEEP_ALL = 7

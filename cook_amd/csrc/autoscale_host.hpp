@@ -78,7 +78,7 @@ void cycle_set_job_hashes(cook_engine* e, const int32_t* hash, uint32_t first, u
 void cycle_autoscale(cook_engine* e, const cook_autoscale_params* p, uint32_t* task_idx, uint32_t cap, cook_autoscale_info* info,
                      const AsClusterReq* req = nullptr) {
   if (!p) e->fail(COOK_E_INVALID, "cook_cycle_autoscale: null params");
-  if (!e->cycle_cons_ran || !e->rank_done || !e->match_ran() || !e->cb)
+  if (!e->cycle_cons_ran || !e->rank_done || !e->match_ran() || !e->cb || e->kube_last)
     e->fail(COOK_E_STATE, "cook_cycle_autoscale needs the last cook_cycle_run (or cook_cycle_run_rank + cook_cycle_match_multi) to have run the "
                           "considerable filters, with no stage / cook_cycle_update / cook_considerable since");
   if (!std::isfinite(p->scale_factor)) e->fail(COOK_E_INVALID, "cook_cycle_autoscale: scale_factor is not finite");

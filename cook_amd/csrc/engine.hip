@@ -58,6 +58,7 @@ struct UpdateBufs;   // cycle_update.hpp
 struct UserStatsBufs;  // user_stats_host.hpp
 struct AutoscaleBufs;  // autoscale_host.hpp
 struct SweepBufs;      // sweep_host.hpp
+struct KubeBufs;       // kube_host.hpp
 struct UnschedBufs;    // unscheduled_host.hpp
 struct UsageBufs;      // usage_host.hpp
 struct QueueBufs;      // queue_host.hpp
@@ -198,6 +199,7 @@ struct cook_engine {
   // the last cycle ran the considerable filters under a staged user state, and nothing has replaced that state, the rank or the match
   // since (cook_cycle_autoscale reads all three)
   bool cycle_cons_ran = false;
+  bool kube_last = false;  // the last cycle ended in a distribution (cook_cycle_run_kube): job_to_offer holds 0 / -1 = launched / not, no placement ran
   // ---- the standing queue of the queue cycles (queue_host.hpp): `ranked` is the queue a match cycle may consume — the last cycle took its
   // jobs from it and nothing has shifted or dropped the rows it points at since (with rank_done and a match that has run: that cycle is complete)
   bool q_valid = false;
@@ -235,6 +237,7 @@ struct cook_engine {
   std::unique_ptr<UserStatsBufs> usb;  // cook_user_stats* (allocated on first use)
   std::unique_ptr<AutoscaleBufs> asb;  // cook_cycle_autoscale (allocated on first use)
   std::unique_ptr<SweepBufs> swb;      // cook_sweep_running (allocated on first use)
+  std::unique_ptr<KubeBufs> kub;       // cook_kube_distribute (allocated on first use)
   std::unique_ptr<UnschedBufs> unb;    // cook_unscheduled (allocated on first use)
   std::unique_ptr<UsageBufs> ugb;      // cook_usage_breakdown* (allocated on first use)
   MatchIn last_in{};  // the MatchIn of the last match run (K, j_index as used)
@@ -342,6 +345,7 @@ static void limiter_filter_finish(cook_engine* e, const unsigned* h);
 #include "usage_host.hpp"
 #include "rebal_resident_host.hpp"  // the rebalancer's stage from the resident cycle state: RebalBufs, ConsBufs' eligible mask, cycle_update.hpp's element copies
 #include "cycle_host.hpp"      // a cycle's front parts (rank or queue step, considerable filters) and its single-pool entry: needs the two above them
+#include "kube_host.hpp"       // a Kubernetes-scheduler pool: the distributor, and the cycle that ends in it (needs the front parts above)
 
 }  // namespace
 
@@ -796,6 +800,7 @@ int cook_cycle_fetch(cook_engine* e, uint32_t* ranked, uint32_t* n_ranked, int32
     rank_fetch(e, ranked, n_ranked, nullptr);
     if (n_considered) *n_considered = e->cycle_considered;
     match_fetch(e, e->cycle_considered, job_to_offer, nullptr, head_matched);
+    if (e->kube_last && job_to_offer) std::fill(job_to_offer, job_to_offer + e->cycle_considered, -1);  // (no placement: the launched jobs' marks are the advance's)
   });
 }
 
@@ -929,6 +934,45 @@ int cook_sweep_running(cook_engine* e, const cook_running_set* tasks, const cook
     sweep_running(e, tasks, groups, p, reason, idx, cap, group_threshold_s, info);
     prof_collect(e);
   });
+}
+
+int cook_kube_distribute(cook_engine* e, uint32_t n_jobs, const uint32_t* location, const double* draw, uint64_t seed,
+                         const cook_kube_clusters* clusters, uint8_t* choice, uint32_t* pos_idx, uint32_t cap, uint32_t* cluster_off,
+                         cook_kube_cluster_info* cluster_info, cook_kube_info* info) {
+  if (info) *info = cook_kube_info{};
+  return guarded(e, [&] {
+    kube_distribute_run(e, n_jobs, location, draw, seed, clusters, choice, pos_idx, cap, cluster_off, cluster_info, info);
+    prof_collect(e);
+  });
+}
+
+int cook_cycle_run_kube(cook_engine* e, const cook_kube_cycle* c, uint32_t* task_idx, uint32_t cap, uint32_t* cluster_off,
+                        cook_kube_cluster_info* cluster_info, cook_kube_info* info) {
+  if (info) *info = cook_kube_info{};
+  return guarded(e, [&] {
+    cycle_run_kube(e, c, task_idx, cap, cluster_off, cluster_info, info);
+    prof_collect(e);
+  });
+}
+int cook_cycle_run_kube_multi(cook_engine** engines, uint32_t n, const cook_kube_cycle* const* cycles, uint32_t* const* task_idx,
+                              const uint32_t* cap, uint32_t* const* cluster_off, cook_kube_cluster_info* const* cluster_info,
+                              cook_kube_info* info, int* rc) {
+  if (!engines || n == 0 || !cycles || !cap || !cluster_off || !cluster_info) return COOK_E_INVALID;
+  for (uint32_t i = 0; i < n; ++i)
+    if (!engines[i] || !cycles[i]) return COOK_E_INVALID;
+  if (!engines_valid(engines, n, false)) return COOK_E_INVALID;
+  auto out = [&](uint32_t i) { return task_idx ? task_idx[i] : nullptr; };
+  if (info)
+    for (uint32_t i = 0; i < n; ++i) info[i] = cook_kube_info{};
+  return run_pools_batched(
+      engines, n,
+      [&](uint32_t i) { return cook_cycle_run_kube(engines[i], cycles[i], out(i), cap[i], cluster_off[i], cluster_info[i], info ? &info[i] : nullptr); },
+      [&](uint32_t i) { cycle_run_kube(engines[i], cycles[i], out(i), cap[i], cluster_off[i], cluster_info[i], info ? &info[i] : nullptr); },
+      /*rank_part=*/false, rc);
+}
+int cook_cycle_fetch_kube(cook_engine* e, uint8_t* choice, uint32_t* n_out) {
+  if (n_out) *n_out = 0;
+  return guarded(e, [&] { cycle_fetch_kube(e, choice, n_out); });
 }
 
 int cook_rebalance_stage(cook_engine* e, const cook_tasks* running, const uint8_t* running_attrs_cached, const cook_jobs* pending,

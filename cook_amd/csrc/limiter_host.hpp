@@ -135,7 +135,7 @@ void limiter_spend(cook_engine* e, const uint8_t* offer_skipped, uint32_t n_offe
   if (!k) return;
   unsigned* cnt = b.counters.ensure(REL_CNT_WORDS);
   memset_async(e, cnt, 0, REL_CNT_WORDS * 4);
-  const uint8_t* skipped = (offer_skipped && e->M) ? h2d_opt(e, b.skipped, offer_skipped, e->M) : nullptr;
+  const uint8_t* skipped = (offer_skipped && e->M && !e->kube_last) ? h2d_opt(e, b.skipped, offer_skipped, e->M) : nullptr;  // (a Kubernetes cycle has no offer indices)
   limiter_spend_launch(e, cnt, skipped, k, spend_ms, true);
   pinned_copy(e, e->h_scratch + REL_H_CNT, cnt, REL_CNT_WORDS * 4, hipMemcpyDeviceToHost);
   sync(e);

@@ -462,6 +462,7 @@ static void match_run_rounds(cook_engine* e, const MatchIn& in, const MatchState
 // with the other pools of the device.
 void match_run_device(cook_engine* e, unsigned K, const uint32_t* j_index, bool defer = false) {
   e->placement_drop();  // (whatever was set up and not run: this match takes its state and its buffers)
+  e->kube_last = false;
   MatchIn in = e->min;
   in.K = K;
   in.j_index = j_index;

@@ -78,7 +78,7 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   QueueBufs& b = bufs(e->qb);
   MatchIn& in = e->min;
   const unsigned n = e->n_ranked, k = e->cycle_considered, G = e->G, M_old = e->M;
-  const bool fold = G && k && in.j_group && !(s && s->groups);
+  const bool fold = G && k && in.j_group && !(s && s->groups) && !e->kube_last;  // (a Kubernetes cycle's launched jobs have no host yet)
   unsigned* cnt = b.counters.ensure(REL_CNT_WORDS);
   const bool advance = k && n, release = release_active(f), churn = churn_active(q.hosts), reserve = reserve_active(q.reservations),
              spend = limiter_spend_due(e, advance ? k : 0u);
@@ -91,10 +91,11 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
     unsigned* add_cnt = b.add_cnt.ensure(std::max(1u, G));
     unsigned* cursor = b.cursor.ensure(std::max(1u, G));
     if (fold) memset_async(e, add_cnt, 0, (size_t)G * 4), memset_async(e, cursor, 0, (size_t)G * 4);
-    skipped = (s && s->offer_skipped && M_old) ? h2d_opt(e, b.skipped, s->offer_skipped, M_old) : nullptr;
+    // (behind a Kubernetes cycle job_to_offer is 0 / -1 = launched / not, no offer index: offer_skipped says nothing about those jobs and is not read)
+    skipped = (s && s->offer_skipped && M_old && !e->kube_last) ? h2d_opt(e, b.skipped, s->offer_skipped, M_old) : nullptr;
     const int32_t* j2o = e->m_j2o.ptr();
     const uint32_t* j_index = e->j_index.ptr();
-    KM<q_mark_removed, 256>(e, "q_mark_removed", div_up(k, 256), e->q_last_pos, j2o, k, n, skipped, (unsigned)(s && s->remove_mode == 1u), j_index,
+    KM<q_mark_removed, 256>(e, "q_mark_removed", div_up(k, 256), e->q_last_pos, j2o, k, n, skipped, (unsigned)((s && s->remove_mode == 1u) || e->kube_last), j_index,
         in.j_group, G, (unsigned)fold, removed, add_cnt, cnt);
     if (c) carried = carry_enqueue(e, c, skipped, k);  // (the carried offer columns are the staged ones from here: the fold below reads hosts and attributes, which stay)
     // ---- the queue: stable compaction, back into the resident buffer ----------------------------------------------------------------

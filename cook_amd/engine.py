@@ -556,6 +556,58 @@ class Engine:
         return dict(reason=reason[:n].copy(), lingering=idx[:L].copy(), stragglers=idx[L:L + S].copy(),
                     cancelled=idx[L + S:L + S + info.cancelled].copy(), threshold_s=thr[:G].copy(), info=info.as_dict())
 
+    def kube_distribute(self, n_jobs: int, cluster_location, cluster_capacity, location=None, draw=None, seed: int = 0,
+                        cap: Optional[int] = None):
+        """The distributor of a Kubernetes-scheduler pool (cook_kube_distribute: scheduling-capacity-constrained-job-distributor,
+        scheduler.clj:1110-1151) over jobs 0 .. n_jobs-1 in order.  cluster_location / cluster_capacity: per compute cluster, in the
+        pool's order (location 0 = none; capacity = cc/max-launchable, int64).  location: per job, 0 = none (None: all 0); draw: per job
+        a float64 in [0, 1) (None: generated from `seed`, A.kube_seed_draw).  -> dict(choice [n_jobs] uint8 (A.KUBE_NO_CLUSTER: none),
+        lists: one array of job positions per cluster, off [n + 1], cluster_info: one dict per cluster (assigned, capacity), info)."""
+        K = int(n_jobs)
+        cl_loc = np.ascontiguousarray(cluster_location, dtype=np.uint32)
+        cl_cap = np.ascontiguousarray(cluster_capacity, dtype=np.int64)
+        n = len(cl_loc)
+        assert len(cl_cap) == n, "one capacity per cluster"
+        loc = np.ascontiguousarray(location, dtype=np.uint32) if location is not None else None
+        dr = np.ascontiguousarray(draw, dtype=np.float64) if draw is not None else None
+        assert all(c is None or len(c) >= K for c in (loc, dr)), "every job column has n_jobs entries"
+        cl = A.CookKubeClusters(n, 0, _p(cl_loc, C.c_uint32) if n else None, _p(cl_cap, C.c_int64) if n else None)
+        cap = K if cap is None else int(cap)
+        choice = np.zeros(max(1, K), dtype=np.uint8)
+        idx = np.zeros(max(1, cap), dtype=np.uint32)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        cinfo = (A.CookKubeClusterInfo * max(1, n))()
+        info = A.CookKubeInfo()
+        rc = self._lib.cook_kube_distribute(self._h, K, _p(loc, C.c_uint32) if loc is not None and K else None,
+                                            _p(dr, C.c_double) if dr is not None and K else None, C.c_uint64(int(seed) & (2 ** 64 - 1)), C.byref(cl),
+                                            _p(choice, C.c_uint8), _p(idx, C.c_uint32), cap, _p(off, C.c_uint32), cinfo, C.byref(info))
+        self.last_kube = dict(choice=choice[:K].copy(), off=off.copy(), cluster_info=[cinfo[c].as_dict() for c in range(n)],
+                              info=info.as_dict())  # (filled in on "more than cap" too)
+        self._chk(rc)
+        return dict(self.last_kube, lists=[idx[off[c]:off[c + 1]].copy() for c in range(n)])
+
+    def cycle_run_kube(self, cluster_location, cluster_capacity, max_jobs_considered: int = 500, min_capacity_threshold: int = 0,
+                       rank_first: bool = False, draw=None, seed: int = 0, carry=None, finished=None, cap: Optional[int] = None, **step):
+        """A Kubernetes-scheduler pool's cycle (cook_cycle_run_kube: handle-kubernetes-scheduler-pool, scheduler.clj:1747-1810): the gate
+        over the clusters' capacities, then a fresh rank (rank_first) or a queue step with every considered job leaving the queue (carry,
+        finished and the step's keywords as cycle_run_queue_release takes them), the considerable filters, and the distributor over the
+        considered jobs.  -> dict(lists: one array of TASK indices per cluster, off, cluster_info, info); info["paused"] = 1: nothing ran."""
+        call = _KubeCall(self, dict(cluster_location=cluster_location, cluster_capacity=cluster_capacity, max_jobs_considered=max_jobs_considered,
+                                    min_capacity_threshold=min_capacity_threshold, rank_first=rank_first, draw=draw, seed=seed, carry=carry,
+                                    finished=finished, cap=cap, **step))
+        rc = self._lib.cook_cycle_run_kube(self._h, C.byref(call.c), _p(call.out, C.c_uint32), call.cap, _p(call.off, C.c_uint32), call.cinfo,
+                                           C.byref(call.info))
+        self.last_kube = call.result(lists=False)  # (filled in on "more than cap" too)
+        self._chk(rc)
+        return call.result()
+
+    def cycle_fetch_kube(self) -> np.ndarray:
+        """the cluster byte per considered position of the last Kubernetes cycle (A.KUBE_NO_CLUSTER: none)"""
+        n = C.c_uint32(0)
+        out = np.zeros(max(1, getattr(self, "_rank_np", 0)), dtype=np.uint8)
+        self._chk(self._lib.cook_cycle_fetch_kube(self._h, _p(out, C.c_uint8), C.byref(n)))
+        return out[: n.value].copy()
+
     # ---- rebalancer ------------------------------------------------------------------------------------------
     def rebalance_stage(self, running: A.Tasks, pending: A.Jobs, pending_job_id, pending_priority, users: A.Users,
                         spare: A.HostSpare, rparams: A.CookRebalanceParams, host_attrs: Optional[A.Offers] = None,
@@ -880,6 +932,66 @@ class _StatsOut:
 
     def result(self) -> dict:
         return A.user_stats_result(self.per_user[:self.n] if self.device_ptr is None else None, self.state[:self.n], self.totals)
+
+
+class _KubeCall:
+    """the argument block and output buffers of one engine's cook_cycle_run_kube"""
+
+    def __init__(self, e: "Engine", kw: dict):
+        kw = dict(kw)
+        self.cl_loc = np.ascontiguousarray(kw.pop("cluster_location"), dtype=np.uint32)
+        self.cl_cap = np.ascontiguousarray(kw.pop("cluster_capacity"), dtype=np.int64)
+        self.n = n = len(self.cl_loc)
+        assert len(self.cl_cap) == n, "one capacity per cluster"
+        self.cl = A.CookKubeClusters(n, 0, _p(self.cl_loc, C.c_uint32) if n else None, _p(self.cl_cap, C.c_int64) if n else None)
+        mjc = int(kw.pop("max_jobs_considered", 500))
+        draw = kw.pop("draw", None)
+        self.draw = np.ascontiguousarray(draw, dtype=np.float64) if draw is not None else None
+        carry, finished = kw.pop("carry", None), kw.pop("finished", None)
+        cap = kw.pop("cap", None)
+        thr, rank_first, seed = int(kw.pop("min_capacity_threshold", 0)), bool(kw.pop("rank_first", False)), int(kw.pop("seed", 0))
+        n_draw = kw.pop("n_draw", None)
+        self.step, self.keep = e._queue_step(**kw) if kw else (None, None)
+        self.parts = [p.as_struct() if p is not None else (None, None) for p in (carry, finished)]
+        ref = lambda s: C.cast(C.pointer(s), C.c_void_p) if s is not None else None  # noqa: E731
+        self.c = A.CookKubeCycle(int(rank_first), mjc, thr, ref(self.step), ref(self.parts[0][0]), ref(self.parts[1][0]), ref(self.cl),
+                                 _p(self.draw, C.c_double) if self.draw is not None and len(self.draw) else None,
+                                 (len(self.draw) if self.draw is not None else 0) if n_draw is None else int(n_draw), 0, seed & (2 ** 64 - 1))
+        self.cap = mjc if cap is None else int(cap)
+        self.out = np.zeros(max(1, self.cap), dtype=np.uint32)
+        self.off = np.zeros(n + 1, dtype=np.uint32)
+        self.cinfo = (A.CookKubeClusterInfo * max(1, n))()
+        self.info = A.CookKubeInfo()
+
+    def result(self, lists: bool = True) -> dict:
+        r = dict(off=self.off.copy(), cluster_info=[self.cinfo[c].as_dict() for c in range(self.n)], info=self.info.as_dict())
+        if lists:
+            r["lists"] = [self.out[self.off[c]:self.off[c + 1]].copy() for c in range(self.n)]
+        return r
+
+
+def cycle_run_kube_multi(engines: Sequence["Engine"], calls: Sequence[dict], raise_errors: bool = True):
+    """cycle_run_kube of several engines (the Kubernetes-scheduler pools of one device) in ONE call (cook_cycle_run_kube_multi).  calls:
+    per engine the keywords of Engine.cycle_run_kube.  -> one result per engine; raise_errors False: (results, codes), a refused engine's
+    result as far as the library filled it."""
+    n = len(engines)
+    cs = [_KubeCall(e, kw) for e, kw in zip(engines, calls)]
+    hs = (C.c_void_p * n)(*[e._h for e in engines])
+    cyc = (C.c_void_p * n)(*[C.cast(C.pointer(c.c), C.c_void_p) for c in cs])
+    outs = (C.c_void_p * n)(*[c.out.ctypes.data for c in cs])
+    caps = (C.c_uint32 * n)(*[c.cap for c in cs])
+    offs = (C.c_void_p * n)(*[c.off.ctypes.data for c in cs])
+    cinfos = (C.c_void_p * n)(*[C.cast(c.cinfo, C.c_void_p) for c in cs])
+    infos = (A.CookKubeInfo * n)()
+    rcs = (C.c_int * n)()
+    rc = engines[0]._lib.cook_cycle_run_kube_multi(hs, n, cyc, outs, caps, offs, cinfos, infos, rcs)
+    for c, i in zip(cs, infos):
+        c.info = i
+    res = [c.result() for c in cs]
+    if raise_errors:
+        _check_multi(engines, rc)
+        return res
+    return res, [int(x) for x in rcs]
 
 
 def _check_multi(engines, rc):

@@ -429,7 +429,8 @@ typedef struct cook_autoscale_no_cluster {
  * host can know is checked in front of the first launch; a refused call changes nothing.  The call makes the stream synchronisations
  * cook_cycle_autoscale makes on the same inputs with cap > 0: the distribution is enqueued behind Out and its counts and lists come
  * back in the read-back that returns |Out|.  Integers only.
- * Not covered: scheduling-capacity-constrained-job-distributor (:1110-1151) picks with rand-nth. */
+ * scheduling-capacity-constrained-job-distributor (:1110-1151), the distributor of a Kubernetes-scheduler pool, is cook_kube_distribute
+ * below. */
 int cook_cycle_autoscale_clusters(cook_engine* e, const cook_autoscale_params* p, const cook_autoscale_clusters* clusters, uint32_t* task_idx,
                                   uint32_t cap, uint32_t* cluster_off /* [n + 1] */, cook_autoscale_info* info,
                                   cook_autoscale_cluster_info* cluster_info /* [n] */, cook_autoscale_no_cluster* no_cluster /* or NULL */);
@@ -442,6 +443,65 @@ int cook_cycle_autoscale_clusters_multi(cook_engine** engines, uint32_t n, const
                                         uint32_t* const* cluster_off, cook_autoscale_info* info /* [n] or NULL */,
                                         cook_autoscale_cluster_info* const* cluster_info, cook_autoscale_no_cluster* no_cluster /* [n] or NULL */,
                                         int* rc /* [n] or NULL */);
+
+/* ---- KUBE: the distributor of a Kubernetes-scheduler pool ----------------------------------------------------------------------------
+ * scheduling-capacity-constrained-job-distributor (scheduler.clj:1110-1151), which handle-kubernetes-scheduler-pool (:1747-1810) hands
+ * its considerable jobs to.  Stateless, like cook_sweep_running: the engine handle only picks the device and stream; no rank,
+ * considerable, match, offers or rebalance state is read or written.
+ * The clusters are the pool's n compute clusters in the caller's order, 0 <= n <= COOK_MAX_CLUSTERS; capacity is cc/max-launchable
+ * (kubernetes/compute_cluster.clj:571-604), computed by the host; it may be zero or negative (such a cluster is never available).
+ * The jobs 0 .. n_jobs-1 go in order, sequentially, with cap[c] starting at capacity[c].  For job k:
+ *  1. acceptable clusters: step 6 of cook_cycle_autoscale_clusters with L = location[k] (location NULL: 0).  L == 0: every cluster;
+ *     otherwise the clusters with location == L, in cluster order.
+ *  2. available clusters: the acceptable ones with cap[c] > 0 (:1128-1139), still in cluster order; m = their number.
+ *  3. m == 0: the job counts towards no_cluster (:no-acceptable-compute-cluster, :1140-1141), choice[k] = COOK_KUBE_NO_CLUSTER; the first
+ *     ten such jobs are reported (:first-ten-jobs, :1147-1150).
+ *  4. otherwise rand-nth (:1142), which is (nth coll (int (* (count coll) (Math/random)))), with the draw u_k as the random number:
+ *     r = min((uint32)(int32)trunc((double)m * u_k), m - 1) — ONE fp64 multiply, round to nearest —, the job goes to the r-th available
+ *     cluster c, choice[k] = c, and cap[c] -= 1 (:1143-1144).  No u < 1 reaches the clamp: for m <= 32 the product m * u rounds to a
+ *     double below m (m * 2^-53 is at least half a unit in the last place below m, and exactly half only for a power of two, where the
+ *     product is exact).
+ *  5. each cluster's jobs stay in job order (group-by keeps it): pos_idx holds the clusters' lists of job positions one after another,
+ *     cluster_off[n + 1] delimits them.
+ * The draws.  draw non-NULL: u_k = draw[k]; a value that is NaN or outside [0, 1): COOK_E_INVALID, checked on the host before the first
+ * launch.  draw NULL: u_k = (double)(cook_splitmix64(seed + k) >> 11) * 2^-53 (exact: a 53-bit integer scaled), where, in uint64
+ * arithmetic modulo 2^64,
+ *     cook_splitmix64(x): z = x + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *                         z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31).
+ * One draw per POSITION is the contract: the reference draws only for the jobs with a non-empty available set, which has the same
+ * distribution (the draws are independent and a job without an available cluster ignores its own) but not the same stream.
+ * cluster_info[c] = {jobs given to c, capacity[c]}.  info: paused = 0, available = the saturated int64 sum of the raw capacities
+ * (negatives included, the reduce + of :1767), max_considerable = n_considered = n_jobs, launched = the lists' total length, no_cluster,
+ * n_first = min(no_cluster, 10) with first_task = their positions, exhaustions = clusters whose capacity the walk brought to zero.
+ * COOK_E_INVALID: n_jobs > INT32_MAX, clusters NULL or n > COOK_MAX_CLUSTERS, a NULL column with n > 0, a bad draw, NULL choice with
+ * n_jobs > 0, NULL pos_idx with cap > 0, NULL cluster_off or cluster_info (the latter with n > 0), the lists longer than cap (choice,
+ * cluster_off, cluster_info and info are still filled) — cap >= n_jobs always suffices.  COOK_E_DEVICE: the walk did not end within
+ * its pass bound (an internal error).  The first call on a handle allocates device memory. */
+#define COOK_KUBE_NO_CLUSTER 0xFFu
+#define COOK_KUBE_TILE 256 /* jobs the walk evaluates at once: a tile holds at most one exhaustion per pass */
+typedef struct cook_kube_clusters {
+  uint32_t n;               /* 0 .. COOK_MAX_CLUSTERS                                                                  */
+  uint32_t reserved;        /* 0                                                                                       */
+  const uint32_t* location; /* [n] compute-cluster->location in the id space of cook_jobs.ckpt_location; 0 = none      */
+  const int64_t* capacity;  /* [n] cc/max-launchable                                                                   */
+} cook_kube_clusters;
+typedef struct cook_kube_cluster_info {
+  uint32_t assigned;        /* jobs the distribution gave the cluster = the length of its list                         */
+  uint32_t reserved;
+  int64_t capacity;         /* as given                                                                                */
+} cook_kube_cluster_info;
+typedef struct cook_kube_info {
+  uint32_t paused;          /* 0 (the gate of :1778 belongs to the pool's cycle)                                        */
+  uint32_t max_considerable;
+  int64_t available;        /* the sum of the raw capacities, saturated                                                 */
+  uint32_t n_considered, launched, no_cluster, n_first;
+  uint32_t first_task[10];
+  uint32_t exhaustions, reserved;
+} cook_kube_info;
+int cook_kube_distribute(cook_engine* e, uint32_t n_jobs, const uint32_t* location /* [n_jobs] or NULL */,
+                         const double* draw /* [n_jobs] or NULL */, uint64_t seed, const cook_kube_clusters* clusters,
+                         uint8_t* choice /* [n_jobs] */, uint32_t* pos_idx, uint32_t cap, uint32_t* cluster_off /* [n + 1] */,
+                         cook_kube_cluster_info* cluster_info /* [n] */, cook_kube_info* info /* or NULL */);
 
 /* ---- SWEEP: the three task killers over the cluster's running set (scheduler.clj:1888-2016, group.clj:17-44) --------------------
  * Stateless, like cook_offers_build: the engine handle only picks the device and stream; no rank, considerable, match, offers or
@@ -963,6 +1023,60 @@ int cook_cycle_fetch_limiters(cook_engine* e, int64_t* tokens, int64_t* last_upd
 int cook_cycle_fetch_rate_limit(cook_engine* e, uint32_t* rate_limited, uint32_t* passed);
 /* the counts of the last cycle; all 0 without limiters */
 int cook_cycle_limiter_info(cook_engine* e, cook_limiter_info* out);
+
+/* ---- KUBE CYCLE (the distributor, cook_kube_distribute, is declared with the autoscaling calls above) ------------------------------
+ * A Kubernetes-scheduler pool's cycle as ONE call (handle-kubernetes-scheduler-pool, scheduler.clj:1747-1810): gate, consider, distribute.
+ *  Gate (:1767-1778): available = the saturated int64 sum of the raw capacities; max_considerable = min(max_jobs_considered,
+ *   max(available, 0)), clamped to uint32.  available > min_capacity_threshold false (strict; n == 0 for any threshold >= 0): the call is
+ *   PAUSED — info->paused = 1 with available and max_considerable, cluster_off all 0, cluster_info filled — and changes nothing: no
+ *   advance runs, the queue is untouched, the last cycle's record is still pending (:1801-1808 without the sleep, which is the host's).
+ *  Consider: rank_first = 1: a fresh rank, as cook_cycle_run; 0: a queue step, as cook_cycle_run_queue_release(step, carry, finished)
+ *   with remove_mode taken as 1 whatever step says (every considered job leaves the queue, :1792-1794; step NULL: defaults).  Then the
+ *   considerable filters over the standing queue and take max_considerable.  The staged offers are never read.
+ *  Distribute: cook_kube_distribute's steps 1-5 over the considered jobs in considered order, L = the job's ckpt_location; the draw of
+ *   considered position k is draw[k] (n_draw >= max_considerable values, each of the first max_considerable in [0, 1)) or the seed rule.
+ *  task_idx receives the clusters' lists of TASK indices one after another, cluster_off[n + 1] delimits them; info->first_task holds task
+ *  indices too.  More than cap entries: COOK_E_INVALID with info, cluster_off and cluster_info filled (the cycle has run); cap >=
+ *  max_jobs_considered always suffices.
+ * What the engine holds afterwards: the cycle is the last cycle for everything that reads positions — cook_cycle_fetch returns the
+ *  queue, n_considered and a job_to_offer of all -1; cook_cycle_fetch_considerable works; cook_cycle_fetch_kube returns the cluster byte
+ *  per considered position.  cook_match_explain, cook_match_metrics* and cook_cycle_autoscale* return COOK_E_STATE: no placement ran.
+ * The next advance (of a Kubernetes cycle or of any queue cycle) treats a job that got a cluster as the cycle's kept placement for the
+ *  user state: with carry->usage = 1 its resources join usage_* and the pool usage in considered order (the order rule of the carry),
+ *  its user spends one token (staged tokens, or the engine's limiters), as process-task-post-launch! does for both handlers (:866-872).
+ *  It adds nothing to the groups' cotask lists (the host is unknown until kube-scheduler binds; pass step->groups when it is known).
+ *  Jobs without a cluster carry nothing and spend nothing.
+ *  offer_skipped (of the step, of cook_cycle_limiters_spend) is NOT read behind a Kubernetes cycle: that cycle's job_to_offer names no
+ *  offer, so a skipped offer says nothing about its jobs; its length is still checked as the step always checks it.
+ * Refused before anything changes: COOK_E_INVALID — c, clusters, cluster_off or (n > 0) cluster_info NULL, n > COOK_MAX_CLUSTERS, a NULL
+ *  cluster column, step->offers, carry->offers = 1, finished->offers = 1 (such a pool has no offer table to edit), n_draw <
+ *  max_considerable, a draw that is NaN or outside [0, 1), cap > 0 with task_idx NULL, and whatever the queue step refuses;
+ *  COOK_E_STATE — before cook_cycle_stage, a queue step without a completed cycle, between a deferred set-up (cook_cycle_run_rank*)
+ *  and cook_cycle_match_multi. */
+typedef struct cook_kube_cycle {
+  uint32_t rank_first;               /* 1: rank, consider, distribute; 0: a queue step                                   */
+  uint32_t max_jobs_considered;
+  int64_t min_capacity_threshold;
+  const cook_queue_step* step;       /* rank_first = 0; NULL: defaults.  offers must be NULL; groups: the cotask table when the hosts are known */
+  const cook_queue_carry* carry;     /* rank_first = 0; or NULL */
+  const cook_finished* finished;     /* rank_first = 0; or NULL */
+  const cook_kube_clusters* clusters;
+  const double* draw;                /* [n_draw] or NULL */
+  uint32_t n_draw, reserved;
+  uint64_t seed;
+} cook_kube_cycle;
+int cook_cycle_run_kube(cook_engine* e, const cook_kube_cycle* c, uint32_t* task_idx, uint32_t cap, uint32_t* cluster_off /* [n + 1] */,
+                        cook_kube_cluster_info* cluster_info /* [n] */, cook_kube_info* info /* or NULL */);
+/* ... for the Kubernetes-scheduler pools of a GPU in one pool batch: the pools' advances, filters and distributions side by side, the
+ * distributor launched once with blockIdx.y as the pool.  Engine i's results, code and message are those of the single call; a paused
+ * pool, a refused pool and a pool that considers nothing can each sit beside good ones.  COOK_E_INVALID with nothing run: engines,
+ * cycles, cap, cluster_off or cluster_info NULL, n == 0, a NULL entry of engines or cycles, an engine twice. */
+int cook_cycle_run_kube_multi(cook_engine** engines, uint32_t n, const cook_kube_cycle* const* cycles, uint32_t* const* task_idx,
+                              const uint32_t* cap, uint32_t* const* cluster_off, cook_kube_cluster_info* const* cluster_info,
+                              cook_kube_info* info /* [n] or NULL */, int* rc /* [n] or NULL */);
+/* choice[k] = the cluster of considered position k of the last cycle (COOK_KUBE_NO_CLUSTER: none), *n_out = their number.  COOK_E_STATE
+ * unless the last cycle was a Kubernetes cycle.  One synchronisation. */
+int cook_cycle_fetch_kube(cook_engine* e, uint8_t* choice, uint32_t* n_out);
 
 /* ---- REBALANCE: replaces init-state + the rebalance loop's decisions ---------------------------------------
  * (rebalancer.clj:222-266, 320-407, 270-309, 434-467; dru.clj:128-144).
