@@ -767,11 +767,116 @@ static __device__ __forceinline__ bool rebal_group_constraint(const RebalIn& in,
 }
 
 // ---- per host: candidates, priority order, prefix aggregates, best feasible prefix ------------------------------------------
-struct HostBest {  // best feasible prefix of a host for the current job
+// The rule (rebalancer.clj:339-349, :384-404), stated ONCE in the pieces below: filter a host's items to the preemption candidates
+// (rebal_candidate), order them by (dru desc, position in B asc) (rebal_before), seed the prefix aggregates with the host's spare resources
+// (rebal_spare_seed), keep the feasible (rebal_fits) prefix with the greatest last DRU, ties to the longest (HostBest), and across hosts the later
+// host wins ties (rebal_host_beats).  Three forms evaluate a host — rebal_host_pair (two hosts of <= 32 items, half a wave each),
+// rebal_host_small (<= 64 items, in registers), rebal_host_big (lists in LDS or the global scratch) — and own only HOW they do it: finding a
+// placed job's index, the rank by counting, the scan, and the arg-max over a wave, a half wave or a list.
+struct HostItem {  // an item of a host: a running task, or a job placed on it earlier in this cycle
+  unsigned slot, pb, usr;  // slot, position in B, user
+  bool a;                  // active
+  double d;                // DRU (0.0 when not active)
+  double c, m, g;          // cpus / mem / gpus (rebal_item_resources)
+};
+// identity + DRU of item t of the host whose running slots start at hs of the host-ordered mirrors: t < n_seg a running slot (its columns lie
+// at hs + t), else, when `valid`, the placed job of pending index pj (each form finds pj its own way)
+static __device__ __forceinline__ HostItem rebal_item(const RebalIn& in, unsigned hs, unsigned n_seg, unsigned t, bool valid, unsigned pj) {
+  HostItem it{0u, 0u, 0u, false, 0.0, 0.0, 0.0, 0.0};
+  if (t < n_seg) {
+    it.slot = in.hperm[hs + t];
+    it.pb = in.h_pb[hs + t];
+    it.a = in.h_act[hs + t] != 0;
+    it.usr = in.h_user[hs + t];
+    it.d = in.h_dru[hs + t];
+  } else if (valid) {
+    it.slot = in.R + pj;
+    it.pb = in.posB[it.slot];
+    it.a = in.act[it.pb] != 0;
+    it.usr = in.slot_user[it.slot];
+    it.d = in.dru[it.pb];
+  }
+  if (!it.a) it.d = 0.0;
+  return it;
+}
+// ... and its resources (of a valid item; the big form asks for the candidates' only)
+static __device__ __forceinline__ void rebal_item_resources(const RebalIn& in, unsigned hs, unsigned n_seg, unsigned t, HostItem& it) {
+  if (t < n_seg)
+    it.c = in.h_cpus[hs + t], it.m = in.h_mem[hs + t], it.g = in.h_gpus[hs + t];
+  else
+    it.c = in.slot_cpus[it.slot], it.m = in.slot_mem[it.slot], it.g = in.slot_gpus[it.slot];
+}
+// may the job preempt this item (rebalancer.clj:339-349)
+static __device__ __forceinline__ bool rebal_candidate(const RebalIn& in, const RebalJob& jb, const HostItem& it) {
+  return it.a && (jb.below || it.usr == jb.us) && !(it.d < in.safe_dru) && (it.d - jb.pdru > in.min_diff);
+}
+// priority-map order inside a host: does the item (dj, pbj) come before (d, pb)
+static __device__ __forceinline__ bool rebal_before(double dj, unsigned pbj, double d, unsigned pb) { return dj > d || (dj == d && pbj < pb); }
+// what the prefix aggregates of host h start from: its spare resources (sp: it has some), added to 0.0 as the reference's reduction does
+static __device__ __forceinline__ SumU4 rebal_spare_seed(const RebalIn& in, unsigned h, bool sp) {
+  if (!sp) return SumU4::zero();
+  return SumU4{0.0, 0.0 + in.spare_c[h], 0.0 + in.spare_m[h], 0.0 + in.spare_g[h], 0u};
+}
+// does an aggregate hold the job (rebalancer.clj:390-396)
+static __device__ __forceinline__ bool rebal_fits(const RebalJob& jb, double cpus, double mem, double gpus) {
+  return mem >= jb.m && cpus >= jb.c && (jb.has_gpus != 0 ? gpus >= jb.g : true);
+}
+struct HostBest {  // best feasible prefix of a host for the current job: (key, len) lexicographic max
   unsigned long long key;  // f64_key(dru), 0 = none
   unsigned len;
   double dru, c, m, g;
+  __device__ __forceinline__ void clear() {
+    key = 0ull;
+    len = 0;
+    dru = c = m = g = 0.0;
+  }
+  // the spare pseudo-entry alone: length 0 under the greatest key there is, when the host's spare resources hold the job
+  __device__ __forceinline__ void spare_alone(const RebalJob& jb, bool sp, const SumU4& seed) {
+    const double DMAXV = 1.7976931348623157e308;
+    if (sp && rebal_fits(jb, seed.cpus, seed.mem, seed.gpus)) key = f64_key(DMAXV), len = 0, dru = DMAXV, c = seed.cpus, m = seed.mem, g = seed.gpus;
+  }
+  // offer the prefix of length n whose last candidate has DRU d and whose aggregate is (ac, am, ag): offered in increasing n, so on equal
+  // keys the later = longer prefix wins (max-key, rebalancer.clj:404)
+  __device__ __forceinline__ void offer(const RebalJob& jb, unsigned n, double d, double ac, double am, double ag) {
+    if (rebal_fits(jb, ac, am, ag) && d >= 0.0 && f64_key(d) >= key) key = f64_key(d), len = n, dru = d, c = ac, m = am, g = ag;
+  }
 };
+// A host whose partial sums rounded: the aggregates left to right, exactly as the reference's reductions.  fetch(k, d, c, m, g) gives the k-th
+// candidate in priority order and says whether there is one (the pair form: the other half's list may be the longer one); b starts clear.
+template <class Fetch>
+static __device__ __forceinline__ void rebal_redo(const RebalJob& jb, bool sp, const SumU4& seed, unsigned n_c, Fetch fetch, HostBest& b) {
+  double ac = seed.cpus, am = seed.mem, ag = seed.gpus;
+  b.spare_alone(jb, sp, seed);
+  for (unsigned k = 0; k < n_c; ++k) {
+    double d, c, m, g;
+    if (!fetch(k, d, c, m, g)) continue;
+    ac += c, am += m, ag += g;
+    b.offer(jb, k + 1, d, ac, am, ag);
+  }
+}
+// across hosts: does the entry (k, h) beat (bk, bh) — a greater key, else the later host (max-key over the hosts in name order,
+// rebalancer.clj:404); no key beats nothing.  Every arg-max over hosts uses this one spelling: two entries compared are either of distinct
+// hosts (>= is >) or the same entry met twice — a butterfly's partner holding the same maximum, a host evaluated in both phases, whose
+// result is the same — and taking an equal entry changes nothing.
+static __device__ __forceinline__ bool rebal_host_beats(unsigned long long k, unsigned h, unsigned long long bk, unsigned bh) {
+  return k != 0ull && (k > bk || (k == bk && h >= bh));
+}
+// a host's result for rebal_apply; base = where its candidates lie in srt_slot, COOK_NONE: rebal_apply re-derives the preempted prefix itself
+static __device__ __forceinline__ void rebal_store_result(const RebalIn& in, unsigned h, const HostBest& b, unsigned base) {
+  in.hres_key[h] = b.key;
+  if (b.key != 0ull) {
+    in.hres_len[h] = b.len;
+    in.hres_base[h] = base;
+    in.hres_dru[h] = b.dru;
+    in.hres_c[h] = b.c;
+    in.hres_m[h] = b.m;
+    in.hres_g[h] = b.g;
+  }
+}
+// is the attribute map of the slot's slave id known (a placed job carries its first preempted task's, rebalancer.clj:279-281)
+static __device__ __forceinline__ bool rebal_slot_known(const RebalIn& in, unsigned slot) {
+  return slot < in.R ? (in.attrs_cached ? in.attrs_cached[slot] != 0 : true) : in.x_known[slot - in.R] != 0;
+}
 // Jobs placed earlier in this cycle form one chain per host (x_head[h] -> x_next[pj] -> ...), newest first; x_cnt[h] = its length.
 // The order inside a host does not matter: the host's items are ordered by (dru desc, position in B asc) anyway.
 static __device__ __forceinline__ unsigned rebal_chain_at(const RebalIn& in, unsigned h, unsigned q) {
@@ -787,9 +892,10 @@ static __device__ __forceinline__ unsigned rebal_x_before(const RebalIn& in, uns
   for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, COOK_WAVE);
   return c;
 }
-// the host's last scored task in priority-map order (rebalancer.clj:369-375) decides which attribute map the host resolves to
-static __device__ __forceinline__ int rebal_host_row(const RebalIn& in, unsigned h, double last_d, unsigned last_pb, unsigned last_slot) {
-  for (int dd = 32; dd >= 1; dd >>= 1) {
+// the host's last scored task in priority-map order (rebalancer.clj:369-375) decides which attribute map the host resolves to: reduced over
+// the wave (from = 32) or over each half of it (from = 16); last_slot COOK_NONE = this lane has none
+static __device__ __forceinline__ int rebal_host_row(const RebalIn& in, unsigned h, double last_d, unsigned last_pb, unsigned last_slot, int from = 32) {
+  for (int dd = from; dd >= 1; dd >>= 1) {
     const double od = __shfl_xor(last_d, dd, COOK_WAVE);
     const unsigned opb = __shfl_xor(last_pb, dd, COOK_WAVE), osl = __shfl_xor(last_slot, dd, COOK_WAVE);
     if (osl != 0xFFFFFFFFu && (last_slot == 0xFFFFFFFFu || od < last_d || (od == last_d && opb > last_pb))) {
@@ -798,57 +904,29 @@ static __device__ __forceinline__ int rebal_host_row(const RebalIn& in, unsigned
       last_slot = osl;
     }
   }
-  bool known = false;
-  if (last_slot != 0xFFFFFFFFu)
-    known = last_slot < in.R ? (in.attrs_cached ? in.attrs_cached[last_slot] != 0 : true) : in.x_known[last_slot - in.R] != 0;
-  return known ? in.row_of_host[h] : -1;
+  return (last_slot != 0xFFFFFFFFu && rebal_slot_known(in, last_slot)) ? in.row_of_host[h] : -1;
 }
 
-// A host with at most 64 items (running tasks + jobs placed this cycle), one item per lane, everything in registers: filter
-// (rebalancer.clj:339-349), rank by (dru desc, position in B asc) with wave broadcasts, prefix aggregates seeded with the spare
-// resources (:384-403), best feasible prefix (:404).  l_rank = 64 words of LDS owned by this wave.  -> out.key != 0 when the host can
-// take the job; sorted_slot = lane k's slot of the k-th candidate in priority order (the preempted tasks are a prefix of it).
+// A host with at most 64 items (running tasks + jobs placed this cycle), one item per lane, everything in registers: filter, rank by
+// counting with wave broadcasts, prefix aggregates, best feasible prefix.  l_rank = 64 words of LDS owned by this wave.  -> out.key != 0 when
+// the host can take the job; sorted_slot = lane k's slot of the k-th candidate in priority order (the preempted tasks are a prefix of it).
 template <bool SAFE = false>
 static __device__ __forceinline__ void rebal_host_small(const RebalIn& in, const RebalJob& jb, unsigned h, unsigned hs, unsigned n_seg, unsigned n_here,
                                                        bool sp, uint32_t* l_rank, HostBest& out, unsigned& sorted_slot) {
   const unsigned lane = lane_id(), t = lane, n = n_seg + n_here;
-  out.key = 0ull;
-  out.len = 0;
-  out.dru = out.c = out.m = out.g = 0.0;
+  out.clear();
   sorted_slot = 0xFFFFFFFFu;
-  const bool valid = t < n, mirrored = t < n_seg;
   unsigned my_pj = 0;
-  if (n_here) {  // wave-uniform
+  if (n_here) {  // wave-uniform: lane n_seg + q takes the q-th job of the host's chain
     unsigned cur = in.x_head[h];
     for (unsigned q = 0; q < n_here; ++q) {
       if (t == n_seg + q) my_pj = cur;
       cur = in.x_next[cur];
     }
   }
-  unsigned slot = 0, pb = 0, usr = 0;
-  bool a = false;
-  double d = 0.0, xc = 0.0, xm = 0.0, xg = 0.0;
-  if (mirrored) {  // a running slot: its columns lie at hs + t of the host-ordered mirrors
-    slot = in.hperm[hs + t];
-    pb = in.h_pb[hs + t];
-    a = in.h_act[hs + t] != 0;
-    usr = in.h_user[hs + t];
-    d = in.h_dru[hs + t];
-    xc = in.h_cpus[hs + t], xm = in.h_mem[hs + t], xg = in.h_gpus[hs + t];
-  } else if (valid) {  // a job placed earlier in this cycle
-    slot = in.R + my_pj;
-    pb = in.posB[slot];
-    a = in.act[pb] != 0;
-    usr = in.slot_user[slot];
-    d = in.dru[pb];
-    xc = in.slot_cpus[slot], xm = in.slot_mem[slot], xg = in.slot_gpus[slot];
-  }
-  if (!a) d = 0.0;
-#if defined(RB_CUT) && RB_CUT == 1
-  if (d == 123.456) out.key = 1ull;
-  return;
-#endif
-  const bool cand = a && (jb.below || usr == jb.us) && !(d < in.safe_dru) && (d - jb.pdru > in.min_diff);
+  HostItem it = rebal_item(in, hs, n_seg, t, t < n, my_pj);
+  if (t < n) rebal_item_resources(in, hs, n_seg, t, it);
+  const bool cand = rebal_candidate(in, jb, it);
   const unsigned long long mask = __ballot(cand);
   const unsigned n_c = (unsigned)__popcll(mask);
   if (n_c == 0 && !sp) return;  // nothing to preempt and nothing spare: no prefix exists (wave-uniform)
@@ -856,78 +934,49 @@ static __device__ __forceinline__ void rebal_host_small(const RebalIn& in, const
   // cached and no placed job sits on the host, any active item gives the same answer
   int row;
   if (!in.attrs_cached && n_here == 0)
-    row = __ballot(a) != 0ull ? in.row_of_host[h] : -1;
+    row = __ballot(it.a) != 0ull ? in.row_of_host[h] : -1;
   else
-    row = rebal_host_row(in, h, d, pb, a ? slot : 0xFFFFFFFFu);
+    row = rebal_host_row(in, h, it.d, it.pb, it.a ? it.slot : 0xFFFFFFFFu);
   if (!rebal_job_constraints(in, jb.pj, row, jb.g)) return;
   if (jb.gtype && !rebal_group_constraint(in, jb, row)) return;
-#if defined(RB_CUT) && RB_CUT == 2
-  if (d == 123.456) out.key = 1ull;
-  return;
-#endif
-  // priority-map order inside the host = (dru desc, position in B asc): rank by counting, the other items broadcast one by one
+  // rank by counting, the other items broadcast one by one
   unsigned r = 0;
   for (unsigned long long m = mask; m != 0ull; m &= m - 1ull) {
     const int j = __ffsll((unsigned long long)m) - 1;
-    const double dj = wave_read_lane_f64(d, j);
-    const unsigned pjx = (unsigned)wave_read_lane((int)pb, j);
-    r += (dj > d || (dj == d && pjx < pb)) ? 1u : 0u;
+    r += rebal_before(wave_read_lane_f64(it.d, j), (unsigned)wave_read_lane((int)it.pb, j), it.d, it.pb) ? 1u : 0u;
   }
   if (cand) l_rank[r] = lane;
   wave_sync();
   const unsigned src = lane < n_c ? l_rank[lane] : 0u;
   wave_sync();  // (the next call of this wave reuses l_rank)
   const bool vk = lane < n_c;
-  const double sd = __shfl(d, (int)src, COOK_WAVE);
-  SumU4 x = SumU4{0.0, __shfl(xc, (int)src, COOK_WAVE), __shfl(xm, (int)src, COOK_WAVE), __shfl(xg, (int)src, COOK_WAVE), 0u};
-  sorted_slot = (unsigned)__shfl((int)slot, (int)src, COOK_WAVE);
+  const double sd = __shfl(it.d, (int)src, COOK_WAVE);
+  SumU4 x = SumU4{0.0, __shfl(it.c, (int)src, COOK_WAVE), __shfl(it.m, (int)src, COOK_WAVE), __shfl(it.g, (int)src, COOK_WAVE), 0u};
+  sorted_slot = (unsigned)__shfl((int)it.slot, (int)src, COOK_WAVE);
   if (!vk) {
     x = SumU4::zero();
     sorted_slot = 0xFFFFFFFFu;
   }
-#if defined(RB_CUT) && RB_CUT == 3
-  if (sd == 123.456) out.key = 1ull;
-  return;
-#endif
-  // prefix aggregates seeded with the spare resources, best feasible prefix: key (f64_key(dru), len) lexicographic max; len 0 = the
-  // spare pseudo-entry alone
-  const double jc = jb.c, jm = jb.m, jg = jb.g;
-  const bool need_g = jb.has_gpus != 0;
-  SumU4 seed = SumU4::zero();
-  if (sp) seed = SumU4{0.0, 0.0 + in.spare_c[h], 0.0 + in.spare_m[h], 0.0 + in.spare_g[h], 0u};
-  const double DMAXV = 1.7976931348623157e308;
-  unsigned long long bk = 0ull;
-  unsigned bl = 0;
-  double bd = 0.0, bc = 0.0, bm = 0.0, bg = 0.0;
-  const bool spare_alone = sp && seed.mem >= jm && seed.cpus >= jc && (need_g ? seed.gpus >= jg : true);
+  const SumU4 seed = rebal_spare_seed(in, h, sp);
   const SumU4 tt = combine_t<SAFE>(seed, wave_incl_scan_u4_rows<SAFE>(x, n_c));
-  if (!SAFE && __any(vk && tt.bad != 0u)) {  // a partial sum rounded: left to right, exactly as the reference's reductions (all lanes alike)
-    double ac = seed.cpus, am = seed.mem, ag = seed.gpus;
-    if (spare_alone) bk = f64_key(DMAXV), bd = DMAXV, bc = ac, bm = am, bg = ag;
-    for (unsigned k = 0; k < n_c; ++k) {
-      ac += __shfl(x.cpus, (int)k, COOK_WAVE);
-      am += __shfl(x.mem, (int)k, COOK_WAVE);
-      ag += __shfl(x.gpus, (int)k, COOK_WAVE);
-      const double dk = __shfl(sd, (int)k, COOK_WAVE);
-      if (am >= jm && ac >= jc && (need_g ? ag >= jg : true) && dk >= 0.0 && f64_key(dk) >= bk) bk = f64_key(dk), bl = k + 1, bd = dk, bc = ac, bm = am, bg = ag;
-    }
-  } else {
-    if (lane == 0 && spare_alone) bk = f64_key(DMAXV), bd = DMAXV, bc = seed.cpus, bm = seed.mem, bg = seed.gpus;
-    const bool enough = vk && tt.mem >= jm && tt.cpus >= jc && (need_g ? tt.gpus >= jg : true) && sd >= 0.0;
-    if (enough && f64_key(sd) >= bk) bk = f64_key(sd), bl = lane + 1, bd = sd, bc = tt.cpus, bm = tt.mem, bg = tt.gpus;  // later prefix wins ties (max-key, :404)
-    // wave arg-max of (bk, bl): the greatest key, and among equal keys the longest prefix = the highest lane (lane k holds prefix
-    // k + 1; the spare pseudo-entry, length 0, sits in lane 0 under the greatest key there is)
-    const unsigned long long mk = wave_max_u64(bk);
-    if (mk == 0ull) return;
-    const unsigned long long own = __ballot(bk == mk);
-    const int wl = 63 - __clzll((unsigned long long)own);
-    bk = mk;
-    bl = (unsigned)wave_read_lane((int)bl, wl);
-    bd = wave_read_lane_f64(bd, wl), bc = wave_read_lane_f64(bc, wl), bm = wave_read_lane_f64(bm, wl), bg = wave_read_lane_f64(bg, wl);
+  if (!SAFE && __any(vk && tt.bad != 0u)) {  // a partial sum rounded (all lanes alike)
+    rebal_redo(jb, sp, seed, n_c, [&](unsigned k, double& dk, double& ck, double& mk, double& gk) {
+      dk = __shfl(sd, (int)k, COOK_WAVE);
+      ck = __shfl(x.cpus, (int)k, COOK_WAVE), mk = __shfl(x.mem, (int)k, COOK_WAVE), gk = __shfl(x.gpus, (int)k, COOK_WAVE);
+      return true;
+    }, out);
+    return;
   }
-  out.key = bk;
-  out.len = bl;
-  out.dru = bd, out.c = bc, out.m = bm, out.g = bg;
+  // lane k holds prefix k + 1; the spare pseudo-entry, length 0, sits in lane 0
+  if (lane == 0) out.spare_alone(jb, sp, seed);
+  if (vk) out.offer(jb, lane + 1, sd, tt.cpus, tt.mem, tt.gpus);
+  // wave arg-max of (key, len): the greatest key, and among equal keys the longest prefix = the highest lane
+  const unsigned long long mk = wave_max_u64(out.key);
+  if (mk == 0ull) return;
+  const int wl = 63 - __clzll((unsigned long long)__ballot(out.key == mk));
+  out.key = mk;
+  out.len = (unsigned)wave_read_lane((int)out.len, wl);
+  out.dru = wave_read_lane_f64(out.dru, wl), out.c = wave_read_lane_f64(out.c, wl), out.m = wave_read_lane_f64(out.m, wl), out.g = wave_read_lane_f64(out.g, wl);
 }
 
 // Two hosts with at most 32 items each in ONE wave, a half per host (lanes 0..31: host h0, lanes 32..63: host h0 + 1): the launch is
@@ -942,52 +991,21 @@ static __device__ __forceinline__ void rebal_host_pair(const RebalIn& in, const 
   const unsigned hs = hv ? in.hstart[h] : 0u, n_seg = hv ? in.hend[h] - hs : 0u, n_here = hv ? in.x_cnt[h] : 0u;
   const unsigned n = n_seg + n_here;
   const bool sp = hv && in.has_spare[h] != 0;
-  out.key = 0ull;
-  out.len = 0;
-  out.dru = out.c = out.m = out.g = 0.0;
-  const bool valid = t < n, mirrored = t < n_seg;
-  unsigned slot = 0, pb = 0, usr = 0;
-  bool a = false;
-  double d = 0.0, xc = 0.0, xm = 0.0, xg = 0.0;
-  if (mirrored) {
-    slot = in.hperm[hs + t];
-    pb = in.h_pb[hs + t];
-    a = in.h_act[hs + t] != 0;
-    usr = in.h_user[hs + t];
-    d = in.h_dru[hs + t];
-    xc = in.h_cpus[hs + t], xm = in.h_mem[hs + t], xg = in.h_gpus[hs + t];
-  } else if (valid) {  // a job placed earlier in this cycle: the (t - n_seg)-th of the host's chain
-    slot = in.R + rebal_chain_at(in, h, t - n_seg);
-    pb = in.posB[slot];
-    a = in.act[pb] != 0;
-    usr = in.slot_user[slot];
-    d = in.dru[pb];
-    xc = in.slot_cpus[slot], xm = in.slot_mem[slot], xg = in.slot_gpus[slot];
-  }
-  if (!a) d = 0.0;
-  const bool cand = a && (jb.below || usr == jb.us) && !(d < in.safe_dru) && (d - jb.pdru > in.min_diff);
+  out.clear();
+  const bool placed = t >= n_seg && t < n;  // a job placed earlier in this cycle: the (t - n_seg)-th of the host's chain
+  HostItem it = rebal_item(in, hs, n_seg, t, t < n, placed ? rebal_chain_at(in, h, t - n_seg) : 0u);
+  if (t < n) rebal_item_resources(in, hs, n_seg, t, it);
+  const bool cand = rebal_candidate(in, jb, it);
   const unsigned long long mask = __ballot(cand);
   const unsigned hmask = (unsigned)(mask >> hb);
   const unsigned n_c = (unsigned)__popc(hmask);
   bool alive = hv && !(n_c == 0 && !sp);
-  // which attribute map the host resolves to (see rebal_host_small)
-  int row = -1;
-  if (__any(in.attrs_cached != nullptr || n_here != 0u)) {  // wave-uniform: the general rule, reduced over the half
-    double last_d = d;
-    unsigned last_pb = pb, last_slot = a ? slot : 0xFFFFFFFFu;
-    for (int dd = 16; dd >= 1; dd >>= 1) {
-      const double od = __shfl_xor(last_d, dd, COOK_WAVE);
-      const unsigned opb = __shfl_xor(last_pb, dd, COOK_WAVE), osl = __shfl_xor(last_slot, dd, COOK_WAVE);
-      if (osl != 0xFFFFFFFFu && (last_slot == 0xFFFFFFFFu || od < last_d || (od == last_d && opb > last_pb))) last_d = od, last_pb = opb, last_slot = osl;
-    }
-    bool known = false;
-    if (last_slot != 0xFFFFFFFFu)
-      known = last_slot < in.R ? (in.attrs_cached ? in.attrs_cached[last_slot] != 0 : true) : in.x_known[last_slot - in.R] != 0;
-    row = (known && hv) ? in.row_of_host[h] : -1;
-  } else {
-    const unsigned amask = (unsigned)(__ballot(a) >> hb);
-    row = (amask != 0u && hv) ? in.row_of_host[h] : -1;
-  }
+  // which attribute map the host resolves to (see rebal_host_small; a half past the last host has no item, hence no row)
+  int row;
+  if (__any(in.attrs_cached != nullptr || n_here != 0u))  // wave-uniform: the general rule, reduced over the half
+    row = rebal_host_row(in, h, it.d, it.pb, it.a ? it.slot : 0xFFFFFFFFu, 16);
+  else
+    row = (unsigned)(__ballot(it.a) >> hb) != 0u ? in.row_of_host[h] : -1;
   if (alive && !rebal_job_constraints(in, jb.pj, row, jb.g)) alive = false;
   if (!__any(alive)) return;
   // rank inside the half by counting; item jj of both halves is broadcast in one step
@@ -996,28 +1014,20 @@ static __device__ __forceinline__ void rebal_host_pair(const RebalIn& in, const 
   for (unsigned m = either; m != 0u; m &= m - 1u) {
     const int jj = __ffs((int)m) - 1;
     const int src = (int)hb + jj;
-    const double dj = __shfl(d, src, COOK_WAVE);
-    const unsigned pjx = (unsigned)__shfl((int)pb, src, COOK_WAVE);
+    const double dj = __shfl(it.d, src, COOK_WAVE);
+    const unsigned pjx = (unsigned)__shfl((int)it.pb, src, COOK_WAVE);
     const bool cj = ((hmask >> jj) & 1u) != 0u;
-    r += (cj && (dj > d || (dj == d && pjx < pb))) ? 1u : 0u;
+    r += (cj && rebal_before(dj, pjx, it.d, it.pb)) ? 1u : 0u;
   }
   if (cand) l_rank[hb + r] = lane;
   wave_sync();
   const bool vk = t < n_c;
   const unsigned src = vk ? l_rank[hb + t] : lane;
   wave_sync();
-  const double sd = __shfl(d, (int)src, COOK_WAVE);
-  SumU4 x = SumU4{0.0, __shfl(xc, (int)src, COOK_WAVE), __shfl(xm, (int)src, COOK_WAVE), __shfl(xg, (int)src, COOK_WAVE), 0u};
+  const double sd = __shfl(it.d, (int)src, COOK_WAVE);
+  SumU4 x = SumU4{0.0, __shfl(it.c, (int)src, COOK_WAVE), __shfl(it.m, (int)src, COOK_WAVE), __shfl(it.g, (int)src, COOK_WAVE), 0u};
   if (!vk) x = SumU4::zero();
-  const double jc = jb.c, jm = jb.m, jg = jb.g;
-  const bool need_g = jb.has_gpus != 0;
-  SumU4 seed = SumU4::zero();
-  if (sp) seed = SumU4{0.0, 0.0 + in.spare_c[h], 0.0 + in.spare_m[h], 0.0 + in.spare_g[h], 0u};
-  const double DMAXV = 1.7976931348623157e308;
-  unsigned long long bk = 0ull;
-  unsigned bl = 0;
-  double bd = 0.0, bc = 0.0, bm = 0.0, bg = 0.0;
-  const bool spare_alone = sp && seed.mem >= jm && seed.cpus >= jc && (need_g ? seed.gpus >= jg : true);
+  const SumU4 seed = rebal_spare_seed(in, h, sp);
   // inclusive scan inside the half: four row steps + the row-to-row step (rows 0 -> 1 and 2 -> 3)
   SumU4 sc = scan_step_u4<0, SAFE>(x);
   sc = scan_step_u4<1, SAFE>(sc);
@@ -1026,37 +1036,34 @@ static __device__ __forceinline__ void rebal_host_pair(const RebalIn& in, const 
   sc = scan_step_u4<4, SAFE>(sc);
   const SumU4 tt = combine_t<SAFE>(seed, sc);
   const unsigned hbad = SAFE ? 0u : (unsigned)(__ballot(vk && tt.bad != 0u) >> hb);
-  if (!SAFE && __any(hbad != 0u)) {  // a partial sum rounded in some half: that half redoes it left to right like the reference (every lane of it alike)
-    double ac = seed.cpus, am = seed.mem, ag = seed.gpus;
-    unsigned long long k2 = 0ull;
-    unsigned l2 = 0;
-    double d2 = 0.0, c2 = 0.0, m2 = 0.0, g2 = 0.0;
-    if (spare_alone) k2 = f64_key(DMAXV), d2 = DMAXV, c2 = ac, m2 = am, g2 = ag;
-    for (unsigned k = 0; k < 32u; ++k) {
-      if (!__any(k < n_c)) break;
-      const double ck = __shfl(x.cpus, (int)(hb + k), COOK_WAVE), mk2 = __shfl(x.mem, (int)(hb + k), COOK_WAVE), gk = __shfl(x.gpus, (int)(hb + k), COOK_WAVE);
-      const double dk = __shfl(sd, (int)(hb + k), COOK_WAVE);
-      if (k < n_c) {
-        ac += ck, am += mk2, ag += gk;
-        if (am >= jm && ac >= jc && (need_g ? ag >= jg : true) && dk >= 0.0 && f64_key(dk) >= k2) k2 = f64_key(dk), l2 = k + 1, d2 = dk, c2 = ac, m2 = am, g2 = ag;
-      }
-    }
+  if (!SAFE && __any(hbad != 0u)) {  // a partial sum rounded in some half: that half takes the left-to-right result (every lane of it alike)
+    HostBest redo;
+    redo.clear();
+    const unsigned n_lo = (unsigned)__popc((unsigned)mask), n_hi = (unsigned)__popc((unsigned)(mask >> 32));
+    const unsigned n_both = n_lo > n_hi ? n_lo : n_hi;  // (wave-uniform: the shuffles need every lane)
+    rebal_redo(jb, sp, seed, n_both, [&](unsigned k, double& dk, double& ck, double& mk, double& gk) {
+      dk = __shfl(sd, (int)(hb + k), COOK_WAVE);
+      ck = __shfl(x.cpus, (int)(hb + k), COOK_WAVE), mk = __shfl(x.mem, (int)(hb + k), COOK_WAVE), gk = __shfl(x.gpus, (int)(hb + k), COOK_WAVE);
+      return k < n_c;
+    }, redo);
     if (hbad != 0u) {
-      if (alive && t == 0) out.key = k2, out.len = l2, out.dru = d2, out.c = c2, out.m = m2, out.g = g2;
+      if (alive && t == 0) out = redo;
       alive = false;  // this half is done
     }
   }
-  if (t == 0 && spare_alone) bk = f64_key(DMAXV), bd = DMAXV, bc = seed.cpus, bm = seed.mem, bg = seed.gpus;
-  const bool enough = vk && tt.mem >= jm && tt.cpus >= jc && (need_g ? tt.gpus >= jg : true) && sd >= 0.0;
-  if (enough && f64_key(sd) >= bk) bk = f64_key(sd), bl = t + 1, bd = sd, bc = tt.cpus, bm = tt.mem, bg = tt.gpus;  // later prefix wins ties (:404)
-  // arg-max of (bk, bl) over the half: the greatest key, among equal keys the highest lane (= the longest prefix)
-  const unsigned long long mk = half_max_u64(bk);
-  const unsigned own = (unsigned)(__ballot(bk == mk) >> hb);
+  HostBest b;
+  b.clear();
+  if (t == 0) b.spare_alone(jb, sp, seed);
+  if (vk) b.offer(jb, t + 1, sd, tt.cpus, tt.mem, tt.gpus);
+  // arg-max of (key, len) over the half: the greatest key, among equal keys the highest lane (= the longest prefix)
+  const unsigned long long mk = half_max_u64(b.key);
+  const unsigned own = (unsigned)(__ballot(b.key == mk) >> hb);
   const int wl = (int)hb + 31 - __clz((int)own);  // own != 0: the lane holding the maximum is among them
-  const unsigned wlen = (unsigned)__shfl((int)bl, wl, COOK_WAVE);
-  const double wd = __shfl(bd, wl, COOK_WAVE), wc = __shfl(bc, wl, COOK_WAVE), wm = __shfl(bm, wl, COOK_WAVE), wg = __shfl(bg, wl, COOK_WAVE);
+  const unsigned wlen = (unsigned)__shfl((int)b.len, wl, COOK_WAVE);
+  const double wd = __shfl(b.dru, wl, COOK_WAVE), wc = __shfl(b.c, wl, COOK_WAVE), wm = __shfl(b.m, wl, COOK_WAVE), wg = __shfl(b.g, wl, COOK_WAVE);
   if (alive && t == 0 && mk != 0ull) out.key = mk, out.len = wlen, out.dru = wd, out.c = wc, out.m = wm, out.g = wg;
 }
+
 
 // hosts with at most 64 items (running tasks + jobs placed this cycle): a wave takes two neighbouring hosts, half a wave each when
 // both hold at most 32 items (rebal_host_pair), else one after the other.  No LDS beyond 64 words per wave, few registers.  The launch
@@ -1094,8 +1101,8 @@ __global__ void __launch_bounds__(COOK_WAVE* RB_WAVES) rebal_decide(const RebalI
           const unsigned h = 2u * pr + q;
           unsigned long long bd = in.hmax_key[h];
           if (in.has_spare[h] != 0) {
-            const double sc = 0.0 + in.spare_c[h], sm = 0.0 + in.spare_m[h], sg = 0.0 + in.spare_g[h];
-            if (sm >= jb.m && sc >= jb.c && (jb.has_gpus != 0 ? sg >= jb.g : true)) bd = ~0ull;
+            const SumU4 seed = rebal_spare_seed(in, h, true);
+            if (rebal_fits(jb, seed.cpus, seed.mem, seed.gpus)) bd = ~0ull;
           }
           mine = mine || (phase == 0u ? bd >= in.thr_key : (bd < in.thr_key && bd >= best && bd != 0ull));
         }
@@ -1110,7 +1117,7 @@ __global__ void __launch_bounds__(COOK_WAVE* RB_WAVES) rebal_decide(const RebalI
   unsigned long long wk = 0ull;
   unsigned wh = 0u;
   auto take = [&](unsigned long long k, unsigned h) {
-    if (k != 0ull && (k > wk || (k == wk && h > wh))) wk = k, wh = h;  // (wave-uniform)
+    if (rebal_host_beats(k, h, wk, wh)) wk = k, wh = h;  // (wave-uniform)
   };
   auto eval_pair = [&](unsigned h0) {
     const bool two = h0 + 1u < in.H;
@@ -1123,18 +1130,7 @@ __global__ void __launch_bounds__(COOK_WAVE* RB_WAVES) rebal_decide(const RebalI
     if (n0 <= 32u && n1 <= 32u && jb.gtype == 0u) {
       HostBest hb;
       rebal_host_pair<SAFE>(in, jb, h0, l_rank[w], hb);
-      if ((lane & 31u) == 0u && h0 + (lane >> 5) < in.H) {
-        const unsigned h = h0 + (lane >> 5);
-        in.hres_key[h] = hb.key;
-        if (hb.key != 0ull) {
-          in.hres_len[h] = hb.len;
-          in.hres_base[h] = 0xFFFFFFFFu;  // rebal_apply re-derives the preempted prefix of a small host itself
-          in.hres_dru[h] = hb.dru;
-          in.hres_c[h] = hb.c;
-          in.hres_m[h] = hb.m;
-          in.hres_g[h] = hb.g;
-        }
-      }
+      if ((lane & 31u) == 0u && h0 + (lane >> 5) < in.H) rebal_store_result(in, h0 + (lane >> 5), hb, 0xFFFFFFFFu);
       const unsigned long long k0 = wave_read_lane_u64(hb.key, 0), k1 = two ? wave_read_lane_u64(hb.key, 32) : 0ull;
       take(k0, h0);
       take(k1, h0 + 1u);
@@ -1153,17 +1149,7 @@ __global__ void __launch_bounds__(COOK_WAVE* RB_WAVES) rebal_decide(const RebalI
         unsigned ss;
         rebal_host_small<SAFE>(in, jb, h, hs, n_seg, n_here, sp, l_rank[w], hb, ss);
       }
-      if (lane == 0) {
-        in.hres_key[h] = hb.key;
-        if (hb.key != 0ull) {
-          in.hres_len[h] = hb.len;
-          in.hres_base[h] = 0xFFFFFFFFu;
-          in.hres_dru[h] = hb.dru;
-          in.hres_c[h] = hb.c;
-          in.hres_m[h] = hb.m;
-          in.hres_g[h] = hb.g;
-        }
-      }
+      if (lane == 0) rebal_store_result(in, h, hb, 0xFFFFFFFFu);
       take(hb.key, h);
     }
   };
@@ -1174,7 +1160,7 @@ __global__ void __launch_bounds__(COOK_WAVE* RB_WAVES) rebal_decide(const RebalI
     unsigned long long bk = 0ull;
     unsigned bh = 0u;
     for (int k = 0; k < RB_WAVES; ++k)
-      if (s_bk[k] != 0ull && (s_bk[k] > bk || (s_bk[k] == bk && s_bh[k] > bh))) bk = s_bk[k], bh = s_bh[k];
+      if (rebal_host_beats(s_bk[k], s_bh[k], bk, bh)) bk = s_bk[k], bh = s_bh[k];
     in.blk_key[phase * in.n_blk + blockIdx.x] = bk;
     in.blk_host[phase * in.n_blk + blockIdx.x] = bh;
     if (in.thr_key != 0ull && phase == 0u && bk != 0ull) atomicMax(in.best_key, bk);
@@ -1208,47 +1194,30 @@ static __device__ void rebal_host_big(const RebalIn& in, const RebalJob& jb, uns
   double *c_mem = big ? in.gs_mem + base : L.mem, *c_gpus = big ? in.gs_gpus + base : L.gpus;
   uint32_t *c_posB = big ? in.gs_posB + base : L.posB, *c_slot = big ? in.gs_slot + base : L.slot;
   uint32_t* c_ord = big ? in.gs_ord + base : L.ord;
-  // ---- pass A: filter (rebalancer.clj:339-349) + the host's last scored task in priority-map order (:369-375) ----------
+  // ---- pass A: filter + the host's last scored task in priority-map order (rebalancer.clj:369-375) ----------------------------
   unsigned n_c = 0;
   double last_d = 0.0;
   unsigned last_pb = 0, last_slot = 0xFFFFFFFFu;
   for (unsigned t0 = 0; t0 < n; t0 += COOK_WAVE) {
     const unsigned t = t0 + lane;
-    const bool valid = t < n;
-    unsigned slot = 0, pb = 0, usr = 0;
-    bool a = false;
-    double d = 0.0;
-    const bool mirrored = valid && t < n_seg;  // a running slot: its columns lie at hs + t of the host-ordered mirrors
-    if (mirrored) {
-      slot = in.hperm[hs + t];
-      pb = in.h_pb[hs + t];
-      a = in.h_act[hs + t] != 0;
-      usr = in.h_user[hs + t];
-      if (a) d = in.h_dru[hs + t];
-    } else if (valid) {  // a job placed earlier in this cycle
-      slot = in.R + rebal_chain_at(in, h, t - n_seg);
-      pb = in.posB[slot];
-      a = in.act[pb] != 0;
-      usr = in.slot_user[slot];
-      if (a) d = in.dru[pb];
+    const bool placed = t >= n_seg && t < n;  // a job placed earlier in this cycle
+    HostItem it = rebal_item(in, hs, n_seg, t, t < n, placed ? rebal_chain_at(in, h, t - n_seg) : 0u);
+    if (it.a && (last_slot == 0xFFFFFFFFu || it.d < last_d || (it.d == last_d && it.pb > last_pb))) {
+      last_d = it.d;
+      last_pb = it.pb;
+      last_slot = it.slot;
     }
-    if (a && (last_slot == 0xFFFFFFFFu || d < last_d || (d == last_d && pb > last_pb))) {
-      last_d = d;
-      last_pb = pb;
-      last_slot = slot;
-    }
-    const bool cand = a && (jb.below || usr == jb.us) && !(d < in.safe_dru) && (d - jb.pdru > in.min_diff);
+    const bool cand = rebal_candidate(in, jb, it);
     const unsigned long long mk = __ballot(cand);
     if (cand) {
       const unsigned idx = n_c + (unsigned)__popcll(mk & lanemask_lt());
-      st_agent(&c_dru[idx], d);
-      st_agent(&c_posB[idx], pb);
-      st_agent(&c_slot[idx], slot);
-      const double xc = mirrored ? in.h_cpus[hs + t] : in.slot_cpus[slot], xm = mirrored ? in.h_mem[hs + t] : in.slot_mem[slot];
-      const double xg = mirrored ? in.h_gpus[hs + t] : in.slot_gpus[slot];
-      st_agent(&c_cpus[idx], xc);
-      st_agent(&c_mem[idx], xm);
-      st_agent(&c_gpus[idx], xg);
+      rebal_item_resources(in, hs, n_seg, t, it);
+      st_agent(&c_dru[idx], it.d);
+      st_agent(&c_posB[idx], it.pb);
+      st_agent(&c_slot[idx], it.slot);
+      st_agent(&c_cpus[idx], it.c);
+      st_agent(&c_mem[idx], it.m);
+      st_agent(&c_gpus[idx], it.g);
     }
     n_c += (unsigned)__popcll(mk);
   }
@@ -1258,18 +1227,14 @@ static __device__ void rebal_host_big(const RebalIn& in, const RebalJob& jb, uns
   if (jb.gtype && !rebal_group_constraint(in, jb, row)) return;
   if (big) __threadfence();
   wave_sync();
-  // ---- pass B: priority-map order inside the host = (dru desc, position in B asc), by counting -----------------------------
+  // ---- pass B: rank by counting over the list ----------------------------------------------------------------------------------
   for (unsigned i0 = 0; i0 < n_c; i0 += COOK_WAVE) {
     const unsigned i = i0 + lane;
     const bool vi = i < n_c;
     const double di = vi ? ld_agent(&c_dru[i]) : 0.0;
     const unsigned pi = vi ? ld_agent(&c_posB[i]) : 0u;
     unsigned r = 0;
-    for (unsigned j = 0; j < n_c; ++j) {
-      const double dj = ld_agent(&c_dru[j]);
-      const unsigned pjx = ld_agent(&c_posB[j]);
-      r += (dj > di || (dj == di && pjx < pi)) ? 1u : 0u;
-    }
+    for (unsigned j = 0; j < n_c; ++j) r += rebal_before(ld_agent(&c_dru[j]), ld_agent(&c_posB[j]), di, pi) ? 1u : 0u;
     if (vi) {
       st_agent(&c_ord[r], i);
       in.srt_slot[base + r] = ld_agent(&c_slot[i]);
@@ -1277,24 +1242,12 @@ static __device__ void rebal_host_big(const RebalIn& in, const RebalJob& jb, uns
   }
   if (big) __threadfence();
   wave_sync();
-  // ---- pass C: prefix aggregates seeded with the spare resources (rebalancer.clj:384-403), best feasible prefix ------------
-  const double jc = jb.c, jm = jb.m, jg = jb.g;
-  const bool need_g = jb.has_gpus != 0;
-  SumU4 carry = SumU4::zero();
-  if (sp) carry = SumU4{0.0, 0.0 + in.spare_c[h], 0.0 + in.spare_m[h], 0.0 + in.spare_g[h], 0u};
-  const SumU4 seed = carry;
-  // per-lane best: key (f64_key(dru), len) lexicographic max; len 0 = the spare pseudo-entry alone
-  unsigned long long bk = 0ull;
-  unsigned bl = 0;
-  double bd = 0.0, bc = 0.0, bm = 0.0, bg = 0.0;
-  const double DMAXV = 1.7976931348623157e308;
-  if (lane == 0 && sp && seed.mem >= jm && seed.cpus >= jc && (need_g ? seed.gpus >= jg : true)) {
-    bk = f64_key(DMAXV);
-    bd = DMAXV;
-    bc = seed.cpus;
-    bm = seed.mem;
-    bg = seed.gpus;
-  }
+  // ---- pass C: prefix aggregates, a chunk of 64 candidates at a time; per-lane best (lane l offers the prefixes l + 1, l + 65, ...) ----
+  const SumU4 seed = rebal_spare_seed(in, h, sp);
+  SumU4 carry = seed;
+  HostBest b;
+  b.clear();
+  if (lane == 0) b.spare_alone(jb, sp, seed);
   unsigned bad = 0u;
   for (unsigned k0 = 0; k0 < n_c; k0 += COOK_WAVE) {
     const unsigned k = k0 + lane;
@@ -1307,49 +1260,25 @@ static __device__ void rebal_host_big(const RebalIn& in, const RebalJob& jb, uns
       d = ld_agent(&c_dru[i]);
     }
     const SumU4 t = combine(carry, wave_incl_scan_u4(x));
-    if (vk) bad |= t.bad;
-    const bool enough = vk && t.mem >= jm && t.cpus >= jc && (need_g ? t.gpus >= jg : true) && d >= 0.0;
-    if (enough) {
-      const unsigned long long key = f64_key(d);
-      if (key >= bk) {  // later prefix wins ties (max-key, rebalancer.clj:404)
-        bk = key;
-        bl = k + 1;
-        bd = d;
-        bc = t.cpus;
-        bm = t.mem;
-        bg = t.gpus;
-      }
+    if (vk) {
+      bad |= t.bad;
+      b.offer(jb, k + 1, d, t.cpus, t.mem, t.gpus);
     }
     carry = wave_bcast_u4(t, COOK_WAVE - 1);
   }
-  if (__any(bad != 0u)) {  // a partial sum rounded: left to right, exactly as the reference's reductions
-    bk = 0ull;
-    bl = 0;
-    if (lane == 0) {
-      double ac = seed.cpus, am = seed.mem, ag = seed.gpus;
-      if (sp && am >= jm && ac >= jc && (need_g ? ag >= jg : true)) {
-        bk = f64_key(DMAXV);
-        bd = DMAXV;
-        bc = ac, bm = am, bg = ag;
-      }
-      for (unsigned k = 0; k < n_c; ++k) {
+  if (__any(bad != 0u)) {  // a partial sum rounded: lane 0 alone, through the list
+    b.clear();
+    if (lane == 0)
+      rebal_redo(jb, sp, seed, n_c, [&](unsigned k, double& dk, double& ck, double& mk, double& gk) {
         const unsigned i = ld_agent(&c_ord[k]);
-        ac += ld_agent(&c_cpus[i]);
-        am += ld_agent(&c_mem[i]);
-        ag += ld_agent(&c_gpus[i]);
-        const double d = ld_agent(&c_dru[i]);
-        if (am >= jm && ac >= jc && (need_g ? ag >= jg : true) && d >= 0.0 && f64_key(d) >= bk) {
-          bk = f64_key(d);
-          bl = k + 1;
-          bd = d;
-          bc = ac, bm = am, bg = ag;
-        }
-      }
-    }
+        ck = ld_agent(&c_cpus[i]), mk = ld_agent(&c_mem[i]), gk = ld_agent(&c_gpus[i]);
+        dk = ld_agent(&c_dru[i]);
+        return true;
+      }, b);
   }
-  // wave arg-max of (bk, bl)
-  unsigned long long mk = bk;
-  unsigned ml = bl;
+  // wave arg-max of (key, len)
+  unsigned long long mk = b.key;
+  unsigned ml = b.len;
   for (int dd = 32; dd >= 1; dd >>= 1) {
     const unsigned long long ok = __shfl_xor(mk, dd, COOK_WAVE);
     const unsigned ol = __shfl_xor(ml, dd, COOK_WAVE);
@@ -1358,15 +1287,8 @@ static __device__ void rebal_host_big(const RebalIn& in, const RebalJob& jb, uns
       ml = ol;
     }
   }
-  if (mk != 0ull && bk == mk && bl == ml) {  // exactly one lane holds (mk, ml): prefix lengths are distinct per lane
-    in.hres_key[h] = mk;
-    in.hres_len[h] = ml;
-    in.hres_base[h] = base;
-    in.hres_dru[h] = bd;
-    in.hres_c[h] = bc;
-    in.hres_m[h] = bm;
-    in.hres_g[h] = bg;
-  }
+  // exactly one lane holds (mk, ml): prefix lengths are distinct per lane
+  if (mk != 0ull && b.key == mk && b.len == ml) rebal_store_result(in, h, b, base);
 }
 
 __global__ void __launch_bounds__(COOK_WAVE* RB_WAVES) rebal_decide_big(const RebalIn* __restrict__ inp) {
@@ -1414,29 +1336,28 @@ __global__ void __launch_bounds__(RB_APPLY_THREADS) rebal_apply(const RebalIn* _
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q)
-      if (k[q] != 0ull && (k[q] > bk || (k[q] == bk && hh[q] >= bh))) bk = k[q], bh = hh[q];  // the later host wins ties
+      if (rebal_host_beats(k[q], hh[q], bk, bh)) bk = k[q], bh = hh[q];
   }
   // hosts of more than 64 items are rebal_decide_big's: their keys are not in any workgroup's entry
   for (unsigned x = tid; x < in.ctl->n_big; x += RB_APPLY_THREADS) {
     const unsigned h = in.big_list[x];
     const unsigned long long k = in.hres_key[h];
-    if (k != 0ull && in.hend[h] - in.hstart[h] + in.x_cnt[h] > (unsigned)COOK_WAVE && (k > bk || (k == bk && h > bh))) bk = k, bh = h;
+    if (in.hend[h] - in.hstart[h] + in.x_cnt[h] > (unsigned)COOK_WAVE && rebal_host_beats(k, h, bk, bh)) bk = k, bh = h;
   }
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long ok = __shfl_xor(bk, d, COOK_WAVE);
-    const unsigned oh = __shfl_xor(bh, d, COOK_WAVE);
-    if (ok > bk || (ok == bk && ok != 0ull && oh > bh)) bk = ok, bh = oh;
-  }
+  auto wave_best = [&]() {  // butterfly: every lane ends with the wave's best entry
+    for (int d = 32; d >= 1; d >>= 1) {
+      const unsigned long long ok = __shfl_xor(bk, d, COOK_WAVE);
+      const unsigned oh = __shfl_xor(bh, d, COOK_WAVE);
+      if (rebal_host_beats(ok, oh, bk, bh)) bk = ok, bh = oh;
+    }
+  };
+  wave_best();
   if (lane == 0) s_key[w] = bk, s_host[w] = bh;
   __syncthreads();
   if (w != 0) return;
   bk = lane < RB_APPLY_THREADS / COOK_WAVE ? s_key[lane] : 0ull;
   bh = lane < RB_APPLY_THREADS / COOK_WAVE ? s_host[lane] : 0u;
-  for (int d = 32; d >= 1; d >>= 1) {
-    const unsigned long long ok = __shfl_xor(bk, d, COOK_WAVE);
-    const unsigned oh = __shfl_xor(bh, d, COOK_WAVE);
-    if (ok > bk || (ok == bk && ok != 0ull && oh > bh)) bk = ok, bh = oh;
-  }
+  wave_best();
   unsigned n_dl = 0;
   if (bk != 0ull) {  // (wave-uniform)  0: no host can take the job — no decision, state unchanged (rebalancer.clj:455-458)
     const unsigned h = bh;
@@ -1461,7 +1382,7 @@ __global__ void __launch_bounds__(RB_APPLY_THREADS) rebal_apply(const RebalIn* _
         g_slot = base == 0xFFFFFFFFu ? s_pre[lane] : in.srt_slot[base + lane];
         g_pbk = in.posB[g_slot];
         g_user = in.slot_user[g_slot];
-        g_known = g_slot < in.R ? (in.attrs_cached ? in.attrs_cached[g_slot] != 0 : true) : in.x_known[g_slot - in.R] != 0;
+        g_known = rebal_slot_known(in, g_slot);
         g_hx = g_slot < in.R ? in.hidx[g_pbk] : 0u;
         g_nt = (in.seg_end[g_user] - in.seg_start[g_user] + RB_RS_TILE - 1) / RB_RS_TILE;
       }
@@ -1574,7 +1495,7 @@ __global__ void __launch_bounds__(RB_APPLY_THREADS) rebal_apply(const RebalIn* _
         if (slot < in.R) in.h_act[in.hidx[pbk]] = 0;
         changed(in.slot_user[slot]);
         in.preempted[c.np++] = slot < in.R ? slot : 0xFFFFFFFFu;  // a task placed this cycle is reported as NONE (rebalancer.clj:529)
-        const bool known = slot < in.R ? (in.attrs_cached ? in.attrs_cached[slot] != 0 : true) : in.x_known[slot - in.R] != 0;
+        const bool known = rebal_slot_known(in, slot);
         if (k == 0) first_known = known;
         if (known) in.pre_hosts[c.n_pre_hosts++] = h;
       }

@@ -245,10 +245,16 @@ def check_rebalance_golden(make_engine):
 
 
 def make_rebalance_case(seed, n_running, n_pending, n_users, n_hosts, *, fractional=False, constraints=False, gpus=False,
-                        spare_frac=0.3, quota_frac=0.1, max_preemption=64, min_dru_diff=0.05, safe_dru=0.0, dru_mode=0, gpu_slots=1):
+                        spare_frac=0.3, quota_frac=0.1, max_preemption=64, min_dru_diff=0.05, safe_dru=0.0, dru_mode=0, gpu_slots=1,
+                        host_sizes=None, host_rng=None):
     """Random pool for cook_rebalance in the shape of the reference's stress generator (test/cook/test/rebalancer.clj:1152-1187)
-    and BASELINE.json C5: running tasks spread over hosts, pending jobs of the same users, some spare capacity."""
+    and BASELINE.json C5: running tasks spread over hosts, pending jobs of the same users, some spare capacity.
+    host_sizes: the number of running tasks of every host (then n_hosts and n_running follow from it, and the tasks are dealt to
+    the hosts by a permutation drawn from host_rng, or from the case's own generator after everything else)."""
     rng = np.random.default_rng(seed)
+    if host_sizes is not None:
+        host_sizes = np.asarray(host_sizes, dtype=np.int64)
+        n_hosts, n_running = len(host_sizes), int(host_sizes.sum())
     R, P = n_running, n_pending
     n = R + P
     cpus = np.clip(np.rint(rng.normal(3.0, 1.0, n)), 1, 8)
@@ -320,12 +326,14 @@ def make_rebalance_case(seed, n_running, n_pending, n_users, n_hosts, *, fractio
     spare = A.HostSpare(host=sh, cpus=rng.integers(0, 6, len(sh)).astype(np.float64) + (0.5 if fractional else 0.0),
                         mem=rng.integers(0, 16, len(sh)) * 1024.0, gpus=rng.integers(0, 3, len(sh)).astype(np.float64))
     rp = A.CookRebalanceParams(safe_dru, min_dru_diff, max_preemption, 0)
+    if host_sizes is not None:
+        running.host = np.repeat(np.arange(n_hosts), host_sizes).astype(np.uint32)[(host_rng or rng).permutation(R)]
     return dict(params=A.default_params(dru_mode=dru_mode), running=running, pending=jobs,
                 pending_job_id=(base + 10_000_000 + rng.permutation(P)).astype(np.int64), pending_priority=prio[R:], users=users,
                 spare=spare, rparams=rp, host_attrs=host_attrs, groups=groups)
 
 
-def rebalance_parity(make_engine, b, min_decisions=0):
+def rebalance_parity(make_engine, b, min_decisions=0, want=None):
     with make_engine(b["params"]) as e:
         e.rebalance_stage(b["running"], b["pending"], b["pending_job_id"], b["pending_priority"], b["users"], b["spare"],
                           b["rparams"], host_attrs=b["host_attrs"], groups=b["groups"])
@@ -333,12 +341,60 @@ def rebalance_parity(make_engine, b, min_decisions=0):
         got = e.rebalance_fetch()
         e.rebalance_run()  # a run must be repeatable on the same staged inputs (it updates spare resources internally)
         again = e.rebalance_fetch()
-    want = pyoracle.rebalance(b["params"], b["running"], b["pending"], b["pending_job_id"], b["pending_priority"], b["users"],
-                              b["spare"], b["rparams"], host_attrs=b["host_attrs"], groups=b["groups"])
+    if want is None:
+        want = pyoracle.rebalance(b["params"], b["running"], b["pending"], b["pending_job_id"], b["pending_priority"], b["users"],
+                                  b["spare"], b["rparams"], host_attrs=b["host_attrs"], groups=b["groups"])
     _rebal_equal(got, want, "random")
     _rebal_equal(again, want, "random, second run")
     assert len(got["decisions"]) >= min_decisions, len(got["decisions"])
     return got
+
+
+REBALANCE_FORM_SIZES = [0, 1, 31, 32, 33, 63, 64, 65, 127, 128, 129]  # around every boundary between the forms that evaluate a host
+
+
+def rebalance_forms_case(seed, fractional, spare_frac, filler=0):
+    """Hosts of every size at which the device takes another form (a pair of hosts per wave up to 32 items, one host in registers up
+    to 64, lists in LDS up to 128, in global memory above), three of each, among `filler` hosts of 0..2 tasks.  -> (case, sizes)"""
+    rng = np.random.default_rng(seed)
+    sizes = np.array(REBALANCE_FORM_SIZES * 3 + list(rng.integers(0, 3, filler)))
+    rng.shuffle(sizes)
+    b = make_rebalance_case(seed=seed, n_running=None, n_pending=48, n_users=12, n_hosts=None, fractional=fractional,
+                            spare_frac=spare_frac, max_preemption=10 ** 6, host_sizes=sizes, host_rng=rng)
+    return b, sizes
+
+
+def rebalance_forms_parity(make_engine, b, sizes):
+    """First the INPUTS, on the oracle's decisions: hosts of every class of size (items = tasks + placed jobs - preempted tasks at the
+    time of the decision) are decided on, and a host is decided on again after a job was placed on it.  Then parity."""
+    want = pyoracle.rebalance(b["params"], b["running"], b["pending"], b["pending_job_id"], b["pending_priority"], b["users"],
+                              b["spare"], b["rparams"], host_attrs=b["host_attrs"], groups=b["groups"])
+    items = np.array(sizes, dtype=np.int64)
+    classes, times = {c: 0 for c in ("<=32", "33..64", "65..128", ">128")}, np.zeros(len(items), dtype=np.int64)
+    for d in want["decisions"]:
+        n = items[d["host"]]
+        classes["<=32" if n <= 32 else "33..64" if n <= 64 else "65..128" if n <= 128 else ">128"] += 1
+        times[d["host"]] += 1
+        items[d["host"]] += 1 - len(d["tasks"])
+    print("rebalance forms: decisions per class", classes, "hosts decided twice", int((times >= 2).sum()))
+    assert all(v >= 1 for v in classes.values()), classes
+    assert (times >= 2).any(), times.max()
+    return rebalance_parity(make_engine, b, want=want)
+
+
+def rebalance_forms_params(seeds=(71, 72)):
+    """test_rebalance_parity_random's inputs at the boundaries between the forms: integer resources (no sum can round), fractional
+    ones (the left-to-right redo in every form), with and without spare resources — and the general path on sums that never round"""
+    return ([dict(forms=s, fractional=f, spare_frac=sp) for s in seeds for f in (False, True) for sp in (0.0, 0.5)]
+            + [dict(forms=71, fractional=False, spare_frac=0.5, general=1)])
+
+
+def rebalance_random(make_engine, kw, monkeypatch):
+    if "forms" not in kw:
+        return rebalance_parity(make_engine, make_rebalance_case(**kw))
+    if kw.get("general"):
+        monkeypatch.setenv("COOK_REBAL_GENERAL", "1")  # read when the run starts
+    return rebalance_forms_parity(make_engine, *rebalance_forms_case(kw["forms"], kw["fractional"], kw["spare_frac"], kw.get("filler", 0)))
 
 
 def rebalance_paths(make_engine):

@@ -222,9 +222,9 @@ def test_rebalance_golden(make_engine):
     dict(seed=707730441, n_running=2, n_pending=29, n_users=9, n_hosts=23, fractional=True, gpus=True, spare_frac=1.0),  # hosts without running tasks that take placed jobs (found by the fuzz sweep)                # spare resources only
     dict(seed=57, n_running=3600, n_pending=10, n_users=2, n_hosts=90),                            # users of several re-scoring tiles
     dict(seed=58, n_running=2600, n_pending=8, n_users=2, n_hosts=70, fractional=True),            # ... redone sequentially
-], ids=lambda kw: "-".join(f"{k}{v}" for k, v in kw.items()))
-def test_rebalance_parity_random(make_engine, kw):
-    P.rebalance_parity(make_engine, P.make_rebalance_case(**kw))
+] + P.rebalance_forms_params(), ids=lambda kw: "-".join(f"{k}{v}" for k, v in kw.items()))  # ... and hosts at every boundary between the forms
+def test_rebalance_parity_random(make_engine, kw, monkeypatch):
+    P.rebalance_random(make_engine, kw, monkeypatch)
 
 
 def test_rebalance_rescoring_paths(make_engine):

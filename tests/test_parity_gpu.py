@@ -226,9 +226,12 @@ def test_rebalance_golden(make_engine):
     dict(seed=707730441, n_running=2, n_pending=29, n_users=9, n_hosts=23, fractional=True, gpus=True, spare_frac=1.0),  # hosts without running tasks that take placed jobs (found by the fuzz sweep)
     dict(seed=57, n_running=60000, n_pending=32, n_users=500, n_hosts=3000, max_preemption=32),  # multi-block scans / sorts
     dict(seed=58, n_running=30000, n_pending=16, n_users=4, n_hosts=900, fractional=True),       # heavy users: many re-scoring tiles, redone sequentially
+] + P.rebalance_forms_params() + [  # hosts at every boundary between the forms; with 1 100 small hosts more, rebal_decide runs in two phases
+    dict(forms=71, fractional=False, spare_frac=0.0, filler=1100),
+    dict(forms=71, fractional=True, spare_frac=0.0, filler=1100),
 ], ids=lambda kw: "-".join(f"{k}{v}" for k, v in kw.items()))
-def test_rebalance_parity_random(make_engine, kw):
-    P.rebalance_parity(make_engine, P.make_rebalance_case(**kw))
+def test_rebalance_parity_random(make_engine, kw, monkeypatch):
+    P.rebalance_random(make_engine, kw, monkeypatch)
 
 
 def test_rebalance_rescoring_paths(make_engine):
