@@ -1533,6 +1533,44 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_matchMetricsMulti(JNIEnv* env, jclas
   }
   return CHECKED(cook_match_metrics_multi(es, (uint32_t)n, rq, rcs));
 }
+/* ---- the launch resources of the last match's placed tasks (cook_match_launch_resources) ----------------------------------------------
+ * n = the match's offers, k = its considered jobs (matchCount; another value: COOK_E_INVALID).  role_cols = {range_off uint32 [n + 1], range_begin int32, range_end int32,
+ * range_role uint8 [range_off[n]], res_source uint32 [n_res], avail double [n_res * n_roles * n], offer_skipped uint8 [n] or null};
+ * out_cols = {port_off uint32 [k + 1], port int32 [cap], port_role uint8 [cap], take double [k * n_res * n_roles], short_mask uint32 [k]};
+ * info_out = one cook_launch_info */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_matchLaunchResources(JNIEnv* env, jclass c, jlong h, jint n, jint k, jint n_roles, jint n_res,
+                                                                 jobjectArray role_cols, jint cap, jobjectArray out_cols, jobject info_out) {
+  int bad = 0;
+  cook_launch_offers o;
+  cook_launch_out out;
+  cook_launch_info* info = BUF(cook_launch_info, info_out);
+  uint64_t n_ranges = 0, cells;
+  uint32_t k_match = 0;
+  (void)c;
+  /* the engine writes cook_match_count entries, whatever k says: a k that is not that count would pass the size checks below and overrun
+   * the buffers (before a match there is no count: the call itself then refuses with COOK_E_STATE and writes nothing) */
+  if (cook_match_count(H(h), &k_match) == COOK_OK && (k < 0 || k_match != (uint32_t)k)) return COOK_E_INVALID;
+  if (n < 0 || k < 0 || cap < 0 || n_roles < 1 || n_roles > COOK_MAX_ROLES || n_res < 1 || n_res > 2 + COOK_MAX_SCALARS || !info || !role_cols || !out_cols)
+    return COOK_E_INVALID;
+  cells = (uint64_t)n_res * (uint64_t)n_roles;
+  o.n = (uint32_t)n, o.n_roles = (uint32_t)n_roles, o.n_res = (uint32_t)n_res, o.reserved = 0;
+  o.range_off = EL(const uint32_t, role_cols, 0, (uint64_t)n + 1u);
+  if (bad || !o.range_off) return COOK_E_INVALID;
+  n_ranges = o.range_off[n];
+  o.range_begin = EL(const int32_t, role_cols, 1, n_ranges);
+  o.range_end = EL(const int32_t, role_cols, 2, n_ranges);
+  o.range_role = EL(const uint8_t, role_cols, 3, n_ranges);
+  o.res_source = EL(const uint32_t, role_cols, 4, n_res);
+  o.avail = EL(const double, role_cols, 5, cells * (uint64_t)n);
+  o.offer_skipped = EL(const uint8_t, role_cols, 6, n);
+  out.cap = (uint32_t)cap, out.reserved = 0;
+  out.port_off = EL(uint32_t, out_cols, 0, (uint64_t)k + 1u);
+  out.port = EL(int32_t, out_cols, 1, cap);
+  out.port_role = EL(uint8_t, out_cols, 2, cap);
+  out.take = EL(double, out_cols, 3, cells * (uint64_t)k);
+  out.short_mask = EL(uint32_t, out_cols, 4, k);
+  return CHECKED(cook_match_launch_resources(H(h), &o, &out, info));
+}
 /* the rows of the last offersRun as the offers of a match / cycle, in place on the device */
 JNIEXPORT jint JNICALL Java_cook_hip_Native_matchStageBuiltOffers(JNIEnv* env, jclass c, jlong h, jint k, jint n_scalars, jobjectArray jobs,
                                                                   jint n_groups, jobjectArray groups, jobject reserved_hosts,

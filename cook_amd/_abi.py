@@ -1217,6 +1217,43 @@ class CookUsageOut(C.Structure):
                 ("bucket_usage", _f64p), ("row_off", _u32p), ("rows", _u32p), ("total", _f64p)]
 
 
+# ---- launch resources (cook_match_launch_resources: the assigned ports and per-role takes of the last match's placed tasks) ------------
+MAX_ROLES = 4
+LAUNCH_CPUS, LAUNCH_MEM, LAUNCH_SCALAR0 = 0, 1, 2
+
+
+class CookLaunchOffers(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("n_roles", C.c_uint32), ("n_res", C.c_uint32), ("reserved", C.c_uint32), ("range_off", _u32p),
+                ("range_begin", _i32p), ("range_end", _i32p), ("range_role", _u8p), ("res_source", _u32p), ("avail", _f64p),
+                ("offer_skipped", _u8p)]
+
+
+class CookLaunchOut(C.Structure):
+    _fields_ = [("cap", C.c_uint32), ("reserved", C.c_uint32), ("port_off", _u32p), ("port", _i32p), ("port_role", _u8p),
+                ("take", _f64p), ("short_mask", _u32p)]
+
+
+class CookLaunchInfo(C.Structure):
+    _fields_ = [("kept", C.c_uint32), ("ports", C.c_uint32), ("offers_used", C.c_uint32), ("short_tasks", C.c_uint32),
+                ("bad_row", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+@dataclass
+class LaunchOffers:
+    """cook_launch_offers: the role view of the last match's offers.  range_off [n + 1], range_begin / range_end (inclusive) /
+    range_role by range, res_source [n_res] (LAUNCH_CPUS, LAUNCH_MEM, LAUNCH_SCALAR0 + s), avail [n_res, n_roles, n],
+    offer_skipped [n] or None.  Roles are in take order ("*" last)."""
+    n: int
+    n_roles: int
+    range_off: np.ndarray
+    range_begin: np.ndarray
+    range_end: np.ndarray
+    range_role: np.ndarray
+    res_source: np.ndarray
+    avail: np.ndarray
+    offer_skipped: Optional[np.ndarray] = None
+
+
 # ---- autoscaling candidates (cook_cycle_autoscale: handle-resource-offers-autoscaling-helper, scheduler.clj:1283-1335) ----------------
 class CookAutoscaleParams(C.Structure):
     _fields_ = [("max_jobs", C.c_uint32), ("n_exclude", C.c_uint32), ("scale_factor", C.c_double), ("offer_skipped", _u8p),

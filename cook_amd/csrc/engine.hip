@@ -68,6 +68,7 @@ struct ChurnBufs;      // churn_host.hpp
 struct ReserveBufs;    // reserve_host.hpp
 struct ResidentRebalBufs;  // rebal_resident_host.hpp
 struct LimiterBufs;    // limiter_host.hpp
+struct LaunchBufs;     // launch_res_host.hpp
 
 }  // namespace
 
@@ -240,6 +241,7 @@ struct cook_engine {
   std::unique_ptr<KubeBufs> kub;       // cook_kube_distribute (allocated on first use)
   std::unique_ptr<UnschedBufs> unb;    // cook_unscheduled (allocated on first use)
   std::unique_ptr<UsageBufs> ugb;      // cook_usage_breakdown* (allocated on first use)
+  std::unique_ptr<LaunchBufs> lrb;     // cook_match_launch_resources (allocated on first use)
   MatchIn last_in{};  // the MatchIn of the last match run (K, j_index as used)
   bool last_in_valid = false;
   bool v_in_is_last = false;  // v_in holds last_in on the device (the window rounds' set-up of the last match uploaded it)
@@ -335,6 +337,7 @@ static void limiter_filter_finish(cook_engine* e, const unsigned* h);
 #include "user_stats_host.hpp"
 #include "autoscale_host.hpp"
 #include "carry_host.hpp"      // a queue cycle's carry: needs the staged user state (considerable_host.hpp)
+#include "launch_res_host.hpp"  // the launch resources of the last match: the carry's keys and segments
 #include "release_host.hpp"    // a queue cycle's release: the carry's segments and column sets
 #include "churn_host.hpp"      // a queue cycle's host churn: the release's host-indexed table, the carry's segments
 #include "reserve_host.hpp"    // the host reservations kept across cycles: the advance's counters (churn_kernels.hpp)
@@ -1039,6 +1042,12 @@ int cook_cycle_rebalance_fetch(cook_engine* e, cook_preemption* decisions, uint3
 int cook_match_explain(cook_engine* e, const uint32_t* job_pos, uint32_t n, uint32_t* counts) {
   return guarded(e, [&] {
     match_explain(e, bufs(e->xb), job_pos, n, counts);
+    prof_collect(e);
+  });
+}
+int cook_match_launch_resources(cook_engine* e, const cook_launch_offers* offers, cook_launch_out* out, cook_launch_info* info) {
+  return guarded(e, [&] {
+    launch_resources(e, offers, out, info);
     prof_collect(e);
   });
 }

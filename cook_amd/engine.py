@@ -715,6 +715,44 @@ class Engine:
                                                _p(out.reshape(-1), C.c_uint32)))
         return out[: len(pos)].copy()
 
+    def match_launch_resources(self, offers: A.LaunchOffers, cap: Optional[int] = None, out: Optional[dict] = None) -> dict:
+        """The assigned ports and the per-role takes of the placed tasks of the LAST match (cook_match_launch_resources: Fenzo's
+        getAssignedPorts and mesos/task.clj's take-resources / take-ports).  -> dict(port_off [K + 1], port [P] int32 ascending per
+        task, port_role [P], take [K, n_res, n_roles] float64 (0.0 = no message), short_mask [K], info = dict(kept, ports,
+        offers_used, short_tasks, bad_row)).  cap: room for the ports; by default a guess from the job count, and a call the library
+        refuses for lack of room alone is made again with the room its info asks for (a refused call has written nothing).  out: a
+        dict of these arrays to write into instead of fresh ones (port / port_role of cap entries; cap is then required).  A refused
+        call raises CookError with the library's code and message; its .info is the call's cook_launch_info."""
+        try:
+            K = self.match_count()
+        except CookError:
+            K = 0  # (no match to size the outputs by: the call itself refuses, with its own message and info)
+        assert out is None or cap is not None, "out needs cap"
+        total = launch_range_ports(offers)
+        guess = cap is None
+        if guess:
+            cap = min(total, max(4096, 4 * K))
+        cap = min(int(cap), 2 ** 32 - 1)
+        while True:
+            mine = out if out is not None else launch_outputs(K, len(offers.res_source), int(offers.n_roles), cap)
+            ro, oo, keep = launch_call_args(offers, mine, cap)
+            info = A.CookLaunchInfo()
+            rc = self._lib.cook_match_launch_resources(self._h, C.byref(ro), C.byref(oo), C.byref(info))
+            del keep
+            d = dict(kept=info.kept, ports=info.ports, offers_used=info.offers_used, short_tasks=info.short_tasks, bad_row=info.bad_row)
+            if guess and rc == -1 and info.bad_row == A.NONE_U32 and cap < info.ports <= total:  # only the room was short
+                cap, guess = int(info.ports), False
+                continue
+            break
+        try:
+            self._chk(rc)
+        except CookError as err:
+            err.info = d
+            raise
+        P = int(mine["port_off"][K])
+        return dict(port_off=mine["port_off"], port=mine["port"][:P], port_role=mine["port_role"][:P], take=mine["take"],
+                    short_mask=mine["short_mask"], info=d)
+
     def match_metrics(self, n_users: int = 0, n_gpu_models: int = 0) -> dict:
         """handle-match-cycle-metrics' numbers (scheduler.clj:1210-1280) for the LAST match."""
         o = _MetricsOut(n_users, n_gpu_models)
@@ -992,6 +1030,41 @@ def cycle_run_kube_multi(engines: Sequence["Engine"], calls: Sequence[dict], rai
         _check_multi(engines, rc)
         return res
     return res, [int(x) for x in rcs]
+
+
+def launch_range_ports(offers: A.LaunchOffers) -> int:
+    """the ports of all ranges of a role view: room that always suffices for Engine.match_launch_resources"""
+    b, e = np.asarray(offers.range_begin, np.int64), np.asarray(offers.range_end, np.int64)
+    return int(min(np.sum(np.maximum(e - b + 1, 0)), 2 ** 32 - 1))
+
+
+def launch_outputs(K: int, n_res: int, n_roles: int, cap: int) -> dict:
+    """fresh output arrays of cook_match_launch_resources for K considered jobs and cap ports"""
+    return dict(port_off=np.zeros(K + 1, np.uint32), port=np.empty(max(1, cap), np.int32), port_role=np.empty(max(1, cap), np.uint8),
+                take=np.zeros((K, n_res, n_roles)), short_mask=np.zeros(K, np.uint32))
+
+
+def launch_call_args(offers: A.LaunchOffers, out: dict, cap: int):
+    """-> (CookLaunchOffers, CookLaunchOut, the arrays their pointers refer to) for cook_match_launch_resources"""
+    o = offers
+    n, n_roles = int(o.n), int(o.n_roles)
+    src = np.ascontiguousarray(o.res_source, dtype=np.uint32)
+    n_res = len(src)
+    roff = np.ascontiguousarray(o.range_off, dtype=np.uint32)
+    rb, re_ = np.ascontiguousarray(o.range_begin, dtype=np.int32), np.ascontiguousarray(o.range_end, dtype=np.int32)
+    rr = np.ascontiguousarray(o.range_role, dtype=np.uint8)
+    avail = np.ascontiguousarray(o.avail, dtype=np.float64)
+    assert len(roff) == n + 1 and len(rb) == len(re_) == len(rr) and avail.size == n_res * n_roles * n
+    skipped = np.ascontiguousarray(o.offer_skipped, dtype=np.uint8) if o.offer_skipped is not None else None
+    assert skipped is None or len(skipped) == n
+    for key in ("port_off", "port", "port_role", "take", "short_mask"):
+        assert out[key].flags["C_CONTIGUOUS"], key
+    pn = lambda a, t: _p(a.reshape(-1), t) if a.size else None  # noqa: E731
+    ro = A.CookLaunchOffers(n, n_roles, n_res, 0, _p(roff, C.c_uint32), pn(rb, C.c_int32), pn(re_, C.c_int32), pn(rr, C.c_uint8),
+                            pn(src, C.c_uint32), pn(avail, C.c_double), _p(skipped, C.c_uint8) if skipped is not None else None)
+    oo = A.CookLaunchOut(int(cap), 0, _p(out["port_off"], C.c_uint32), _p(out["port"], C.c_int32), _p(out["port_role"], C.c_uint8),
+                         pn(out["take"], C.c_double), pn(out["short_mask"], C.c_uint32))
+    return ro, oo, (roff, rb, re_, rr, src, avail, skipped, out)
 
 
 def _check_multi(engines, rc):

@@ -1224,6 +1224,89 @@ typedef struct cook_metrics_req {   /* the arguments of cook_match_metrics for o
 } cook_metrics_req;
 int cook_match_metrics_multi(cook_engine** engines, uint32_t n, const cook_metrics_req* req /* [n] */, int* rc /* [n] or NULL */);
 
+/* ---- LAUNCH RESOURCES: the assigned ports and the per-role takes of every placed task of the last match, on the device ----------
+ * What a Mesos pool needs between the match and the launch: TaskAssignmentResult->task-metadata's :ports-assigned = (vec (sort
+ * getAssignedPorts)) (mesos/task.clj:162-169; written as :instance/ports, scheduler.clj:817-832; the PORT0..PORTn variables and the
+ * docker port mappings, mesos/task.clj:223-236, :322-330) and compile-mesos-messages' split of every placed task's resources over the
+ * host's Mesos roles (mesos/task.clj:404-416: resources-by-role, take-resources, take-all-scalar-resources-for-task,
+ * add-scalar-resources-to-task-infos, take-ports).  Called after any match of the engine, exactly as cook_match_explain is
+ * (cook_match_run, cook_cycle_run*, the queue cycles, cook_cycle_match_multi); it reads that match's resident job_to_offer and job
+ * columns (through the match's j_index where the match read them through it) and writes nothing that any other call reads.
+ *
+ * Inputs (cook_launch_offers): the ROLE VIEW of the offers of that match, indexed by offer row; n must equal the match's offer count.
+ *  - n_roles: 1 .. COOK_MAX_ROLES.  Role ids are given in TAKE order: the caller orders them as (sort-by #(= "*" %) (keys avail))
+ *    does, the "*" role last.  A role a host does not have is passed as amount 0.0 and no range: the reference's
+ *    (or (remaining-resources role-name) 0), which yields no message.
+ *  - port ranges as a CSR: range_off[n + 1], range_begin[], range_end[] (INCLUSIVE, as range-contains? is), range_role[] (< n_roles).
+ *    The ranges of a row are in the order of the lease's portRanges (offer.clj:70-72); over several Mesos offers of one host, in the
+ *    order of resources-by-role's (reduce into).  The ranges of a row must be pairwise disjoint and satisfy 0 <= begin <= end:
+ *    otherwise COOK_E_INVALID with the row in info->bad_row, and nothing is written.  Given that, role-containing-port of a port is
+ *    the role of the range it came from.
+ *  - n_res resource slots, 1 .. 2 + COOK_MAX_SCALARS; res_source[r] says which job column of the match is slot r's request:
+ *    COOK_LAUNCH_CPUS, COOK_LAUNCH_MEM or COOK_LAUNCH_SCALAR0 + s (getScalarRequests = job->scalar-request, scheduler.clj:177-189; the
+ *    note at COOK_MAX_SCALARS applies: under a pool adjuster, scalars 0 / 1 hold the un-adjusted cpus / mem).  A NaN request means
+ *    the job has no request under that name: nothing is taken.
+ *  - avail[n_res][n_roles][n] (slot-major, then role, then row): the resources-by-role amount of each (slot, role, row).  Values must
+ *    be finite and >= 0; anything else: COOK_E_INVALID with info->bad_row.
+ *  - offer_skipped (optional, [n]): filter-matches-for-ratelimit's verdict, as in cook_queue_step.  Tasks on a skipped offer are not
+ *    launched and get nothing.
+ * bad_row is the LOWEST offending row, whatever its fault (ranges, amounts, ports short).
+ *
+ * Semantics.  "Kept" is the carry's predicate: placed, and its offer not skipped.  The kept tasks of an offer are taken in considered
+ * order: Fenzo's assignment order on the VM, and the order of :tasks in a match.
+ *  - PORTS.  Fenzo 0.10.0's source is not in the tree, so this rule is ORACLE-DEFINED, like the tie rules: a fresh set of leases
+ *    starts the VM's port cursor at 0; the c-th consumed port is the c-th port of the row's ranges concatenated in their given order;
+ *    with c_k = the sum of `ports` over the kept tasks ahead of task k on its offer, task k gets ports number c_k .. c_k + ports_k - 1
+ *    of that sequence.  They are returned ASCENDING per task ((vec (sort ...)): a task's slice can span ranges that are not
+ *    ascending), each with its role.  A row whose kept tasks ask for more ports than its ranges hold: COOK_E_INVALID with
+ *    info->bad_row, nothing written (the match cannot produce this when cook_offers.ports was the ranges' size; under a carry the
+ *    caller passes the host's CURRENT ranges).
+ *  - SCALARS.  take-resources, literally: per (offer, slot), task after task, role after role in take order:
+ *    take = min(still_needed, avail[role]); if take > 0: still_needed -= take, avail[role] -= take, and a message (role, take) is
+ *    emitted.  Every subtraction is a plain fp64 operation in exactly that order: the results are bit-identical to the sequential
+ *    reduce for ANY inputs (the promise of the carry's folds).
+ *
+ * Outputs (cook_launch_out), all in the caller's memory and indexed by considered position k in [0, K) (K = cook_match_count):
+ * port_off[K + 1], port[cap] (int32) and port_role[cap] (uint8): task k's ports are port[port_off[k] .. port_off[k + 1]);
+ * take[K][n_res][n_roles] (fp64; 0.0 = no message); short_mask[K]: bit r set when slot r's :amount-still-needed is not 0.
+ * info: kept tasks, ports, offers used (rows with a kept task), tasks with a short slot, bad_row (COOK_NONE_U32: none).  A task that was
+ * not kept gets an empty port list and a zero row.  More than cap ports: COOK_E_INVALID with info filled in and nothing else written.
+ *
+ * Refused before the first launch, whatever the host can know — COOK_E_INVALID: offers, out, info or a needed array NULL, n other
+ * than the match's offer count, n_roles / n_res out of range, a res_source that names no column or a scalar the match did not have,
+ * range_off not starting at 0 or decreasing.  COOK_E_STATE: no match yet, a deferred set-up that has not run, or a Kubernetes-scheduler
+ * cycle (as cook_match_explain answers there).  A refused call changes nothing but *info (zeros, bad_row = COOK_NONE_U32 unless said
+ * otherwise above).  Two stream synchronisations: the first brings the error word and the totals (failures are all-or-nothing, as in
+ * cook_usage_breakdown), the second ends the copies (and brings one word: COOK_E_STATE "internal inconsistency" after it means that the
+ * engine caught itself writing a port out of place — no input can cause it, and the outputs are then not valid).  Left to the host: keeping a host's ranges across a carry or a release, the
+ * task-info protobufs, executor choice, slave ids. */
+#define COOK_MAX_ROLES 4
+#define COOK_LAUNCH_CPUS 0    /* res_source: the match's cook_jobs.cpus */
+#define COOK_LAUNCH_MEM 1     /* ... cook_jobs.mem                      */
+#define COOK_LAUNCH_SCALAR0 2 /* ... + s: named scalar s                */
+typedef struct cook_launch_offers {
+  uint32_t n, n_roles, n_res, reserved;
+  const uint32_t* range_off;    /* [n + 1]                                  */
+  const int32_t* range_begin;   /* [range_off[n]]                           */
+  const int32_t* range_end;
+  const uint8_t* range_role;
+  const uint32_t* res_source;   /* [n_res]                                  */
+  const double* avail;          /* [n_res][n_roles][n]                      */
+  const uint8_t* offer_skipped; /* [n] or NULL                              */
+} cook_launch_offers;
+typedef struct cook_launch_out {
+  uint32_t cap, reserved;       /* room of port / port_role, in ports       */
+  uint32_t* port_off;           /* [K + 1]                                  */
+  int32_t* port;                /* [cap]                                    */
+  uint8_t* port_role;           /* [cap]                                    */
+  double* take;                 /* [K][n_res][n_roles]                      */
+  uint32_t* short_mask;         /* [K]                                      */
+} cook_launch_out;
+typedef struct cook_launch_info {
+  uint32_t kept, ports, offers_used, short_tasks, bad_row, reserved[3];
+} cook_launch_info;
+int cook_match_launch_resources(cook_engine* e, const cook_launch_offers* offers, cook_launch_out* out, cook_launch_info* info);
+
 /* ---- USER STATISTICS: the arithmetic of set-stats-counters! (monitor.clj:40-116, 177-207) from the last rank, on the device --------
  * Per user u and state s (0 running, 1 waiting, 2 starved, 3 waiting-under-quota): per_user[(u*4 + s)*3 + {0,1,2}] = {jobs, cpus, mem};
  * a user absent from a state's map (monitor.clj builds maps) has zeros there and its bit clear in user_state[u] (COOK_USTAT_*).
