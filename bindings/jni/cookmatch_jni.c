@@ -1595,3 +1595,114 @@ JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleStageBuiltOffers(JNIEnv* env, j
   (void)c;
   return CHECKED(cook_cycle_stage_built_offers(H(h), &t, &u, &j, groups ? &g : 0, res, (uint32_t)n_reserved, with_task_limits));
 }
+
+/* ---- the resident pod table: a pool whose offers are rebuilt from its pods every cycle (cook_offers_stage_pod_ids, cook_offers_update,
+ * cook_offers_update_info, cook_offers_fetch_pods, cook_cycle_set_built_offers, cook_cycle_run_queue_pods*) ------------------------------
+ * A pod delta: remove_id = direct buffer of n_remove uint32; add = the eight pod columns of pods_of (n_add rows), add_id = n_add uint32;
+ * node_row = n_node_rows uint32, node_values = the nine node columns of nodes_of (n_node_rows rows, n_attr_keys keys).  Null arrays: none. */
+static cook_pod_delta pod_delta_of(JNIEnv* env, jint n_remove, jobject remove_id, jint n_add, jobjectArray add, jobject add_id, jint n_node_rows,
+                                   jobject node_row, jint n_attr_keys, jobjectArray node_values, cook_pods* pd, cook_nodes* nd, int* bad_out) {
+  cook_pod_delta d;
+  int bad = 0;
+  const jint nr = n_remove > 0 ? n_remove : 0, na = n_add > 0 ? n_add : 0, nn = n_node_rows > 0 ? n_node_rows : 0;
+  *pd = pods_of(env, na, add, &bad);
+  *nd = nodes_of(env, nn, n_attr_keys, node_values, &bad);
+  d.n_remove = remove_id ? (uint32_t)nr : 0u;
+  d.remove_id = BUFN(const uint32_t, remove_id, nr);
+  d.add = add ? pd : 0;
+  d.add_id = BUFN(const uint32_t, add_id, na);
+  d.n_node_rows = node_row ? (uint32_t)nn : 0u;
+  d.node_row = BUFN(const uint32_t, node_row, nn);
+  d.node_values = node_values ? nd : 0;
+  if (bad || n_remove < 0 || n_add < 0 || n_node_rows < 0) *bad_out = 1;
+  return d;
+}
+/* pod_id: direct buffer of n uint32 (the staged pods' ids, row order) */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_offersStagePodIds(JNIEnv* env, jclass c, jlong h, jint n, jobject pod_id, jint id_cap) {
+  int bad = 0;
+  const jint np = n > 0 ? n : 0;
+  const uint32_t* ids = BUFN(const uint32_t, pod_id, np);
+  (void)c;
+  if (bad || n < 0 || id_cap < 0) return COOK_E_INVALID;
+  return cook_offers_stage_pod_ids(H(h), ids, (uint32_t)np, (uint32_t)id_cap);
+}
+JNIEXPORT jint JNICALL Java_cook_hip_Native_offersUpdate(JNIEnv* env, jclass c, jlong h, jint n_remove, jobject remove_id, jint n_add,
+                                                         jobjectArray add, jobject add_id, jint n_node_rows, jobject node_row,
+                                                         jint n_attr_keys, jobjectArray node_values) {
+  int bad = 0;
+  cook_pods pd;
+  cook_nodes nd;
+  const cook_pod_delta d = pod_delta_of(env, n_remove, remove_id, n_add, add, add_id, n_node_rows, node_row, n_attr_keys, node_values, &pd, &nd, &bad);
+  (void)c;
+  return CHECKED(cook_offers_update(H(h), &d));
+}
+/* the counts of the last pod delta (cook_offers_update_info): info_out = direct buffer of one cook_pod_delta_info */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_offersUpdateInfo(JNIEnv* env, jclass c, jlong h, jobject info_out) {
+  int bad = 0;
+  cook_pod_delta_info* out = BUF(cook_pod_delta_info, info_out);
+  (void)c;
+  if (bad || !out) return COOK_E_INVALID;
+  return cook_offers_update_info(H(h), out);
+}
+/* The pod table as it stands (cook_offers_fetch_pods).  cols: {node, cpus, mem, gpus, gpu_model, disk, disk_type, flags, id} direct
+ * buffers with room for cap rows each (null: skipped); n_out: direct buffer of one jint that receives the row count (also when cap is
+ * too small: COOK_E_INVALID, no column written) */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_offersFetchPods(JNIEnv* env, jclass c, jlong h, jint cap, jobjectArray cols, jobject n_out) {
+  int bad = 0, rc;
+  const jint cp = cap > 0 ? cap : 0;
+  cook_pod_rows r;
+  jint* n = BUF(jint, n_out);
+  (void)c;
+  r.cap = (uint32_t)cp;
+  r.n = 0;
+  r.node = EL(uint32_t, cols, 0, cp);
+  r.cpus = EL(double, cols, 1, cp);
+  r.mem = EL(double, cols, 2, cp);
+  r.gpus = EL(int32_t, cols, 3, cp);
+  r.gpu_model = EL(uint32_t, cols, 4, cp);
+  r.disk = EL(double, cols, 5, cp);
+  r.disk_type = EL(uint32_t, cols, 6, cp);
+  r.flags = EL(uint8_t, cols, 7, cp);
+  r.id = EL(uint32_t, cols, 8, cp);
+  if (bad || cap < 0) return COOK_E_INVALID;
+  rc = cook_offers_fetch_pods(H(h), &r);
+  if (n) *n = (jint)r.n;
+  return rc;
+}
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleSetBuiltOffers(JNIEnv* env, jclass c, jlong h, jint with_task_limits) {
+  (void)env, (void)c;
+  return cook_cycle_set_built_offers(H(h), with_task_limits);
+}
+/* cycleRunQueueReserve of a pool whose offers are built from its pods (cook_cycle_run_queue_pods; defer != 0:
+ * cook_cycle_run_queue_pods_multi for this one pool, the placement then runs in cycleMatchMulti): no host churn, the pod delta of
+ * pod_delta_of in its place (has_pods = 0: none, a rebuild from the table as it stands); the step carries no offers. */
+JNIEXPORT jint JNICALL Java_cook_hip_Native_cycleRunQueuePods(JNIEnv* env, jclass c, jlong h, jint num_considerable, jint remove_mode,
+                                                              jint n_last_offers, jobject offer_skipped, jint n_groups, jobjectArray groups,
+                                                              jint carry_usage, jint n_users, jobject tokens_left, jint n_finished,
+                                                              jint n_fin_scalars, jobjectArray finished, jint release_usage, jint release_groups,
+                                                              jint has_pods, jint n_remove, jobject remove_id, jint n_add, jobjectArray add,
+                                                              jobject add_id, jint n_node_rows, jobject node_row, jint n_attr_keys,
+                                                              jobjectArray node_values, jint release_matched, jint replace, jint n_reserve,
+                                                              jobject rsv_pending, jobject rsv_host, jint with_task_limits, jint defer) {
+  int bad = 0;
+  cook_pods pd;
+  cook_nodes nd;
+  cook_groups g = groups_of(env, n_groups, groups, &bad);
+  const cook_queue_step s = step_of(env, remove_mode, n_last_offers, offer_skipped, 0, groups ? &g : 0, &bad);
+  const cook_queue_carry cy = carry_of(env, 0, carry_usage, n_users, tokens_left, &bad);
+  const cook_finished f = finished_of(env, n_finished, n_fin_scalars, finished, 0, release_usage, release_groups, &bad);
+  const cook_reservations rv = reservations_of(env, release_matched, replace, n_reserve, rsv_pending, rsv_host, &bad);
+  const cook_pod_delta d = pod_delta_of(env, n_remove, remove_id, n_add, add, add_id, n_node_rows, node_row, n_attr_keys, node_values, &pd, &nd, &bad);
+  cook_engine* e = H(h);
+  const cook_queue_step* sp = &s;
+  const uint32_t k = (uint32_t)num_considerable;
+  const cook_queue_carry* cp = &cy;
+  const cook_finished* fp = finished ? &f : 0;
+  const cook_pod_delta* dp = has_pods ? &d : 0;
+  const cook_reservations* rp = &rv;
+  const int32_t wl = (int32_t)with_task_limits;
+  (void)c;
+  if (bad) return COOK_E_INVALID;
+  return defer ? cook_cycle_run_queue_pods_multi(&e, 1, &sp, &cp, &fp, &dp, &rp, &wl, &k)
+               : cook_cycle_run_queue_pods(e, sp, cp, fp, dp, rp, with_task_limits, k);
+}

@@ -989,6 +989,71 @@ class Pods:
                         _ptr(self.gpu_model, _u32p), _ptr(self.disk, _f64p), _ptr(self.disk_type, _u32p), _ptr(self.flags, _u8p))
 
 
+class CookPodDelta(C.Structure):  # cook_offers_update, cook_cycle_run_queue_pods*
+    _fields_ = [("n_remove", C.c_uint32), ("remove_id", _u32p), ("add", C.POINTER(CookPods)), ("add_id", _u32p),
+                ("n_node_rows", C.c_uint32), ("node_row", _u32p), ("node_values", C.POINTER(CookNodes))]
+
+
+class CookPodDeltaInfo(C.Structure):  # cook_offers_update_info
+    _fields_ = [("removed", C.c_uint32), ("remove_missing", C.c_uint32), ("added", C.c_uint32), ("node_rows", C.c_uint32),
+                ("n_pods", C.c_uint32), ("n_offers", C.c_uint32)]
+
+
+class CookPodRows(C.Structure):  # cook_offers_fetch_pods
+    _fields_ = [("cap", C.c_uint32), ("n", C.c_uint32), ("node", _u32p), ("cpus", _f64p), ("mem", _f64p), ("gpus", _i32p),
+                ("gpu_model", _u32p), ("disk", _f64p), ("disk_type", _u32p), ("flags", _u8p), ("id", _u32p)]
+
+
+POD_COLUMNS = (("node", np.uint32), ("cpus", np.float64), ("mem", np.float64), ("gpus", np.int32), ("gpu_model", np.uint32),
+               ("disk", np.float64), ("disk_type", np.uint32), ("flags", np.uint8), ("id", np.uint32))
+
+
+class PodDelta:
+    """What changed in a pool's pods between two match cycles (cook_pod_delta).  remove: ids of the pods that leave; add / add_id: a
+    Pods with the rows that join, behind the last survivor in list order, and their ids; node_rows / node_values: node rows replaced
+    in place by the rows of a Nodes (host None there: the rows keep their host ids).  A pod the watch modifies is a remove plus an add."""
+
+    def __init__(self, remove=None, add: Optional["Pods"] = None, add_id=None, node_rows=None, node_values: Optional["Nodes"] = None,
+                 node_host=None):
+        self.remove = _arr(remove if remove is not None else [], np.uint32)
+        self.add = add
+        self.add_id = _arr(add_id, np.uint32)
+        self.node_rows = _arr(node_rows if node_rows is not None else [], np.uint32)
+        self.node_values = node_values
+        self.node_host = _arr(node_host, np.uint32)  # (Nodes fills a missing host column with 0..n-1: the delta's is given apart)
+
+    def as_struct(self):
+        """-> (CookPodDelta, the objects its pointers refer to)"""
+        ps = self.add.as_struct() if self.add is not None else None
+        ns = self.node_values.as_struct() if self.node_values is not None else None
+        if ns is not None:
+            ns.host = _ptr(self.node_host, _u32p)
+        st = CookPodDelta(len(self.remove), _ptr(self.remove, _u32p) if len(self.remove) else _u32p(), C.pointer(ps) if ps is not None else None,
+                          _ptr(self.add_id, _u32p), len(self.node_rows), _ptr(self.node_rows, _u32p) if len(self.node_rows) else _u32p(),
+                          C.pointer(ns) if ns is not None else None)
+        return st, (ps, ns, self.remove, self.add, self.add_id, self.node_rows, self.node_values, self.node_host)
+
+
+class PodRows:
+    """Caller-owned columns cook_offers_fetch_pods fills: room for `cap` rows in every pod column and the ids; .n is what the call wrote."""
+
+    def __init__(self, cap: int):
+        self.cap = int(cap)
+        self.cols = {k: np.zeros(max(1, self.cap), dt) for k, dt in POD_COLUMNS}
+        self.struct = CookPodRows(self.cap, 0, *[_ptr(self.cols[k], _PT[dt]) for k, dt in POD_COLUMNS])
+
+    @property
+    def n(self):
+        return int(self.struct.n)
+
+    def column(self, name):
+        return self.cols[name][:self.n]
+
+    def pods(self) -> "Pods":
+        """The table as a Pods (every column)"""
+        return Pods(**{k: self.column(k).copy() for k, _ in POD_COLUMNS if k != "id"})
+
+
 def offer_params(clobber_synthetic_pods=False, filter_out_unsound_gpu_nodes=False, max_pods_per_node=2 ** 31 - 1,
                  n_gpu_models=0, n_disk_types=0, gpu_slots=1, disk_slots=1) -> CookOfferParams:
     """gpu_slots / disk_slots: entries per offer row of the "gpus" / "disk" maps (the node's own model plus the models only its

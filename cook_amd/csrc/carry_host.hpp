@@ -15,6 +15,10 @@ struct QueueArgs {
   const cook_finished* finished;
   const cook_host_churn* hosts;
   const cook_reservations* reservations;
+  // cook_cycle_run_queue_pods* (podtable_host.hpp): the offers are rebuilt from the resident pod table inside the advance
+  const cook_pod_delta* pods = nullptr;
+  bool pods_on = false;
+  int with_task_limits = 0;
 };
 
 // where a queue cycle's advance lands its read-backs in h_scratch, in 64-bit words: the advance's two counters (1 word), the carry's

@@ -53,6 +53,7 @@ struct KernelStat {
 struct RebalBufs;  // rebalance_host.hpp
 struct ConsBufs;   // considerable_host.hpp
 struct OfferBufs;  // offers_host.hpp
+struct PodTableBufs;  // podtable_host.hpp
 struct ExplainBufs;  // explain_host.hpp
 struct UpdateBufs;   // cycle_update.hpp
 struct UserStatsBufs;  // user_stats_host.hpp
@@ -232,6 +233,8 @@ struct cook_engine {
   std::unique_ptr<ConsBufs> cb;
   // ---- offer construction (allocated on first use) ----
   std::unique_ptr<OfferBufs> ofb;
+  std::unique_ptr<PodTableBufs> ptb;  // the resident pod table's identity and delta (allocated on first use)
+  bool offers_built = false;          // the staged offers are rows of this engine's cook_offers_run, in place (offers_note_hosts)
   // ---- why-unscheduled summaries / match-cycle metrics (allocated on first use) ----
   std::unique_ptr<ExplainBufs> xb;
   std::unique_ptr<UpdateBufs> ub;  // cook_cycle_update (allocated on first use)
@@ -342,6 +345,7 @@ static void limiter_filter_finish(cook_engine* e, const unsigned* h);
 #include "churn_host.hpp"      // a queue cycle's host churn: the release's host-indexed table, the carry's segments
 #include "reserve_host.hpp"    // the host reservations kept across cycles: the advance's counters (churn_kernels.hpp)
 #include "limiter_host.hpp"    // the launch-rate limiters kept across cycles: QueueArgs (carry_host.hpp), the advance's counters
+#include "podtable_host.hpp"   // the resident pod table: OfferBufs (offers_host.hpp), QueueArgs; queue_host.hpp calls its queue part
 #include "queue_host.hpp"
 #include "sweep_host.hpp"
 #include "unscheduled_host.hpp"
@@ -671,6 +675,31 @@ int cook_cycle_run_queue_reserve_multi(cook_engine** engines, uint32_t n, const 
                                        const cook_finished* const* finished, const cook_host_churn* const* hosts,
                                        const cook_reservations* const* reservations, const uint32_t* num_considerable) {
   return queue_run_multi(engines, n, steps, carries, finished, hosts, reservations, num_considerable);
+}
+// ... of a pool whose offers are built from its pods (podtable_host.hpp): no host churn, the pod delta and the rebuild in its place
+static QueueArgs queue_pods_args(const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished, const cook_pod_delta* pods,
+                                 const cook_reservations* reservations, int with_task_limits) {
+  QueueArgs q{step, carry, finished, nullptr, reservations};
+  q.pods = pods, q.pods_on = true, q.with_task_limits = with_task_limits;
+  return q;
+}
+int cook_cycle_run_queue_pods(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
+                              const cook_pod_delta* pods, const cook_reservations* reservations, int with_task_limits, uint32_t num_considerable) {
+  return queue_run_one(e, queue_pods_args(step, carry, finished, pods, reservations, with_task_limits), num_considerable, /*defer=*/false);
+}
+// the pools one after another (offers_* are launches of their own, not batched behind cook_multi): each exactly its single call, deferred
+int cook_cycle_run_queue_pods_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps, const cook_queue_carry* const* carries,
+                                    const cook_finished* const* finished, const cook_pod_delta* const* pods,
+                                    const cook_reservations* const* reservations, const int32_t* with_task_limits, const uint32_t* num_considerable) {
+  if (!engines || n == 0 || !num_considerable || !engines_valid(engines, n, false)) return COOK_E_INVALID;
+  auto at = [](auto* const* part, uint32_t i) { return part ? part[i] : nullptr; };
+  int first = COOK_OK;
+  for (uint32_t i = 0; i < n; ++i) {
+    const QueueArgs q = queue_pods_args(at(steps, i), at(carries, i), at(finished, i), at(pods, i), at(reservations, i), with_task_limits ? with_task_limits[i] : 0);
+    const int rc = queue_run_one(engines[i], q, num_considerable[i], /*defer=*/true);
+    if (rc != COOK_OK && first == COOK_OK) first = rc;
+  }
+  return first;
 }
 int cook_cycle_set_reservations(cook_engine* e, const cook_reservations* r) {
   return guarded(e, [&] {
@@ -1082,7 +1111,31 @@ int cook_batch_stats(const cook_engine* lead, uint32_t out[5]) {
 }
 
 int cook_offers_stage(cook_engine* e, const cook_nodes* nodes, const cook_pods* pods, const cook_offer_params* params) {
-  return guarded(e, [&] { offers_stage(e, bufs(e->ofb), nodes, pods, params); });
+  return guarded(e, [&] {
+    if (e->ptb) e->ptb->drop_ids();  // (the pods' ids go with the table they named)
+    offers_stage(e, bufs(e->ofb), nodes, pods, params);
+  });
+}
+int cook_offers_stage_pod_ids(cook_engine* e, const uint32_t* pod_id, uint32_t n, uint32_t id_cap) {
+  return guarded(e, [&] { podtable_stage_ids(e, pod_id, n, id_cap); });
+}
+int cook_offers_update(cook_engine* e, const cook_pod_delta* d) {
+  return guarded(e, [&] {
+    podtable_update(e, d);
+    prof_collect(e);
+  });
+}
+int cook_offers_update_info(cook_engine* e, cook_pod_delta_info* out) {
+  return guarded(e, [&] { podtable_info(e, out); });
+}
+int cook_offers_fetch_pods(cook_engine* e, cook_pod_rows* out) {
+  return guarded(e, [&] { podtable_fetch(e, out); });
+}
+int cook_cycle_set_built_offers(cook_engine* e, int with_task_limits) {
+  return guarded(e, [&] {
+    podq_set_built_offers(e, with_task_limits);
+    prof_collect(e);
+  });
 }
 int cook_offers_run(cook_engine* e) {
   return guarded(e, [&] {

@@ -33,6 +33,7 @@ void offers_note_hosts(cook_engine* e, const uint32_t* host, unsigned M, bool on
   e->o_hosts.clear();
   e->o_run_cols_made = false;
   e->o_hosts_known = on_host;
+  e->offers_built = !on_host;
   if (!on_host || !M) return;
   std::vector<uint32_t> hs(host, host + M);
   std::sort(hs.begin(), hs.end());

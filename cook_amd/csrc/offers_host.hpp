@@ -6,6 +6,7 @@ struct OfferBufs {
   unsigned Nn = 0, Np = 0, n_attr = 0, n_offers = 0;
   cook_offer_params params{};
   double ms = 0;
+  uint32_t max_host = 0xFFFFFFFFu;  // an upper bound of the staged nodes' host ids (0xFFFFFFFF: no host column); the pods' queue cycles size host tables by it
   // inputs
   DArr<double> n_cpus, n_mem, n_disk, p_cpus, p_mem, p_disk;
   DArr<int32_t> n_gpus, p_gpus;
@@ -48,6 +49,8 @@ void offers_stage(cook_engine* e, OfferBufs& b, const cook_nodes* nodes, const c
   b.gpu_slots = res_slots(e, params->gpu_slots, "cook_offers_stage: gpu_slots");
   b.disk_slots = res_slots(e, params->disk_slots, "cook_offers_stage: disk_slots");
   b.n_attr = nodes->attr ? nodes->n_attr_keys : 0u;
+  b.max_host = 0xFFFFFFFFu;
+  if (nodes->host && Nn) b.max_host = *std::max_element(nodes->host, nodes->host + Nn);
   h2d(e, b.n_cpus, nodes->cpus, Nn);
   h2d(e, b.n_mem, nodes->mem, Nn);
   b.nd = NodeCols{b.n_cpus.ptr(), b.n_mem.ptr(), h2d_opt(e, b.n_gpus, nodes->gpus, Nn), h2d_opt(e, b.n_gpu_model, nodes->gpu_model, Nn),
@@ -65,7 +68,9 @@ void offers_stage(cook_engine* e, OfferBufs& b, const cook_nodes* nodes, const c
   b.staged = true;
 }
 
-void offers_run(cook_engine* e, OfferBufs& b) {
+// everything of cook_offers_run but its synchronisation: the kernels, and the offer count on its way into h_scratch[h_word] (a queue
+// cycle's rebuild lets it ride in the advance's read-back; offers_finish takes it from there)
+void offers_enqueue(cook_engine* e, OfferBufs& b, unsigned h_word) {
   if (!b.staged) e->fail(COOK_E_STATE, "cook_offers_run before cook_offers_stage");
   const unsigned Nn = b.Nn, Np = b.Np;
   const unsigned G = b.params.n_gpu_models + 1u, D = b.params.n_disk_types + 1u;
@@ -81,10 +86,7 @@ void offers_run(cook_engine* e, OfferBufs& b) {
   memset_async(e, b.disk_cap.ptr(), 0, (size_t)D * 8);
   memset_async(e, b.disk_cons.ptr(), 0, (size_t)D * 8);
   memset_async(e, b.totals.ptr(), 0, sizeof(OfferTotalsDev));
-  if (Nn == 0) {
-    b.done = true;
-    return;
-  }
+  if (Nn == 0) return;
   const unsigned gN = div_up(Nn, 256);
   // ---- pods stably partitioned by node: within a node the list order of node-name->pods survives ----------------------------
   b.seg_start.ensure(Nn);
@@ -131,10 +133,16 @@ void offers_run(cook_engine* e, OfferBufs& b) {
                  b.o_gpu_model.ensure((size_t)Nn * GS), b.o_gpu_count.ensure((size_t)Nn * GS),  b.o_disk_type.ensure((size_t)Nn * DS), b.o_disk_space.ensure((size_t)Nn * DS),
                  b.o_num_pods.ensure(Nn),  b.o_attr.ensure((size_t)Nn * std::max(1u, b.n_attr))};
   KL("offers_emit", offers_emit, gN, 256, b.nd, b.d_host, av, (const uint32_t*)b.block_offers.ptr(), b.d_attr, b.n_attr, GS, DS, rows, d_total);
-  copy_async(e, e->h_scratch, d_total, 4, hipMemcpyDeviceToHost);
-  sync(e);
-  std::memcpy(&b.n_offers, e->h_scratch, 4);
+  pinned_copy(e, e->h_scratch + h_word, d_total, 4, hipMemcpyDeviceToHost);
+}
+void offers_finish(cook_engine* e, OfferBufs& b, unsigned h_word) {
+  if (b.Nn) std::memcpy(&b.n_offers, e->h_scratch + h_word, 4);
   b.done = true;
+}
+void offers_run(cook_engine* e, OfferBufs& b) {
+  offers_enqueue(e, b, 0);
+  if (b.Nn) sync(e);
+  offers_finish(e, b, 0);
 }
 
 template <class T>
@@ -184,15 +192,13 @@ COOK_KERNEL void fill_i32(int32_t* p, unsigned n, int32_t v) {
 }
 // the rows of the last cook_offers_run as a cook_offers of device columns (offer.clj:31-76: Kubernetes leases; COOK_MAX_TASKS_PER_HOST
 // = the cluster's max pods per node, COOK_NUM_TASKS_ON_HOST = the node's pod count)
-cook_offers built_offers_view(cook_engine* e, int with_task_limits) {
-  if (!e->ofb || !e->ofb->done) e->fail(COOK_E_STATE, "built offers requested before cook_offers_run");
-  OfferBufs& b = *e->ofb;
-  const unsigned M = b.n_offers;
-  b.o_k8s.ensure(std::max(1u, M));
-  b.o_max_tasks.ensure(std::max(1u, M));
-  if (M) {
-    memset_async(e, b.o_k8s.ptr(), 1, M);
-    KM<fill_i32, 256>(e, "fill_i32", div_up(M, 256), b.o_max_tasks.ptr(), M, (int32_t)b.params.max_pods_per_node);
+// fill: the rows whose two constant columns are written (a rebuild whose count is still on its way: every node's)
+cook_offers built_offers_cols(cook_engine* e, OfferBufs& b, unsigned M, unsigned fill, int with_task_limits) {
+  b.o_k8s.ensure(std::max(1u, fill));
+  b.o_max_tasks.ensure(std::max(1u, fill));
+  if (fill) {
+    memset_async(e, b.o_k8s.ptr(), 1, fill);
+    KM<fill_i32, 256>(e, "fill_i32", div_up(fill, 256), b.o_max_tasks.ptr(), fill, (int32_t)b.params.max_pods_per_node);
   }
   cook_offers o;
   std::memset(&o, 0, sizeof(o));
@@ -214,4 +220,8 @@ cook_offers built_offers_view(cook_engine* e, int with_task_limits) {
     o.num_tasks = b.o_num_pods.ptr();
   }
   return o;
+}
+cook_offers built_offers_view(cook_engine* e, int with_task_limits) {
+  if (!e->ofb || !e->ofb->done) e->fail(COOK_E_STATE, "built offers requested before cook_offers_run");
+  return built_offers_cols(e, *e->ofb, e->ofb->n_offers, e->ofb->n_offers, with_task_limits);
 }

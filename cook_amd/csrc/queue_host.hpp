@@ -8,7 +8,8 @@
 // in the same synchronisation.  A host churn (churn_host.hpp) is enqueued behind the release; its counter rides there too.  The host
 // reservations (reserve_host.hpp) are enqueued behind the churn: they touch neither the queue nor the offers, and their two counters
 // ride there as well.  The launch-rate limiters (limiter_host.hpp) spend the last cycle's kept placements behind the reservations; their two
-// counters ride there too.
+// counters ride there too.  The pod delta and the offer rebuild of a pool whose offers are built from its pods (podtable_host.hpp) are enqueued
+// behind all of these, which read the old rows; the rebuilt offer count rides in the same synchronisation.
 #pragma once
 #include "queue_kernels.hpp"
 
@@ -41,6 +42,7 @@ void queue_check_step(cook_engine* e, const QueueArgs& q) {
   churn_check(e, q);
   reserve_check(e, q);
   limiter_check(e, q);
+  podq_check(e, q);
   if (!s) return;
   if (s->remove_mode > 1u) e->fail(COOK_E_INVALID, "cook_queue_step.remove_mode: 0 = the kept matches, 1 = every considered job");
   if (s->offer_skipped && s->n_offer_skipped != e->M)
@@ -136,6 +138,8 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   if (q.reservations || e->rvb) reserve_enqueue(e, q.reservations, cnt, skipped, advance ? k : 0u);
   // ---- the launch-rate limiters: the last cycle's kept placements spend their tokens, in front of the considerable filters --------------------
   limiter_enqueue(e, cnt, skipped, advance ? k : 0u);
+  // ---- the pod delta and the offer rebuild (cook_cycle_run_queue_pods*): behind everything above, which reads the OLD rows -----------------------
+  if (q.pods_on) podq_enqueue(e, q);
   if (release || churn || reserve || spend) pinned_copy(e, e->h_scratch + REL_H_CNT, cnt, REL_CNT_WORDS * 4, hipMemcpyDeviceToHost);
   // ---- the step's groups and offers (behind the kernels above on the stream: the fold read the OLD offers) ------------------------------
   if (s && s->groups && G) {
@@ -153,7 +157,8 @@ void queue_advance(cook_engine* e, const QueueArgs& q) {
   if (s && s->offers) match_stage_offers(e, s->offers, false);
   if (e->chb) e->chb->info.n_offers = e->M;  // (the rows behind the advance, whoever set them)
   carry_tokens(e, c);
-  if (advance || release || churn || reserve || spend || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
+  if (advance || release || churn || reserve || spend || q.pods_on || (s && (s->groups || s->offers)) || (c && c->tokens_left)) sync(e);  // (the host arrays of the step are read until here)
+  if (q.pods_on) podq_finish(e, q);  // (the rebuilt rows are the staged offers from here)
   if (c) carry_finish(e);
   if (advance) {
     unsigned h[2] = {0, 0};

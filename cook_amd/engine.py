@@ -827,6 +827,52 @@ class Engine:
                                                           C.byref(gs) if gs is not None else None, _p(res, C.c_uint32),
                                                           len(reserved_hosts), int(bool(with_task_limits))))
 
+    # ---- the resident pod table: a pool whose offers are rebuilt from its pods every cycle -----------------------------
+    def offers_stage_pod_ids(self, pod_id, id_cap: int):
+        """The staged pods' ids (cook_offers_stage_pod_ids): pod_id[i] names staged pod row i, dense slot numbers below id_cap."""
+        ids = np.ascontiguousarray(pod_id, np.uint32)
+        self._chk(self._lib.cook_offers_stage_pod_ids(self._h, _p(ids, C.c_uint32) if len(ids) else None, len(ids), int(id_cap)))
+
+    def offers_update(self, delta: A.PodDelta):
+        """A pod delta applied to the resident tables on the device (cook_offers_update): see A.PodDelta for the order rule."""
+        st, keep = delta.as_struct()
+        self._chk(self._lib.cook_offers_update(self._h, C.byref(st)))
+        del keep
+
+    def offers_update_info(self) -> dict:
+        """The counts of the last pod delta (cook_offers_update_info)."""
+        out = A.CookPodDeltaInfo()
+        self._chk(self._lib.cook_offers_update_info(self._h, C.byref(out)))
+        return {k: int(getattr(out, k)) for k, _ in A.CookPodDeltaInfo._fields_}
+
+    def offers_fetch_pods(self, rows: Optional[A.PodRows] = None) -> A.PodRows:
+        """The pod table as it stands, list order (cook_offers_fetch_pods).  rows None: sized by the table."""
+        probe = A.CookPodRows()  # cap 0: the call reports n (and refuses cap < n without a synchronisation)
+        rc = self._lib.cook_offers_fetch_pods(self._h, C.byref(probe))
+        if rc != 0 and probe.n == 0:
+            self._chk(rc)
+        if rows is None:
+            rows = A.PodRows(probe.n)
+        self._chk(self._lib.cook_offers_fetch_pods(self._h, C.byref(rows.struct)))
+        return rows
+
+    def cycle_set_built_offers(self, with_task_limits: bool = False):
+        """The rows of the last offers_run become the staged offers of the cycle in place (cook_cycle_set_built_offers); the next cycle
+        is a rank cycle."""
+        self._chk(self._lib.cook_cycle_set_built_offers(self._h, int(bool(with_task_limits))))
+
+    def cycle_run_queue_pods(self, num_considerable: int, carry: Optional[A.QueueCarry] = None, finished: Optional[A.Finished] = None,
+                             pods: Optional[A.PodDelta] = None, reservations: Optional[A.Reservations] = None,
+                             with_task_limits: bool = False, **step):
+        """A queue cycle of a pool whose offers are built from its pods (cook_cycle_run_queue_pods): cycle_run_queue_reserve without a
+        host churn; behind the parts that read the old rows the pod delta is applied (None: none), the offers are rebuilt from the
+        resident tables and become the staged offers, then considerable -> take K -> match."""
+        st, keep = self._queue_step(**step)
+        built = [p.as_struct() if p is not None else (None, None) for p in (carry, finished, pods, reservations)]
+        self._chk(self._lib.cook_cycle_run_queue_pods(self._h, C.byref(st), *[C.byref(s) if s is not None else None for s, _ in built],
+                                                      int(bool(with_task_limits)), int(num_considerable)))
+        del keep, built
+
     def offers_timing(self) -> float:
         ms = C.c_double(0)
         self._lib.cook_offers_timing(self._h, C.byref(ms))
@@ -1237,6 +1283,29 @@ def cycle_run_queue_reserve_multi(engines: Sequence[Engine], num_considerable, s
     """cycle_run_queue_hosts_multi with one cook_reservations per engine (cook_cycle_run_queue_reserve_multi; None: none for that
     pool); cycle_match_multi places them.  A pool whose step is refused stays as it was and raises after the others have gone on."""
     _queue_call_multi("cook_cycle_run_queue_reserve_multi", engines, num_considerable, steps, carries, finished, hosts, reservations)
+
+
+def cycle_run_queue_pods_multi(engines: Sequence[Engine], num_considerable, steps: Optional[Sequence[Optional[dict]]] = None,
+                               carries: Optional[Sequence[Optional[A.QueueCarry]]] = None,
+                               finished: Optional[Sequence[Optional[A.Finished]]] = None,
+                               pods: Optional[Sequence[Optional[A.PodDelta]]] = None,
+                               reservations: Optional[Sequence[Optional[A.Reservations]]] = None, with_task_limits=False):
+    """cycle_run_queue_pods of several engines in ONE call (cook_cycle_run_queue_pods_multi), the pools one after another, each placement
+    deferred to cycle_match_multi.  A pool that is refused stays as it was and raises after the others have gone on."""
+    if not engines:
+        return
+    n = len(engines)
+    arr = (C.c_void_p * n)(*[e._h for e in engines])
+    ks = [int(num_considerable)] * n if np.isscalar(num_considerable) else [int(k) for k in num_considerable]
+    ks = (C.c_uint32 * n)(*[min(k, 0xFFFFFFFF) for k in ks])
+    wl = [bool(with_task_limits)] * n if np.isscalar(with_task_limits) else list(with_task_limits)
+    wl = (C.c_int32 * n)(*[int(bool(w)) for w in wl])
+    steps, *parts = [list(x) if x is not None else [None] * n for x in (steps, carries, finished, pods, reservations)]
+    assert len(steps) == n and all(len(ps) == n for ps in parts)
+    built = [[e._queue_step(**(s or {})) for e, s in zip(engines, steps)]]
+    built += [[p.as_struct() if p is not None else (None, None) for p in ps] for ps in parts]
+    ptrs = [(C.c_void_p * n)(*[C.addressof(st) if st is not None else None for st, _ in b]) for b in built]
+    _check_multi(engines, engines[0]._lib.cook_cycle_run_queue_pods_multi(arr, n, *ptrs, wl, ks))
 
 
 def reservations_of(decisions, pending_ord=None):

@@ -1582,6 +1582,94 @@ int cook_cycle_stage_built_offers(cook_engine* e, const cook_tasks* tasks, const
                                   const cook_groups* groups, const uint32_t* reserved_hosts, uint32_t n_reserved,
                                   int with_task_limits);
 
+/* ---- THE RESIDENT POD TABLE: a Kubernetes pool whose offers are rebuilt from its pods every match cycle -------------------------
+ * (kubernetes/compute_cluster.clj:539-545 pending-offers -> generate-offers on every match trigger, over the node map and the pod
+ * map plus the starting pods, :314-319 add-starting-pods; every offer carries :reject-after-match-attempt, :188: nothing stands
+ * between cycles.)  cook_offers_stage uploads both tables; from there on the pod table LIVES on the device and takes what changed
+ * between two cycles as short lists.  All of this is additive: cook_offers_stage / _run / _fetch work as before.
+ *
+ * Identity.  cook_offers_stage_pod_ids gives the staged pods ids: pod_id[i] is the id of staged pod row i (n = the staged row
+ * count, else COOK_E_INVALID), dense caller-chosen slot numbers below id_cap in the identity convention at the top of this file,
+ * each at most once (COOK_E_INVALID; the table then has no ids).  The engine keeps the id column with the table, an id -> row
+ * table of id_cap words on the device and a live-id bitmap on the host, from which every refusal below is decided before anything
+ * changes and without a synchronisation.  COOK_E_STATE before cook_offers_stage.  cook_offers_stage drops the ids.
+ *
+ * cook_offers_update applies a delta on the device.  THE ORDER RULE (a contract: a node's pods are folded left to right, and a
+ * 0.1-cpu request is not dyadic): surviving pods keep their relative order; added rows go behind the last survivor, in list
+ * order; a pod the watch MODIFIES is a remove plus an add, and it moves to the end; removes apply before adds, so an id may leave
+ * and rejoin in one call.  Every staged pod column moves with its row.  A column the table has and `add` lacks gets, for the
+ * joining rows, what NULL means for it (0; disk: absent, -1); a column `add` carries and the table lacks is refused (stage again).
+ * node_row / node_values replace the listed node rows IN PLACE, column by column under the same rule, the label rows included
+ * (node_values->host NULL: the rows keep their host ids).  The node SET, and with it the offer order, does not change: nodes that
+ * join or leave mean a fresh cook_offers_stage (the offer order is the node-name order, a tie-break contract).
+ * COOK_E_INVALID, nothing changed: an id >= id_cap; an id twice in either list; an added id that is live and does not leave in
+ * this call; node_row out of range or listed twice; a column the table lacks; node_values->n != n_node_rows or another
+ * n_attr_keys; a NULL list behind a count; add without node / cpus / mem / add_id; node_values without cpus / mem.
+ * COOK_E_STATE: before cook_offers_stage + cook_offers_stage_pod_ids.  A remove_id that is not live is no error: it is counted
+ * (remove_missing).  The rows of the last cook_offers_run stay as they are until the next one. */
+typedef struct cook_pod_delta {
+  uint32_t n_remove;
+  const uint32_t* remove_id; /* pods that leave                                                                 */
+  const cook_pods* add;      /* rows that join (add->n of them; NULL: none) ...                                  */
+  const uint32_t* add_id;    /* ... and their ids                                                                */
+  uint32_t n_node_rows;
+  const uint32_t* node_row;  /* node rows replaced in place ...                                                  */
+  const cook_nodes* node_values; /* ... by these (node_values->n == n_node_rows)                                 */
+} cook_pod_delta;
+int cook_offers_stage_pod_ids(cook_engine* e, const uint32_t* pod_id, uint32_t n, uint32_t id_cap);
+int cook_offers_update(cook_engine* e, const cook_pod_delta* d);
+/* the counts of the last delta (cook_offers_update, or a queue cycle's): n_pods the table's rows behind it, n_offers the rows of
+ * the last cook_offers_run / rebuild (0: none yet) */
+typedef struct cook_pod_delta_info {
+  uint32_t removed, remove_missing, added, node_rows, n_pods, n_offers;
+} cook_pod_delta_info;
+int cook_offers_update_info(cook_engine* e, cook_pod_delta_info* out);
+/* the pod table as it stands, list order, in one synchronisation (as cook_cycle_fetch_offers: n is always written; cap < n is
+ * COOK_E_INVALID; a NULL column is skipped; a column the table lacks reads as what NULL means; id without ids: COOK_NONE_U32) */
+typedef struct cook_pod_rows {
+  uint32_t cap, n;
+  uint32_t* node;
+  double* cpus;
+  double* mem;
+  int32_t* gpus;
+  uint32_t* gpu_model;
+  double* disk;
+  uint32_t* disk_type;
+  uint8_t* flags;
+  uint32_t* id;
+} cook_pod_rows;
+int cook_offers_fetch_pods(cook_engine* e, cook_pod_rows* out);
+/* The rows of the engine's last cook_offers_run become the STAGED offers of its cycle in place: what cook_cycle_delta.offers does
+ * from host arrays, with the columns and the with_task_limits meaning of cook_cycle_stage_built_offers.  Tasks, users, jobs,
+ * groups, limiters and reservations stay.  Legal wherever a cook_cycle_update that carries offers is (COOK_E_STATE before a cycle
+ * stage or before cook_offers_run); like it, it ends the standing queue: the next cycle is a rank cycle (cook_cycle_run*).  This
+ * is how a rank cycle of such a pool gets current offers. */
+int cook_cycle_set_built_offers(cook_engine* e, int with_task_limits);
+/* A queue cycle of a pool whose offers are built from its pods: cook_cycle_run_queue_reserve without a host churn, plus the pod
+ * delta and the offer rebuild inside the advance.  The mark-removed step, the groups' fold, the usage carry, the release, the
+ * reservations and the limiters' spend are enqueued first and read the OLD rows (the last cycle's job_to_offer indexes them);
+ * then, where the churn has its place, the delta (pods NULL: none, a rebuild from the table as it stands), the rebuild by the
+ * kernels of cook_offers_run, and the rebuilt rows become the staged offers as by cook_cycle_set_built_offers, in front of the
+ * considerable filters.  The rebuild writes the row buffers the last match read: ONE stream orders it behind every reader, so
+ * there is no second set of rows.  The offer count rides in the advance's one read-back: the call makes exactly as many stream
+ * synchronisations as cook_cycle_run_queue_reserve, and no upload that grows with the cluster.
+ * The offers come from the pods: step->offers, carry->offers = 1 and finished->offers = 1 are COOK_E_INVALID, nothing changed, and
+ * so is everything cook_offers_update refuses.  Cook's own launches are rows of pods->add (add-starting-pods), the finished tasks'
+ * pods are in pods->remove_id; carry->usage, finished->usage, finished->groups, the reservations and the limiters work as in
+ * cook_cycle_run_queue_reserve.  COOK_E_STATE: staged offers that were not built on this engine (cook_cycle_stage_built_offers,
+ * cook_cycle_set_built_offers or this call), a delta without ids.  Afterwards cook_offers_fetch, cook_cycle_fetch_offers,
+ * cook_match_explain, cook_match_metrics, cook_cycle_autoscale and cook_cycle_rebalance_stage describe this cycle's rows.
+ * _multi: the arrays-of-pointers form (an array NULL: that part for no pool; with_task_limits per pool, NULL: 0); the pools run
+ * one after another, each exactly its single call with the placement deferred to cook_cycle_match_multi; returns the first code
+ * that is not COOK_OK, the other pools go on. */
+int cook_cycle_run_queue_pods(cook_engine* e, const cook_queue_step* step, const cook_queue_carry* carry, const cook_finished* finished,
+                              const cook_pod_delta* pods, const cook_reservations* reservations, int with_task_limits,
+                              uint32_t num_considerable);
+int cook_cycle_run_queue_pods_multi(cook_engine** engines, uint32_t n, const cook_queue_step* const* steps,
+                                    const cook_queue_carry* const* carries, const cook_finished* const* finished,
+                                    const cook_pod_delta* const* pods, const cook_reservations* const* reservations,
+                                    const int32_t* with_task_limits, const uint32_t* num_considerable);
+
 /* Number of jobs of the engine's last match (cook_match_run: the staged jobs; cook_cycle_run / the lockstep calls: the
  * considerable jobs actually taken, <= num_considerable): the length cook_match_fetch / cook_cycle_fetch write. */
 int cook_match_count(cook_engine* e, uint32_t* n_jobs);
