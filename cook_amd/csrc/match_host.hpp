@@ -84,6 +84,12 @@ void match_stage_inputs(cook_engine* e, const cook_jobs* j, const cook_offers* o
   if (j->group && g)
     for (unsigned k = 0; k < K; ++k)
       if (j->group[k] != COOK_NONE_U32 && j->group[k] >= G) e->fail(COOK_E_INVALID, "cook_match_stage: group id out of range");
+  // a pool beyond the walk's owner table is refused HERE, with the other checks on the inputs and under the params in force NOW: behind a
+  // refused cook_match_stage the last match and its inputs are whole and can still be fetched (cook_cycle_stage has restaged the rank's
+  // inputs by then, as for its other checks).  match_run_device asks again, since cook_engine_set_params may come in between: a pool staged
+  // under the serial sweep (no such table) and run under the window rounds is refused only there, the last match's state already reset; one
+  // staged under the window rounds is refused here even if the sweep was meant to run it — set the params first
+  if (K) match_check_offer_count(e, M);
   e->placement_drop();  // (the columns below may move: a set-up would point at freed ones)
   reserve_drop(e);      // (the engine's own reservation map and `launched` go with the rows they index)
   MatchIn& in = e->min;

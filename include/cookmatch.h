@@ -560,7 +560,11 @@ int cook_sweep_running(cook_engine* e, const cook_running_set* tasks, const cook
  * (bit 0 resources, bit 1 constraints).  reserved_hosts: hosts reserved by the rebalancer for ANY job.
  * Ties between offers of equal fitness go to the lowest offer INDEX (array position).  The reference's recorded simulator run
  * (simulator_files/example-out-trace.csv) is reproduced row for row when the offers of a cycle are passed in DESCENDING hostname
- * order (ascending order yields the mirror image on identical hosts): that is the order a binding should use. */
+ * order (ascending order yields the mirror image on identical hosts): that is the order a binding should use.
+ * A pool of more offers than the placement walk's offer table holds (about 150 000; the serial sweep and the spreaders have no such
+ * table) is refused with COOK_E_INVALID by the STAGE call (cook_match_stage, cook_cycle_stage and their built-offers forms, cook_match),
+ * under the params in force then: behind a refused cook_match_stage the engine's last match is untouched and cook_match_fetch still
+ * returns it.  cook_match_run asks again under the params in force at the run. */
 int cook_match(cook_engine* e, const cook_jobs* considerable, const cook_offers* offers, const cook_groups* groups,
                const uint32_t* reserved_hosts, uint32_t n_reserved, int32_t* job_to_offer, uint32_t* fail_code,
                uint8_t* head_matched);
